@@ -2,7 +2,7 @@
 """Benchmark of the AMT-SAGA hot path on MI355X: audio windows/sec through the
 detect -> subtract loop (BASELINE.json metric), one process per GPU.
 
-    python bench.py --gpus 1 --steps K --warmup W [--workload c3|c2|c5]
+    python bench.py --gpus 1 --steps K --warmup W [--workload c3|c2|c5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,7 +11,12 @@ already resident in HBM: STFT(2048) -> mag/phase/max -> `iters` x [features ->
 RDCNN heads -> note decision -> guess lookup -> subtract] -> event gather.
 Weak scaling: every rank processes the same number of windows.
 
-Prints ONE JSON line on rank 0 with the driver contract plus
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the driver contract
+(metric, value, unit, ms_per_step, higher_is_better, dtype, the configuration) and nothing it would have to measure
+apart.  --dump-outputs DIR then writes what the last timed step returned (see dump_outputs) as DIR/<name>.npy; the
+inputs and weights are seeded, so two builds can be compared output for output.
+
+--full adds the measurements below, each outside the timed region (--no-extras / --no-cpu-baseline drop some of them):
   roofline      dominant kernel(s) of the step, timed with HIP events recorded around every conv layer in the one-stream
                 measurement pass: conv mode 3 (default) -- the FFT-domain form of the timing heads' 4 x 16 layers (fc_gemm_kernel +
                 fc_row_kernel per layer): algorithmic HBM bytes of the frequency tensors / time; modes 0-2 -- the
@@ -35,6 +40,7 @@ Prints ONE JSON line on rank 0 with the driver contract plus
                           (TranscriptionLoop.run_stream), steady state
   prepare_ms              the untimed per-batch set-up (STFT + song-level CQT normalisers)
   value_prepare_inclusive the same step with that set-up inside the timed region (a fresh batch every step)
+  events_checksum, distinct_decisions   sum and spread of the timed region's event records
 """
 import argparse
 import json
@@ -79,6 +85,53 @@ def build(workload, B):
                              subtract=workload['subtract'], groups=workload['groups'])
     loop.setup_device()
     return p, loop
+
+
+DUMP_BYTES = 48 << 20          # bound of the residual sample --dump-outputs writes (the whole residual is ~2 GB at C3)
+
+
+def dump_outputs(d, events, b):
+    """What a caller of the timed step receives, from its last step: the gathered event records (int32, stored exactly
+    as float64), the residual's per-window maxima, and the residual magnitude spectrogram [k, T, F] of a fixed, seeded
+    sample of this rank's windows (their indices in residual_mag_windows)."""
+    os.makedirs(d, exist_ok=True)
+    B, T, F = b.mag.shape[0], b.mag.shape[1], b.F
+    k = max(1, min(B, DUMP_BYTES // (T * F * 4)))
+    idx = np.sort(np.random.default_rng(0).choice(B, k, replace=False))
+    out = {'events': events.numpy().astype(np.float64),
+           'residual_ref_max': b.ref_max.float().cpu().numpy(),
+           'residual_mag_sample': b.mag[torch.as_tensor(idx, device=b.mag.device), :, :F].float().cpu().numpy(),
+           'residual_mag_windows': idx.astype(np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(d, name + '.npy'), a)
+
+
+def headline(args, wl, p, B, world, dt, conv_mode):
+    """The driver contract's fields of the result line: the rate of the timed region and what it ran."""
+    arith = 2 if conv_mode == 3 else conv_mode
+    return {
+        'metric': 'audio windows/sec (44.1 kHz, 2048-pt STFT) through full detect->subtract loop',
+        'value': round(B * world * args.steps / dt, 2), 'unit': 'windows/s', 'n_gpus': world, 'steps': args.steps,
+        'warmup': args.warmup, 'ms_per_step': round(dt / args.steps * 1e3, 2),
+        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+        'dtype': {0: 'f32', 1: 'f32 (conv: split-bf16 x3 operands, f32 accumulate)',
+                  2: 'f32 (conv: split-fp16 x2 operands, f32 accumulate)',
+                  3: 'f32 (conv: split-fp16 x2 operands, f32 accumulate; 4x16 layers on the large images in the FFT domain)'}[conv_mode],
+        'data': 'synthetic (additive-synth windows, seeded synthetic weights with calibrated BN statistics)',
+        'config': {'workload': wl['name'], 'windows_per_gpu': B, 'n_fft': p.N, 'hop': p.H,
+                   'frames': p.timing_frames, 'iters': wl['iters'], 'heads': list(wl['heads']),
+                   'parallelism': 'windows sharded x%d, event all-gather' % world},
+        'arithmetic_note': {
+            0: 'convolutions on the f32 matrix pipe (v_mfma_f32_32x32x2_f32)',
+            1: 'f32-equivalent: every f32 operand split exactly into 3 bf16 terms, 6 MFMAs per product '
+               'block, f32 accumulate; same parity bars as --conv-mode 0 (tests/test_gpu_rdcnn.py)',
+            2: 'f32-equivalent: every f32 operand = f16 h + 2^-11 f16 l (22 significand bits, per-window power-of-two '
+               'range scaling from measured maxima), 3 MFMAs per product block, f32 accumulate, ~1e-7 rms / <= 2^-21 '
+               'worst case per product; same parity bars as --conv-mode 0 (tests/test_gpu_rdcnn.py); value_f32_mfma '
+               '(--full) is the same step on the f32 MFMA',
+        }[arith] + (' The 32->32 (4x16) layers on the 20x516 images run in the FFT domain (amt_fftconv.hip): 576-point f32 FFTs '
+                    'of channel pairs, per-frequency-pair GEMMs in the same split-fp16 arithmetic; same parity bars.' if conv_mode == 3 else ''),
+    }
 
 
 def _cpu_worker_setup(wl_name, n_fft):
@@ -203,14 +256,20 @@ def main():
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--workload', default='c3', choices=sorted(WORKLOADS))
     ap.add_argument('--windows', type=int, default=0, help='windows per GPU (default: the workload size)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure the rooflines, the extra legs and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned to DIR/<name>.npy')
     ap.add_argument('--cpu-seconds', type=float, default=24.0, help='CPU work of the baseline sample (both legs)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--no-extras', action='store_true',
-                    help='skip the f32-MFMA and H2D-inclusive legs (profiling runs)')
+                    help='with --full: skip the f32-MFMA and H2D-inclusive legs (profiling runs)')
     ap.add_argument('--conv-mode', type=int, default=None, choices=(0, 1, 2, 3),
                     help='convolution arithmetic: 3 = FFT-domain form of the 4 x 16 layers on the large images + split-fp16 elsewhere '
                          '(default), 2 = split-fp16 everywhere, 1 = split-bf16, 0 = f32 MFMA; all f32-equivalent')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     from amt_saga import dist as adist, synth
     rank, world, local = adist.init()
@@ -231,13 +290,14 @@ def main():
                                  groups=wl['groups'], sr=p.sr, device=dev)
     window0 = rank * B
     # song-level constants once per batch (training.py:269-282 computes them once per song): untimed set-up,
-    # reported as prepare_ms
+    # reported as prepare_ms (--full)
     loop.prepare(wave)
     torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    loop.prepare(wave)
-    torch.cuda.synchronize()
-    prepare_ms = (time.perf_counter() - t0) * 1e3
+    if args.full:
+        t0 = time.perf_counter()
+        loop.prepare(wave)
+        torch.cuda.synchronize()
+        prepare_ms = (time.perf_counter() - t0) * 1e3
     refs = loop.refs
     timing_nets = [loop.nets[k] for k in ('timing_start', 'timing_end') if k in loop.nets]
     prof_nets = timing_nets or list(loop.nets.values())
@@ -264,6 +324,13 @@ def main():
     # ---- the timed region: the product as it runs -----------------
     dt, (events, last) = timed_steps(args.steps, step)
     value = B * world * args.steps / dt
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, events, last)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, wl, p, B, world, dt, conv_mode)), flush=True)
+        adist.shutdown()
+        return
     # ---- per-kernel measurement pass, OUTSIDE the timed region: the same steps on ONE stream, so that a kernel's duration
     # (the rooflines' denominator) is that of a kernel that owns the chip, with HIP events around every conv layer and
     # around the STFT / subtract launches (events on the launch stream = torch's current stream)
@@ -566,18 +633,8 @@ def main():
         cpu = cpu_baseline(p, args.workload, wave[:n_cpu].cpu().numpy(), refs_cpu, args.cpu_seconds)
 
     if rank == 0:
-        out = {
-            'metric': 'audio windows/sec (44.1 kHz, 2048-pt STFT) through full detect->subtract loop',
-            'value': round(value, 2), 'unit': 'windows/s', 'n_gpus': world, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': round(dt / args.steps * 1e3, 2),
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': {0: 'f32', 1: 'f32 (conv: split-bf16 x3 operands, f32 accumulate)',
-                      2: 'f32 (conv: split-fp16 x2 operands, f32 accumulate)',
-                      3: 'f32 (conv: split-fp16 x2 operands, f32 accumulate; 4x16 layers on the large images in the FFT domain)'}[conv_mode],
-            'data': 'synthetic (additive-synth windows, seeded synthetic weights with calibrated BN statistics)',
-            'config': {'workload': wl['name'], 'windows_per_gpu': B, 'n_fft': p.N, 'hop': p.H,
-                       'frames': T, 'iters': wl['iters'], 'heads': list(wl['heads']),
-                       'parallelism': 'windows sharded x%d, event all-gather' % world},
+        out = headline(args, wl, p, B, world, dt, conv_mode)
+        out.update({
             # the dominant kernel(s) of the step: in conv mode 3 the FFT-domain layer pair (GEMM + row transforms; bound by
             # the HBM traffic of the frequency tensors), else the largest direct convolution class (matrix pipe), which in
             # mode 3 is reported as roofline_mfma
@@ -600,17 +657,7 @@ def main():
             'events_checksum': int(events.to(torch.int64).sum().item()),
             'distinct_decisions': {k: int(torch.unique(events[:, c]).numel())
                                    for c, k in ((2, 'pitch'), (4, 'velocity'), (5, 'onset_frame'), (6, 'end_frame'))},
-            'arithmetic_note': {
-                0: 'convolutions on the f32 matrix pipe (v_mfma_f32_32x32x2_f32)',
-                1: 'f32-equivalent: every f32 operand split exactly into 3 bf16 terms, 6 MFMAs per product '
-                   'block, f32 accumulate; same parity bars as --conv-mode 0 (tests/test_gpu_rdcnn.py)',
-                2: 'f32-equivalent: every f32 operand = f16 h + 2^-11 f16 l (22 significand bits, per-window power-of-two '
-                   'range scaling from measured maxima), 3 MFMAs per product block, f32 accumulate, ~1e-7 rms / <= 2^-21 '
-                   'worst case per product; same parity bars as --conv-mode 0 (tests/test_gpu_rdcnn.py); value_f32_mfma '
-                   'is the same step on the f32 MFMA',
-            }[arith] + (' The 32->32 (4x16) layers on the 20x516 images run in the FFT domain (amt_fftconv.hip): 576-point f32 FFTs '
-                        'of channel pairs, per-frequency-pair GEMMs in the same split-fp16 arithmetic; same parity bars.' if conv_mode == 3 else ''),
-        }
+        })
         out.update(extras)
         if cpu:
             out['speedup_vs_cpu_baseline'] = round(value / cpu['value'], 1)
