@@ -34,7 +34,7 @@
 // 32-position M-tile and 32 output channels (wider layers are split over blockIdx.y) and walks all
 // taps with v_mfma_f32_16x16x32_f16 on tap pairs; the next chunk's input is requested under the last
 // weight group; small images (H x W <= 64) use the masked form (no halo).  Tile geometry and the
-// masked idea follow conv_bf16x6_kernel (amt_rdcnn.hip).  An earlier two-M-tiles-per-wave kernel on
+// masked idea follow conv_bf16x6_kernel (amt_conv_bf16x6.h).  An earlier two-M-tiles-per-wave kernel on
 // v_mfma_f32_32x32x16_f16 and the experiments around it are recorded in profiles/r01/ablation_f16x3.txt.
 #pragma once
 

@@ -32,3 +32,27 @@ int amt_fftpk_forward_fft(const amt_fftpk_layer *L, const float *in_sp, size_t i
 int amt_fftpk_gemm(const amt_fftpk_layer *L, const float *Xf, const float *amaxf, int B, float *Yf, hipStream_t st);
 int amt_fftpk_inverse_epilogue(const amt_fftpk_layer *L, const float *Yf, const FcEpilogue &ep, int B, float *out_sp, size_t out_stride,
                                float *Xf_next, float *amaxf_next, float *amax_out, hipStream_t st);
+
+// ---- one handle for both forms: amt_rdcnn_forward chains either kind with the same host code -------------------------
+// At most one of row / pk is set; H x W is the layer's image (the packed form has it fixed at 10 x 64).
+struct FcLayer {
+    amt_fftconv_layer *row = nullptr;
+    amt_fftpk_layer *pk = nullptr;
+    int H = 0, W = 0;
+    explicit operator bool() const { return row || pk; }
+};
+static inline size_t fc_freq_floats(const FcLayer &l, int B) {
+    return l.pk ? amt_fftpk_freq_floats(B) : amt_fftconv_freq_floats(B, l.H);
+}
+static inline int fc_forward_fft(const FcLayer &l, const float *in_sp, size_t in_stride, int B, float *Xf, float *amaxf, hipStream_t st) {
+    return l.pk ? amt_fftpk_forward_fft(l.pk, in_sp, in_stride, B, Xf, amaxf, st)
+                : amt_fftconv_forward_fft(l.row, in_sp, in_stride, B, l.H, l.W, Xf, amaxf, st);
+}
+static inline int fc_gemm(const FcLayer &l, const float *Xf, const float *amaxf, int B, float *Yf, hipStream_t st) {
+    return l.pk ? amt_fftpk_gemm(l.pk, Xf, amaxf, B, Yf, st) : amt_fftconv_gemm(l.row, Xf, amaxf, B, l.H, Yf, st);
+}
+static inline int fc_inverse_epilogue(const FcLayer &l, const float *Yf, const FcEpilogue &ep, int B, float *out_sp, size_t out_stride,
+                                      float *Xf_next, float *amaxf_next, float *amax_out, hipStream_t st) {
+    return l.pk ? amt_fftpk_inverse_epilogue(l.pk, Yf, ep, B, out_sp, out_stride, Xf_next, amaxf_next, amax_out, st)
+                : amt_fftconv_inverse_epilogue(l.row, Yf, ep, B, l.H, l.W, out_sp, out_stride, Xf_next, amaxf_next, amax_out, st);
+}

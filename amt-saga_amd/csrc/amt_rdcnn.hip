@@ -1,31 +1,14 @@
-// RDCNN forward (res_net.predict) for gfx950: implicit-GEMM convolutions on the matrix pipe
-// with fused BN + sigmoid (+ shortcut add + BN) epilogues, in three f32-equivalent arithmetics:
-//   mode 2 (default) split-fp16, amt_conv_f16x3.h;  mode 1 split-bf16, conv_bf16x6_kernel below;
-//   mode 0 f32 MFMA, conv_mfma_kernel below (described next).
+// RDCNN forward (res_net.predict) for gfx950, host side: topology walk, weight folding and pre-arrangement, the
+// per-layer launch plan, and the forward walk.  The convolutions are implicit GEMMs on the matrix pipe with fused
+// BN + sigmoid (+ shortcut add + BN) epilogues, in three f32-equivalent arithmetics:
+//   mode 2 (default) split-fp16, amt_conv_f16x3.h;  mode 1 split-bf16, amt_conv_bf16x6.h;  mode 0 f32 MFMA,
+//   amt_conv_f32.h;  mode 3 = mode 2 with the large 4 x 16 layers in the FFT domain (amt_fftconv.h).
+// The first layer, shortcut projection, max-pool, Dense and output kernels are in amt_rdcnn_small.h.
 //
-// Replaces keras Model.predict for the graph built in
-// /root/reference/RDCNN.py:176-233 (+ _add_shortcut :312-335, output scaling
-// :304-310, :591-597) -- see oracle/rdcnn.py for the CPU restatement.
+// Replaces keras Model.predict for the graph built in RDCNN.py:176-233 of the reference (+ _add_shortcut :312-335,
+// output scaling :304-310, :591-597) -- see oracle/rdcnn.py for the CPU restatement.
 //
-// Data layout in HBM: activations NHWC f32, [B][H][W][C]; the flatten order of
-// Keras (H, W, C) is then the memory order, so Dense consumes it as is.
-//
-// Conv kernel (Cin multiple of 32): one 256-thread workgroup computes
-// 128*MT output positions x Cout channels.  GEMM view: M = positions,
-// N = Cout, K = (dy, dx, cin).  v_mfma_f32_32x32x2_f32 (f32 in, f32 acc: a
-// k-ordered fmaf chain per (tap, 32-channel chunk), the chunks' sums added in
-// tap order) -- the contraction the north star puts on MFMA while keeping
-// float parity with the CPU.
-//   * the input tile incl. the conv halo (explicit zeros = Keras "same"
-//     padding, asymmetric for even kernels) is staged once per 32-channel
-//     chunk into LDS as [pos][33] (pad 1 float: A-fragment reads hit 32
-//     distinct banks);
-//   * weights are pre-arranged on the host as [cchunk][tap][c][j][nt] so a
-//     (tap, chunk) slab is one linear copy into a double-buffered LDS slab
-//     and a lane's B fragments for all N-tiles are one ds_read_b32/b64/b128;
-//   * one barrier per tap; 16 k-steps x MT x NT MFMAs between barriers;
-//   * epilogue: acc*s1+t1 -> sigmoid -> (+shortcut)*s2+t2 -> coalesced NHWC
-//     stores (a store instruction = two full 128-B channel rows).
+// All kernels stay in THIS translation unit: the build gives it per-file code generation flags (build.py).
 #include "amt_common.h"
 #include "amt_fftconv.h"
 #include "amt_convh.h"
@@ -34,916 +17,41 @@
 #include <cmath>
 #include <cstdlib>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-#define RD_CC 32           // channels per staged chunk
-#define RD_CSTRIDE 33      // LDS floats per staged position
-#define RD_BN_EPS 1e-3f
-
-struct ConvParams {
-    const float *in;  size_t in_win_stride;      // [B][H][W][CIN]
-    float *out;       size_t out_win_stride;     // [B][H][W][COUT]
-    const float *sc;  size_t sc_win_stride;      // shortcut tensor (same shape as out) or null
-    const float *w;                              // pre-arranged weights
-    const float *s1, *t1, *s2, *t2;              // folded BN (s2/t2 null if no residual)
-    int B, H, W;
-    int TH, TW, NWIN;                            // workgroup tile
-    int tiles_h, tiles_w;
-    int cout_total;                              // channels of the output tensor (>= the kernel's COUT
-                                                 // when the layer is split over blockIdx.y N-slices)
-    // rank-1 shortcut (conv_f16x3s_kernel): the first residual block projects the ONE-channel network
-    // input with a 1x1 kernel + BN (RDCNN.py:328-334); instead of materialising that [H][W][COUT]
-    // tensor the epilogue forms (x * w_c) * s_c + t_c itself -- the operations of proj_kernel
-    const float *sc1 = nullptr; size_t sc1_win_stride = 0;      // [B][H][W] (null: not used)
-    const float *sc1_w = nullptr, *sc1_s = nullptr, *sc1_t = nullptr;   // [COUT]
-    int pad_t = 0, pad_l = 0;                    // TRAIN form of conv_f16x3s_kernel only: rows / columns of padding before the image
-};
-
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + __expf(-v)); }
-
-template <int KH, int KW, int CIN, int COUT, int MT>
-__global__ __launch_bounds__(256) void conv_mfma_kernel(ConvParams p) {
-    constexpr int NT = COUT / 32;
-    constexpr int NCHUNK = CIN / RD_CC;
-    constexpr int NTAPS = KH * KW;
-    constexpr int PCAP = 128 * MT;               // positions per workgroup
-    constexpr int PAD_T = (KH - 1) / 2, PAD_L = (KW - 1) / 2;
-    constexpr int WSLAB = RD_CC * COUT;           // floats per (tap, chunk) weight slab
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float *wbuf = smem;                           // [2][WSLAB]
-    int *pos_sp = reinterpret_cast<int *>(smem + 2 * WSLAB);   // [PCAP] spatial index or -1
-    int *pos_win = pos_sp + PCAP;                 // [PCAP] global window
-    float *in_lds = reinterpret_cast<float *>(pos_win + PCAP); // [POSIN][33]
-
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int THin = p.TH + KH - 1, TWin = p.TW + KW - 1;
-    // block -> (window group, tile row, tile col)
-    int bid = blockIdx.x;
-    const int tc = bid % p.tiles_w; bid /= p.tiles_w;
-    const int tr = bid % p.tiles_h; bid /= p.tiles_h;
-    const int win0 = bid * p.NWIN;
-    const int r0 = tr * p.TH, c0 = tc * p.TW;
-    const int ptile = p.TH * p.TW;
-
-    for (int q = tid; q < PCAP; q += 256) {
-        const int w_ = q / ptile, rem = q - w_ * ptile;
-        const int r = rem / p.TW, c = rem - r * p.TW;
-        const bool ok = w_ < p.NWIN && (win0 + w_) < p.B && (r0 + r) < p.H && (c0 + c) < p.W;
-        pos_sp[q] = ok ? (r0 + r) * p.W + (c0 + c) : -1;
-        pos_win[q] = win0 + w_;
-    }
-    // per-lane LDS base (floats) of the A fragment for each of this wave's M-tiles
-    int abase[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        int q = (wid * MT + mt) * 32 + (lane & 31);
-        int w_ = q / ptile, rem = q - w_ * ptile;
-        int r = rem / p.TW, c = rem - r * p.TW;
-        if (w_ >= p.NWIN) { w_ = 0; r = 0; c = 0; }       // padding rows of the tile: any valid address
-        abase[mt] = ((w_ * THin + r) * TWin + c) * RD_CSTRIDE + (lane >> 5);
-    }
-    f32x16 acc[MT][NT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[mt][nt][e] = 0.f;
-
-    constexpr int WV4 = WSLAB / 4 / 256;          // float4 per thread per slab (1, 2 or 4)
-    static_assert(WSLAB % (4 * 256) == 0, "slab split");
-    // N-slice of this workgroup (layers whose output-tile grid cannot fill the chip are split
-    // over blockIdx.y into COUT-wide channel slices, each with its own weight block)
-    const int cout_off = blockIdx.y * COUT;
-    const float4 *wg4 = reinterpret_cast<const float4 *>(p.w + (size_t)blockIdx.y * ((size_t)CIN * NTAPS * COUT));
-
-    for (int ch = 0; ch < NCHUNK; ++ch) {
-        __syncthreads();                          // previous chunk fully consumed
-        // ---- stage the input tile (32 channels) with its zero halo -------------
-        {
-            const int c4 = tid & 7;               // float4 within the 32 channels
-            const int cl = tid >> 3;              // column lane 0..31
-            for (int wr = 0; wr < p.NWIN * THin; ++wr) {
-                const int w_ = wr / THin, ri = wr - w_ * THin;
-                const int gr = r0 - PAD_T + ri;
-                const int gw = win0 + w_;
-                const bool rok = gr >= 0 && gr < p.H && gw < p.B;
-                const float *src = p.in + (size_t)gw * p.in_win_stride +
-                                   ((size_t)gr * p.W) * CIN + ch * RD_CC + c4 * 4;
-                float *dst = in_lds + (size_t)wr * TWin * RD_CSTRIDE + c4 * 4;
-                for (int ci = cl; ci < TWin; ci += 32) {
-                    const int gc = c0 - PAD_L + ci;
-                    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (rok && gc >= 0 && gc < p.W)
-                        v = *reinterpret_cast<const float4 *>(src + (size_t)gc * CIN);
-                    float *d = dst + ci * RD_CSTRIDE;
-                    d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-                }
-            }
-        }
-        // ---- first weight slab of this chunk ---------------------------------
-        {
-            const float4 *src = wg4 + (size_t)(ch * NTAPS) * (WSLAB / 4);
-            float4 *dst = reinterpret_cast<float4 *>(wbuf);
-#pragma unroll
-            for (int i = 0; i < WV4; ++i) dst[tid + i * 256] = src[tid + i * 256];
-        }
-        __syncthreads();
-        int cur = 0;
-        for (int dy = 0; dy < KH; ++dy) {
-            for (int dx = 0; dx < KW; ++dx) {
-                const int tap = dy * KW + dx;
-                float4 wpre[WV4];
-                const bool more = tap + 1 < NTAPS;
-                if (more) {
-                    const float4 *src = wg4 + (size_t)(ch * NTAPS + tap + 1) * (WSLAB / 4);
-#pragma unroll
-                    for (int i = 0; i < WV4; ++i) wpre[i] = src[tid + i * 256];
-                }
-                const int tapoff = (dy * TWin + dx) * RD_CSTRIDE;
-                const float *wb = wbuf + cur * WSLAB + ((lane >> 5) * 32 + (lane & 31)) * NT;
-                // blocked summation: the 32 products of one (tap, chunk) go through a fresh accumulator (an fmaf
-                // chain of length 32 inside the matrix pipe) which is then added to the running sum -- 64 + 32
-                // roundings on the critical path of a K = 2048 contraction instead of 2048.  A single chain over
-                // all of K (round 1-2) sat 11x farther from the float64 result than numpy's blocked GEMM on the
-                // timing head at N = 2048 (profiles/r02/rdcnn_error_vs_f64.json); OpenBLAS blocks K the same way.
-                f32x16 part[MT][NT];
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) part[mt][nt][e] = 0.f;
-#pragma unroll
-                for (int cp = 0; cp < RD_CC / 2; ++cp) {
-                    float a[MT];
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) a[mt] = in_lds[abase[mt] + tapoff + 2 * cp];
-                    float bfr[NT];
-                    const float *wrow = wb + (2 * cp) * 32 * NT;
-                    if constexpr (NT == 1) {
-                        bfr[0] = wrow[0];
-                    } else if constexpr (NT == 2) {
-                        const float2 t2 = *reinterpret_cast<const float2 *>(wrow);
-                        bfr[0] = t2.x; bfr[1] = t2.y;
-                    } else {
-                        const float4 t4 = *reinterpret_cast<const float4 *>(wrow);
-                        bfr[0] = t4.x; bfr[1] = t4.y; bfr[2] = t4.z; bfr[3] = t4.w;
-                    }
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt)
-                            part[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(
-                                a[mt], bfr[nt], part[mt][nt], 0, 0, 0);
-                }
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) acc[mt][nt][e] = __fadd_rn(acc[mt][nt][e], part[mt][nt][e]);
-                if (more) {
-                    float4 *dst = reinterpret_cast<float4 *>(wbuf + (cur ^ 1) * WSLAB);
-#pragma unroll
-                    for (int i = 0; i < WV4; ++i) dst[tid + i * 256] = wpre[i];
-                }
-                __syncthreads();
-                cur ^= 1;
-            }
-        }
-    }
-    // ---- epilogue ---------------------------------------------------------------
-    const int j = lane & 31;
-    const int CT = p.cout_total;
-    float s1[NT], t1[NT], s2[NT], t2[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        s1[nt] = p.s1[cout_off + nt * 32 + j]; t1[nt] = p.t1[cout_off + nt * 32 + j];
-        s2[nt] = p.s2 ? p.s2[cout_off + nt * 32 + j] : 1.f;
-        t2[nt] = p.t2 ? p.t2[cout_off + nt * 32 + j] : 0.f;
-    }
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-            const int q = (wid * MT + mt) * 32 + row;
-            const int sp = pos_sp[q];
-            if (sp < 0) continue;
-            const int gw = pos_win[q];
-            float *o = p.out + (size_t)gw * p.out_win_stride + (size_t)sp * CT + cout_off + j;
-            const float *scp = p.sc ? p.sc + (size_t)gw * p.sc_win_stride + (size_t)sp * CT + cout_off + j : nullptr;
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                float v = sigmoidf_(acc[mt][nt][e] * s1[nt] + t1[nt]);
-                if (scp) v = (v + scp[nt * 32]) * s2[nt] + t2[nt];
-                o[nt * 32] = v;
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------
-// Split-bf16 convolution ("bf16x6"): fp32-equivalent products on the bf16 MFMA pipe.
-// Every f32 operand x is split exactly into three bf16 terms x = x1 + x2 + x3
-// (8 + 8 + 8 mantissa bits); the product x*y is the six terms with i + j <= 4
-// (x1y1, x1y2, x2y1, x1y3, x2y2, x3y1), each exact in the MFMA's f32 accumulate; the
-// dropped terms are <= 2^-26 |xy|, below f32 rounding.  Six v_mfma_f32_32x32x16_bf16
-// per 16-deep k-block replace eight v_mfma_f32_32x32x2_f32: 2.67x fewer matrix-pipe
-// cycles at f32 accuracy (bf16 MFMA = 16x the f32 MFMA rate, MI355X_MICROARCH.md).
-//   * 512-thread workgroup, 8 waves x one 32-position M-tile; same tile geometry,
-//     halo staging and epilogue as the f32 kernel;
-//   * activations stay f32 in HBM and are split once per workgroup while staging
-//     into LDS as [pos][plane(3)][32 ch] bf16 (208-B pitch: conflict-free
-//     ds_read_b128 A fragments, lane = position, 8 consecutive channels);
-//   * weights are split on the host and laid out so a (tap, k-block, plane, N-tile)
-//     fragment is one conflict-free ds_read_b128 per lane.
-// ---------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-#define BX_CC 16                             // channels per staged chunk (one bf16 k-block)
-#define BX_PSTRIDE 112                      // bytes per staged position: 3 planes x 16 ch x 2 B + 16 pad
-__host__ __device__ __forceinline__ int bx_row_pitch(int TW, int TWin) {
-    return TWin + (((TW - TWin) % 16) + 16) % 16;
-}
-
-__host__ __device__ __forceinline__ unsigned short amt_f2bf(float x) {
-    unsigned int u;
-#ifdef __HIP_DEVICE_COMPILE__
-    u = __float_as_uint(x);
-#else
-    memcpy(&u, &x, 4);
-#endif
-    u += 0x7FFFu + ((u >> 16) & 1u);         // round to nearest even
-    return (unsigned short)(u >> 16);
-}
-__host__ __device__ __forceinline__ float amt_bf2f(unsigned short h) {
-    unsigned int u = ((unsigned int)h) << 16;
-#ifdef __HIP_DEVICE_COMPILE__
-    return __uint_as_float(u);
-#else
-    float f; memcpy(&f, &u, 4); return f;
-#endif
-}
-__host__ __device__ __forceinline__ void amt_split3(float x, unsigned short &h1, unsigned short &h2,
-                                                    unsigned short &h3) {
-    h1 = amt_f2bf(x);
-    const float r1 = x - amt_bf2f(h1);
-    h2 = amt_f2bf(r1);
-    const float r2 = r1 - amt_bf2f(h2);
-    h3 = amt_f2bf(r2);
-}
-
-// MASKED = true is the small-image form (whole H x W image of NWIN windows per workgroup):
-// the LDS tile holds only real positions plus one all-zero position, and every tap's A
-// fragment address is chosen per lane (in-bounds neighbour or the zero position), so the
-// "same" padding costs no LDS -- a 5x8 image with a 4x16 kernel would otherwise stage 4.6x its
-// size in halo zeros.  Layers are additionally split over blockIdx.y into COUT-wide slices.
-template <int KH, int KW, int CIN, int COUT, bool MASKED>
-__global__ __launch_bounds__(512, 4) void conv_bf16x6_kernel(ConvParams p, const uint4 *__restrict__ w16s) {
-    // Geometry: 8 waves x one 32-position M-tile = 256 output positions per workgroup; the
-    // contraction is walked in 16-channel chunks (one bf16 k-block per tap), so the staged
-    // input tile is [pos][plane(3)][16 ch] bf16 = 112 B per position and TWO workgroups fit
-    // a CU: one stages / stores while the other keeps the matrix pipe busy.
-    constexpr int NT = COUT / 32;
-    constexpr int NCHUNK = CIN / BX_CC;
-    constexpr int NTAPS = KH * KW;
-    constexpr int PCAP = 256;
-    constexpr int PAD_T = (KH - 1) / 2, PAD_L = (KW - 1) / 2;
-    constexpr int TPS = (NT == 1 && NTAPS % 2 == 0) ? 2 : 1;       // taps per weight slab
-    constexpr int NSLAB = NTAPS / TPS;
-    constexpr int SLAB_V4 = TPS * 3 * NT * 64;                      // uint4 per slab (fragment = 64 lanes x 16 B)
-    constexpr int WV4 = (SLAB_V4 + 511) / 512;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    uint4 *wbuf = reinterpret_cast<uint4 *>(smem);                  // [3][SLAB_V4]
-    int *pos_sp = reinterpret_cast<int *>(wbuf + 3 * SLAB_V4);      // [PCAP]
-    int *pos_win = pos_sp + PCAP;
-    char *in_lds = reinterpret_cast<char *>(pos_win + PCAP);        // [POSIN][112 B]
-
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int THin = MASKED ? p.TH : p.TH + KH - 1, TWin = MASKED ? p.TW : p.TW + KW - 1;
-    // LDS row pitch (in positions) == TW (mod 16): consecutive flattened tile positions stay an
-    // odd number (7) of 16-byte slots apart across the row wrap -> conflict-free b128 reads
-    const int RP = MASKED ? p.TW : bx_row_pitch(p.TW, TWin);
-    const int cout_off = blockIdx.y * COUT;                         // N-slice of this workgroup
-    const uint4 *w16 = w16s + (size_t)blockIdx.y * ((size_t)NCHUNK * NSLAB * SLAB_V4);
-    int bid = blockIdx.x;
-    const int tc = bid % p.tiles_w; bid /= p.tiles_w;
-    const int tr = bid % p.tiles_h; bid /= p.tiles_h;
-    const int win0 = bid * p.NWIN;
-    const int r0 = tr * p.TH, c0 = tc * p.TW;
-    const int ptile = p.TH * p.TW;
-
-    for (int q = tid; q < PCAP; q += 512) {
-        const int w_ = q / ptile, rem = q - w_ * ptile;
-        const int r = rem / p.TW, c = rem - r * p.TW;
-        const bool ok = w_ < p.NWIN && (win0 + w_) < p.B && (r0 + r) < p.H && (c0 + c) < p.W;
-        pos_sp[q] = ok ? (r0 + r) * p.W + (c0 + c) : -1;
-        pos_win[q] = win0 + w_;
-    }
-    int abase, lr, lc;                                              // lane's LDS base and tile coords
-    {
-        int q = wid * 32 + (lane & 31);
-        int w_ = q / ptile, rem = q - w_ * ptile;
-        int r = rem / p.TW, c = rem - r * p.TW;
-        if (w_ >= p.NWIN) { w_ = 0; r = 0; c = 0; }
-        abase = ((w_ * THin + r) * RP + c) * BX_PSTRIDE + (lane >> 5) * 16;
-        lr = r; lc = c;
-    }
-    const int zero_off = p.NWIN * THin * RP * BX_PSTRIDE + (lane >> 5) * 16;   // MASKED: the zero position
-    f32x16 acc[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[nt][e] = 0.f;
-
-    for (int ch = 0; ch < NCHUNK; ++ch) {
-        __syncthreads();
-        // ---- stage + split the input tile (16 channels) --------------------------------
-        // work item = (halo row, column, 8-channel half); items are dealt round-robin to the
-        // 512 threads and ALL of a thread's global loads are issued before the first split,
-        // so the tile costs one memory latency instead of one per halo row.
-        {
-            const int nrow = p.NWIN * THin;
-            const int items = nrow * TWin * 2;
-            constexpr int MAXIT = 2;
-            for (int it0 = 0; it0 < items; it0 += 512 * MAXIT) {
-                float4 v0[MAXIT], v1[MAXIT];
-                int dsto[MAXIT];
-#pragma unroll
-                for (int u = 0; u < MAXIT; ++u) {
-                    const int it = it0 + u * 512 + tid;
-                    v0[u] = make_float4(0.f, 0.f, 0.f, 0.f); v1[u] = v0[u]; dsto[u] = -1;
-                    if (it < items) {
-                        const int cg = it & 1;
-                        const int pc = it >> 1;
-                        const int wr = pc / TWin, ci = pc - wr * TWin;
-                        const int w_ = wr / THin, ri = wr - w_ * THin;
-                        const int gr = r0 + ri - (MASKED ? 0 : PAD_T), gc = c0 + ci - (MASKED ? 0 : PAD_L), gw = win0 + w_;
-                        dsto[u] = (wr * RP + ci) * BX_PSTRIDE + cg * 16;
-                        if (gr >= 0 && gr < p.H && gw < p.B && gc >= 0 && gc < p.W) {
-                            const float4 *src = reinterpret_cast<const float4 *>(
-                                p.in + (size_t)gw * p.in_win_stride + ((size_t)gr * p.W + gc) * CIN + ch * BX_CC + cg * 8);
-                            v0[u] = src[0]; v1[u] = src[1];
-                        }
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < MAXIT; ++u) {
-                    if (dsto[u] < 0) continue;
-                    const float v[8] = {v0[u].x, v0[u].y, v0[u].z, v0[u].w, v1[u].x, v1[u].y, v1[u].z, v1[u].w};
-                    unsigned short h[3][8];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) amt_split3(v[e], h[0][e], h[1][e], h[2][e]);
-                    char *dst = in_lds + dsto[u];
-#pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) {
-                        uint4 pk;
-                        pk.x = h[pl][0] | ((unsigned)h[pl][1] << 16);
-                        pk.y = h[pl][2] | ((unsigned)h[pl][3] << 16);
-                        pk.z = h[pl][4] | ((unsigned)h[pl][5] << 16);
-                        pk.w = h[pl][6] | ((unsigned)h[pl][7] << 16);
-                        *reinterpret_cast<uint4 *>(dst + pl * 32) = pk;
-                    }
-                }
-            }
-        }
-        if (MASKED && tid < 7) {                                     // the all-zero position (112 B)
-            *reinterpret_cast<uint4 *>(in_lds + p.NWIN * THin * RP * BX_PSTRIDE + tid * 16) = make_uint4(0, 0, 0, 0);
-        }
-        // ---- K loop over weight slabs: 3 LDS buffers, global prefetch two slabs ahead ------
-        //  step s: issue the loads of slab s+2 (registers), run slab s from LDS, then park
-        //  slab s+1 (loaded during step s-1: two slab-times of latency budget) into LDS.
-        //  The loads are inline asm on purpose: hipcc sinks an ordinary prefetch load down to
-        //  its use and waits vmcnt(0) there (and it waits vmcnt(0) before every ds_read while a
-        //  global_load_lds is in flight).  The kernel must stay spill-free: a spill of an
-        //  in-flight asm destination would save stale data (checked by the build).
-        {
-            const uint4 *src = w16 + (size_t)(ch * NSLAB) * SLAB_V4;
-            for (int i = tid; i < SLAB_V4; i += 512) wbuf[i] = src[i];
-        }
-        u32x4 wpa[WV4], wpb[WV4];
-        auto issue = [&](u32x4 (&wp)[WV4], int slab) {
-            const uint4 *src = w16 + (size_t)(ch * NSLAB + slab) * SLAB_V4;
-#pragma unroll
-            for (int i = 0; i < WV4; ++i) {
-                const uint4 *ptr = src + min(tid + i * 512, SLAB_V4 - 1);
-                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(wp[i]) : "v"(ptr) : "memory");
-            }
-        };
-        auto park = [&](u32x4 (&wp)[WV4], int slab) {
-            u32x4 *dst = reinterpret_cast<u32x4 *>(wbuf + (slab % 3) * SLAB_V4);
-#pragma unroll
-            for (int i = 0; i < WV4; ++i)
-                if (tid + i * 512 < SLAB_V4) dst[tid + i * 512] = wp[i];
-        };
-        if (NSLAB > 1) issue(wpa, 1);                          // slab 1, parked at the end of step 0
-        __syncthreads();
-        auto step = [&](int s_, u32x4 (&w_next)[WV4], u32x4 (&w_new)[WV4]) {
-            if (s_ + 2 < NSLAB) issue(w_new, s_ + 2);
-            const uint4 *wb = wbuf + (s_ % 3) * SLAB_V4 + lane;
-            union U { uint4 u; bf16x8 v; };
-            U a[TPS][3];
-            U b[TPS][3][NT];
-            {
-#pragma unroll
-                for (int tt = 0; tt < TPS; ++tt) {
-                    const int tap = s_ * TPS + tt;
-                    const int dy = tap / KW, dx = tap - dy * KW;
-                    const char *ab;
-                    if constexpr (MASKED) {
-                        const int rr = lr + dy - PAD_T, cc = lc + dx - PAD_L;
-                        const bool inb = (unsigned)rr < (unsigned)p.H && (unsigned)cc < (unsigned)p.W;
-                        ab = in_lds + (inb ? abase + ((dy - PAD_T) * RP + (dx - PAD_L)) * BX_PSTRIDE : zero_off);
-                    } else {
-                        ab = in_lds + abase + (dy * RP + dx) * BX_PSTRIDE;
-                    }
-#pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) {
-                        a[tt][pl].u = *reinterpret_cast<const uint4 *>(ab + pl * 32);
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt) b[tt][pl][nt].u = wb[((tt * 3 + pl) * NT + nt) * 64];
-                    }
-                }
-            }
-            {
-#pragma unroll
-                for (int tt = 0; tt < TPS; ++tt)
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-                        // smallest terms first
-                        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tt][2].v, b[tt][0][nt].v, acc[nt], 0, 0, 0);
-                        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tt][1].v, b[tt][1][nt].v, acc[nt], 0, 0, 0);
-                        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tt][0].v, b[tt][2][nt].v, acc[nt], 0, 0, 0);
-                        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tt][1].v, b[tt][0][nt].v, acc[nt], 0, 0, 0);
-                        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tt][0].v, b[tt][1][nt].v, acc[nt], 0, 0, 0);
-                        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tt][0].v, b[tt][0][nt].v, acc[nt], 0, 0, 0);
-                    }
-            }
-            __builtin_amdgcn_sched_barrier(0);       // the MFMA chain stays above the slab hand-over
-            if (s_ + 1 < NSLAB) {
-                // retire slab s+1's loads; slab s+2's (the WV4 newest) may stay in flight
-                if (s_ + 2 < NSLAB) {
-                    if constexpr (WV4 == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-                    else if constexpr (WV4 == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-                    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                } else {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                }
-                park(w_next, s_ + 1);
-            }
-            __syncthreads();
-        };
-        static_assert(NSLAB % 2 == 0, "slab loop is unrolled by two");
-        for (int s_ = 0; s_ < NSLAB; s_ += 2) {
-            step(s_, wpa, wpb);
-            step(s_ + 1, wpb, wpa);
-        }
-    }
-    // ---- epilogue (as in the f32 kernel, MT = 1) ---------------------------------------------
-    const int j = cout_off + (lane & 31);
-    float s1[NT], t1[NT], s2[NT], t2[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        s1[nt] = p.s1[nt * 32 + j]; t1[nt] = p.t1[nt * 32 + j];
-        s2[nt] = p.s2 ? p.s2[nt * 32 + j] : 1.f;
-        t2[nt] = p.t2 ? p.t2[nt * 32 + j] : 0.f;
-    }
-    // per batch of EPB rows: all shortcut loads first, then the arithmetic and the stores
-    constexpr int EPB = 4;
-#pragma unroll
-    for (int half = 0; half < 16 / EPB; ++half) {
-        int spq[EPB], gwq[EPB];
-        float scv[EPB][NT];
-#pragma unroll
-        for (int e8 = 0; e8 < EPB; ++e8) {
-            const int e = half * EPB + e8;
-            const int row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-            const int q = wid * 32 + row;
-            spq[e8] = pos_sp[q];
-            gwq[e8] = pos_win[q];
-        }
-        if (p.sc) {
-#pragma unroll
-            for (int e8 = 0; e8 < EPB; ++e8) {
-                const float *scp = p.sc + (size_t)gwq[e8] * p.sc_win_stride + (size_t)max(spq[e8], 0) * p.cout_total + j;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) scv[e8][nt] = spq[e8] >= 0 ? scp[nt * 32] : 0.f;
-            }
-        }
-#pragma unroll
-        for (int e8 = 0; e8 < EPB; ++e8) {
-            const int e = half * EPB + e8;
-            if (spq[e8] < 0) continue;
-            float *o = p.out + (size_t)gwq[e8] * p.out_win_stride + (size_t)spq[e8] * p.cout_total + j;
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                float v = sigmoidf_(acc[nt][e] * s1[nt] + t1[nt]);
-                if (p.sc) v = (v + scv[e8][nt]) * s2[nt] + t2[nt];
-                o[nt * 32] = v;
-            }
-        }
-    }
-}
-
+#include "amt_conv_f32.h"
+#include "amt_conv_bf16x6.h"
 #include "amt_conv_f16x3.h"
+#include "amt_rdcnn_small.h"
 
-// ---- first layer (Cin = 1): direct convolution on the VALU ---------------------
-// A workgroup walks row tiles of 256/COUT*4 output columns of one window row.  The
-// input rows (with the zero halo) and all weights sit in LDS; thread = (column
-// group, cout) computes 4 consecutive columns x 1 channel, so one weight read
-// feeds 4 FMAs and the input reads are wave broadcasts.  Stores are coalesced NHWC.
-struct Conv1Params {
-    const float *in; size_t in_win_stride;       // [B][H][W]
-    float *out; size_t out_win_stride;
-    const float *sc; size_t sc_win_stride;
-    const float *w;                              // [KH*KW][COUT]
-    const float *s1, *t1, *s2, *t2;
-    int B, H, W, KH, KW, COUT;
-    float *amax_out = nullptr;                   // [B] max |output| per window (atomicMax; conv1_mfma_kernel) or null
-};
-#define C1_PPT 4
-__global__ __launch_bounds__(256) void conv1_kernel(Conv1Params p) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int ntap = p.KH * p.KW;
-    const int groups = 256 / p.COUT;             // column groups per workgroup
-    const int TWc = groups * C1_PPT;             // output columns per tile
-    const int XW = TWc + p.KW - 1;               // staged input columns
-    float *wl = smem;                            // [ntap][COUT]
-    float *xt = smem + ntap * p.COUT;            // [KH][XW]
-    for (int i = threadIdx.x; i < ntap * p.COUT; i += 256) wl[i] = p.w[i];
-    const int pad_t = (p.KH - 1) / 2, pad_l = (p.KW - 1) / 2;
-    const int co = threadIdx.x % p.COUT;
-    const int pg = threadIdx.x / p.COUT;
-    const int tiles_w = (p.W + TWc - 1) / TWc;
-    const long total = (long)p.B * p.H * tiles_w;
-    const float s1 = p.s1[co], t1 = p.t1[co];
-    const float s2 = p.s2 ? p.s2[co] : 1.f, t2 = p.t2 ? p.t2[co] : 0.f;
-    for (long tile = blockIdx.x; tile < total; tile += gridDim.x) {
-        const int tc = (int)(tile % tiles_w);
-        long rest = tile / tiles_w;
-        const int r = (int)(rest % p.H);
-        const int b = (int)(rest / p.H);
-        const int c0 = tc * TWc;
-        const float *x = p.in + (size_t)b * p.in_win_stride;
-        __syncthreads();                         // previous tile consumed (and wl visible)
-        for (int i = threadIdx.x; i < p.KH * XW; i += 256) {
-            const int dy = i / XW, cx = i - dy * XW;
-            const int gr = r + dy - pad_t, gc = c0 + cx - pad_l;
-            xt[i] = (gr >= 0 && gr < p.H && gc >= 0 && gc < p.W) ? x[(size_t)gr * p.W + gc] : 0.f;
-        }
-        __syncthreads();
-        float acc[C1_PPT];
-#pragma unroll
-        for (int q = 0; q < C1_PPT; ++q) acc[q] = 0.f;
-        for (int dy = 0; dy < p.KH; ++dy) {
-            const float *xr = xt + dy * XW + pg * C1_PPT;
-            const float *wr = wl + dy * p.KW * p.COUT + co;
-            for (int dx = 0; dx < p.KW; ++dx) {
-                const float wv = wr[dx * p.COUT];
-#pragma unroll
-                for (int q = 0; q < C1_PPT; ++q) acc[q] = fmaf(xr[dx + q], wv, acc[q]);
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < C1_PPT; ++q) {
-            const int c = c0 + pg * C1_PPT + q;
-            if (c >= p.W) continue;
-            const size_t sp = (size_t)r * p.W + c;
-            float v = sigmoidf_(acc[q] * s1 + t1);
-            if (p.sc) v = (v + p.sc[(size_t)b * p.sc_win_stride + sp * p.COUT + co]) * s2 + t2;
-            p.out[(size_t)b * p.out_win_stride + sp * p.COUT + co] = v;
-        }
-    }
-}
-
-// ---- first layer on the matrix pipe (Cout = 32) ---------------------------------------------
-// GEMM view: M = output positions, N = 32 filters, K = KH*KW taps; v_mfma_f32_32x32x2_f32 (f32
-// in, f32 accumulate: the same k-ordered fmaf chain as conv1_kernel).  The whole [K][32] kernel
-// lives in K/2 B-fragment registers per lane; an A fragment is one ds_read_b32 of the
-// single-channel input tile (lane = position, lane half = the odd tap of a tap pair, i.e. the
-// next column).  A workgroup (4 waves) owns a TH x TW tile of <= 512 positions = <= 16 M-tiles,
-// wave w takes M-tiles w, w+4, ...; workgroups walk the tiles grid-stride.
-#define C1M_PCAP 512
-template <int KH, int KW>
-__global__ __launch_bounds__(256) void conv1_mfma_kernel(Conv1Params p, int TH, int TW, int tiles_h,
-                                                          int tiles_w) {
-    constexpr int K = KH * KW, NK2 = K / 2;
-    static_assert(K % 2 == 0 && KW % 2 == 0, "tap pairs share a kernel row");
-    constexpr int PAD_T = (KH - 1) / 2, PAD_L = (KW - 1) / 2;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int RPW = TW + KW - 1, THin = TH + KH - 1;
-    int *pos_rc = reinterpret_cast<int *>(smem);            // [PCAP] r | c << 16 (tile-local)
-    int *pos_sp = pos_rc + C1M_PCAP;                         // [PCAP] global spatial index or -1
-    float *tpatch = reinterpret_cast<float *>(pos_sp + C1M_PCAP);   // [4 waves][32][HX_TPITCH]
-    float *xt = tpatch + 4 * 32 * HX_TPITCH;                 // [THin][RPW]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    float *tb = tpatch + wid * 32 * HX_TPITCH;
-    const int c4 = (lane & 7) * 4;
-    const int PT = TH * TW, nmt = (PT + 31) >> 5;
-    for (int q = tid; q < C1M_PCAP; q += 256) {
-        const int r = q / TW, c = q - r * TW;
-        pos_rc[q] = q < PT ? (r | (c << 16)) : -1;
-    }
-    const int co = lane & 31;
-    float bq[NK2];
-#pragma unroll
-    for (int i = 0; i < NK2; ++i) bq[i] = p.w[(2 * i + (lane >> 5)) * 32 + co];
-    const float s1 = p.s1[co], t1 = p.t1[co];
-    float4 s2v = make_float4(1.f, 1.f, 1.f, 1.f), t2v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p.s2) s2v = *reinterpret_cast<const float4 *>(p.s2 + c4);
-    if (p.t2) t2v = *reinterpret_cast<const float4 *>(p.t2 + c4);
-    const long total = (long)p.B * tiles_h * tiles_w;
-    for (long tile = blockIdx.x; tile < total; tile += gridDim.x) {
-        const int tc = (int)(tile % tiles_w);
-        const long rest = tile / tiles_w;
-        const int tr = (int)(rest % tiles_h);
-        const int b = (int)(rest / tiles_h);
-        const int r0 = tr * TH, c0 = tc * TW;
-        const float *x = p.in + (size_t)b * p.in_win_stride;
-        __syncthreads();                                     // previous tile consumed (pos_rc visible)
-        for (int i = tid; i < THin * RPW; i += 256) {
-            const int ri = i / RPW, ci = i - ri * RPW;
-            const int gr = r0 + ri - PAD_T, gc = c0 + ci - PAD_L;
-            xt[i] = (gr >= 0 && gr < p.H && gc >= 0 && gc < p.W) ? x[(size_t)gr * p.W + gc] : 0.f;
-        }
-        for (int q = tid; q < C1M_PCAP; q += 256) {
-            const int rc = pos_rc[q];
-            const int r = r0 + (rc & 0xFFFF), c = c0 + (rc >> 16);
-            pos_sp[q] = (rc >= 0 && r < p.H && c < p.W) ? r * p.W + c : -1;
-        }
-        __syncthreads();
-        float tmax = 0.f;                                    // max |output| of this wave's share of the tile
-        for (int mt = wid; mt < nmt; mt += 4) {
-            const int rc = pos_rc[mt * 32 + (lane & 31)];
-            const int abase = rc >= 0 ? (rc & 0xFFFF) * RPW + (rc >> 16) + (lane >> 5) : (lane >> 5);
-            f32x16 acc;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-            for (int i = 0; i < NK2; ++i) {
-                constexpr int dummy = 0; (void)dummy;
-                const int dy = (2 * i) / KW, dx = (2 * i) % KW;
-                const float a = xt[abase + dy * RPW + dx];
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bq[i], acc, 0, 0, 0);
-            }
-            // turn the 32 x 32 tile through a wave-private LDS patch: 16-byte stores, 4 channels per lane
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-                tb[row * HX_TPITCH + co] = sigmoidf_(acc[e] * s1 + t1);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int row = (lane >> 3) + 8 * i;
-                const int sp = pos_sp[mt * 32 + row];
-                float4 v = *reinterpret_cast<const float4 *>(tb + row * HX_TPITCH + c4);
-                if (sp < 0) continue;
-                if (p.sc) {
-                    const float4 sc = *reinterpret_cast<const float4 *>(p.sc + (size_t)b * p.sc_win_stride + (size_t)sp * 32 + c4);
-                    v.x = (v.x + sc.x) * s2v.x + t2v.x; v.y = (v.y + sc.y) * s2v.y + t2v.y;
-                    v.z = (v.z + sc.z) * s2v.z + t2v.z; v.w = (v.w + sc.w) * s2v.w + t2v.w;
-                }
-                tmax = fmaxf(tmax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-                *reinterpret_cast<float4 *>(p.out + (size_t)b * p.out_win_stride + (size_t)sp * 32 + c4) = v;
-            }
-        }
-        if (p.amax_out) {                                    // one window per tile
-            tmax = wave_max(tmax);
-            if (lane == 0) atomicMax(reinterpret_cast<int *>(p.amax_out) + b, __float_as_int(tmax));
-        }
-    }
-}
-// tile of <= 512 positions that needs the fewest 32-position M-tiles over the image
-static void choose_tile1(int H, int W, int *TH_, int *TW_) {
-    long best = -1;
-    for (int TH = 1; TH <= H && TH <= C1M_PCAP; ++TH) {
-        int TWmax = std::min(W, C1M_PCAP / TH);
-        for (int TW = std::max(1, TWmax - 40); TW <= TWmax; ++TW) {
-            const long tiles = (long)((H + TH - 1) / TH) * ((W + TW - 1) / TW);
-            const long cost = tiles * ((TH * TW + 31) / 32);
-            if (best < 0 || cost < best) { best = cost; *TH_ = TH; *TW_ = TW; }
-        }
-    }
-}
-
-// ---- shortcut projection: BN(avgpool(conv1x1(x)))  (RDCNN.py:328-334) -----------
-// The 1x1 convolution and the average pool commute; pooling first cuts the
-// contraction work by the pool area.  A workgroup owns <= 64 output columns of one
-// output row: phase 1 pools the inputs into LDS (coalesced over channels), phase 2
-// contracts the pooled vectors with the [CIN][COUT] kernel (coalesced over cout).
-struct ProjParams {
-    const float *in; size_t in_win_stride;       // [B][H][W][CIN]
-    float *out; size_t out_win_stride;           // [B][HO][WO][COUT]
-    const float *w;                              // [CIN][COUT] or null (identity channels)
-    const float *s, *t;                          // folded: out = s*(sum) + t  (bias inside t)
-    int B, H, W, CIN, COUT, PH, PW, HO, WO;
-};
-#define PJ_TW 64
-__global__ __launch_bounds__(256) void proj_kernel(ProjParams p) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];   // [PJ_TW][CIN]
-    const int wo0 = blockIdx.x * PJ_TW;
-    const int ho = blockIdx.y, b = blockIdx.z;
-    const int nwo = min(PJ_TW, p.WO - wo0);
-    const float inv = 1.0f / (float)(p.PH * p.PW);
-    const float *x = p.in + (size_t)b * p.in_win_stride;
-    for (int i = threadIdx.x; i < nwo * p.CIN; i += 256) {
-        const int wl = i / p.CIN, ci = i - wl * p.CIN;
-        const int wo = wo0 + wl;
-        float a = 0.f;
-        for (int dy = 0; dy < p.PH; ++dy)
-            for (int dx = 0; dx < p.PW; ++dx)
-                a += x[((size_t)(ho * p.PH + dy) * p.W + (wo * p.PW + dx)) * p.CIN + ci];
-        smem[i] = a * inv;
-    }
-    __syncthreads();
-    // four consecutive output channels per thread: 16-byte weight loads and output stores
-    float *o = p.out + (size_t)b * p.out_win_stride + ((size_t)ho * p.WO + wo0) * p.COUT;
-    const int C4 = p.COUT >> 2;
-    for (int i = threadIdx.x; i < nwo * C4; i += 256) {
-        const int wl = i / C4, co = (i - wl * C4) << 2;
-        float4 acc;
-        if (p.w) {
-            acc = make_float4(0.f, 0.f, 0.f, 0.f);
-            const float *pv = smem + wl * p.CIN;
-            for (int ci = 0; ci < p.CIN; ++ci) {
-                const float4 wv = *reinterpret_cast<const float4 *>(p.w + (size_t)ci * p.COUT + co);
-                const float a = pv[ci];
-                acc.x = fmaf(a, wv.x, acc.x); acc.y = fmaf(a, wv.y, acc.y);
-                acc.z = fmaf(a, wv.z, acc.z); acc.w = fmaf(a, wv.w, acc.w);
-            }
-        } else {
-            acc = *reinterpret_cast<const float4 *>(smem + wl * p.CIN + co);
-        }
-        const float4 sv = *reinterpret_cast<const float4 *>(p.s + co);
-        const float4 tv = *reinterpret_cast<const float4 *>(p.t + co);
-        acc.x = acc.x * sv.x + tv.x; acc.y = acc.y * sv.y + tv.y;
-        acc.z = acc.z * sv.z + tv.z; acc.w = acc.w * sv.w + tv.w;
-        *reinterpret_cast<float4 *>(o + (size_t)wl * p.COUT + co) = acc;
-    }
-}
-
-// ---- MaxPooling2D (valid, stride = pool) ------------------------------------------
-__global__ __launch_bounds__(256) void maxpool_kernel(const float *__restrict__ in,
-                                                       size_t in_win_stride, float *__restrict__ out,
-                                                       size_t out_win_stride, int B, int H, int W,
-                                                       int C, int PH, int PW, int HO, int WO) {
-    // four channels per thread (C is a multiple of 32): 16-byte loads and stores
-    const int C4 = C >> 2;
-    const size_t total = (size_t)B * HO * WO * C4;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C4) << 2;
-        size_t r = i / C4;
-        const int wo = (int)(r % WO); r /= WO;
-        const int ho = (int)(r % HO);
-        const int b = (int)(r / HO);
-        const float *x = in + (size_t)b * in_win_stride;
-        float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-        for (int dy = 0; dy < PH; ++dy)
-            for (int dx = 0; dx < PW; ++dx) {
-                const float4 v = *reinterpret_cast<const float4 *>(
-                    x + ((size_t)(ho * PH + dy) * W + (wo * PW + dx)) * C + c);
-                m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
-            }
-        *reinterpret_cast<float4 *>(out + (size_t)b * out_win_stride + ((size_t)ho * WO + wo) * C + c) = m;
-    }
-}
-
-// ---- Dense: C[M][N] = act(A[M][K] B[K][N] + bias[N]) on v_mfma_f32_32x32x2_f32 -----
-// M = windows is small (<= 512 per chunk) and N = 300, so the grid of output tiles is
-// tiny; to fill the chip a workgroup owns one 32x32 output tile and its 4 waves split K
-// four ways (wave-private LDS staging, [32][33] pitch: conflict-free fragment reads), then
-// the four partial tiles are summed through LDS in a fixed order (deterministic).  A long
-// contraction (the 5120-wide flatten of the timing head) is additionally split over
-// gridDim.z workgroups that write partial tiles; dense_reduce_kernel adds them in z order.
-#define DN_KC 32
-#define DN_KSPLIT 8
-__global__ __launch_bounds__(256) void dense_kernel(const float *__restrict__ A, int K,
-                                                     const float *__restrict__ Bm,
-                                                     const float *__restrict__ bias, int N,
-                                                     float *__restrict__ Cm, int M, int act,
-                                                     float *__restrict__ part) {
-    __shared__ float as[4][32 * 33];
-    __shared__ float bs[4][DN_KC * 32];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int m0 = blockIdx.y * 32, n0 = blockIdx.x * 32;
-    const int KS = gridDim.z;
-    const int Kz = ((K + KS - 1) / KS + 4 * DN_KC - 1) / (4 * DN_KC) * (4 * DN_KC);   // K range per workgroup
-    const int kz1 = min(K, (int)(blockIdx.z + 1) * Kz);
-    const int kq = Kz / 4;                                           // K range per wave, chunk aligned
-    const int kbeg = blockIdx.z * Kz + wid * kq, kend = min(kz1, kbeg + kq);
-    f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-    float *aw = as[wid], *bw = bs[wid];
-    for (int k0 = 0; k0 < kq; k0 += DN_KC) {                         // same trip count in every wave
-        __syncthreads();
-        for (int i = lane; i < 32 * DN_KC; i += 64) {
-            const int r = i / DN_KC, kk = i - r * DN_KC;
-            const int k = kbeg + k0 + kk;
-            aw[r * 33 + kk] = (m0 + r < M && k < kend) ? A[(size_t)(m0 + r) * K + k] : 0.f;
-        }
-        for (int i = lane; i < DN_KC * 32; i += 64) {
-            const int kk = i >> 5, c = i & 31;
-            const int k = kbeg + k0 + kk;
-            bw[i] = (k < kend && n0 + c < N) ? Bm[(size_t)k * N + n0 + c] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < DN_KC; kk += 2) {
-            const float a = aw[(lane & 31) * 33 + kk + (lane >> 5)];
-            const float bv = bw[(kk + (lane >> 5)) * 32 + (lane & 31)];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bv, acc, 0, 0, 0);
-        }
-    }
-    __syncthreads();
-    // partial tiles -> LDS [wave][row][col(33)], then every thread sums 4 outputs
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        const int row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        as[wid][row * 33 + (lane & 31)] = acc[e];
-    }
-    __syncthreads();
-    for (int i = tid; i < 32 * 32; i += 256) {
-        const int row = i >> 5, col = i & 31;
-        const int m = m0 + row, n = n0 + col;
-        if (m < M && n < N) {
-            float v = ((as[0][row * 33 + col] + as[1][row * 33 + col]) +
-                       (as[2][row * 33 + col] + as[3][row * 33 + col]));
-            if (part) { part[((size_t)blockIdx.z * M + m) * N + n] = v; continue; }
-            v += bias[n];
-            if (act == 1) v = sigmoidf_(v);
-            Cm[(size_t)m * N + n] = v;
-        }
-    }
-}
-__global__ void dense_reduce_kernel(const float *__restrict__ part, int KS, const float *__restrict__ bias,
-                                    int N, float *__restrict__ Cm, int M, int act) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)M * N) return;
-    float v = part[i];
-    for (int z = 1; z < KS; ++z) v += part[(size_t)z * M * N + i];
-    v += bias[i % N];
-    if (act == 1) v = sigmoidf_(v);
-    Cm[i] = v;
-}
-
-// ---- output activation: softmax (K > 1) or sigmoid + range scaling (K == 1) -------
-__global__ void head_output_kernel(const float *__restrict__ logits, float *__restrict__ y, int B,
-                                   int K, float lo, float hi) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const float *l = logits + (size_t)b * K;
-    float *o = y + (size_t)b * K;
-    if (K == 1) {
-        const float a = 1.0f / (1.0f + expf(-l[0]));
-        o[0] = a * (hi - lo) + lo;                 // RDCNN.py:308-310 with out_func range [0,1]
-    } else {
-        float m = -INFINITY;
-        for (int k = 0; k < K; ++k) m = fmaxf(m, l[k]);
-        float s = 0.f;
-        for (int k = 0; k < K; ++k) s += expf(l[k] - m);
-        for (int k = 0; k < K; ++k) o[k] = expf(l[k] - m) / s;
-    }
-}
+#define RD_BN_EPS 1e-3f
 
 // =====================================================================================
 // Host side: topology walk, weight folding / pre-arrangement, launch plan
 // =====================================================================================
-struct DevBuf { float *p = nullptr; };
-
+// Launch plan of one convolution variant: workgroup tile, LDS bytes, N-slicing and the weights in the variant's layout
+struct ConvPlan {
+    int TH = 0, TW = 0, NWIN = 1;  // tile of NWIN windows x TH x TW positions (TH == 0: no tile fits)
+    size_t lds = 0;
+    int nslice = 1, cw = 0;    // output channels are computed in nslice slices (blockIdx.y) of cw channels
+    bool masked = false;       // small-image form: whole images per workgroup, no halo
+    double eff = 0;            // useful fraction of the tile's positions
+    void *w = nullptr;         // device weights (null: the variant is not built for this layer)
+};
 struct ConvOp {
     int cin, cout, H, W, kh, kw;
-    float *w = nullptr, *s1 = nullptr, *t1 = nullptr, *s2 = nullptr, *t2 = nullptr;
+    float *s1 = nullptr, *t1 = nullptr, *s2 = nullptr, *t2 = nullptr;
     bool residual = false;
     int sc_proj = -1;          // index into projs, -1 => identity shortcut
     int pool_after = 0;        // 1 => maxpool (ph, pw) follows
-    int TH = 0, TW = 0, NWIN = 1, MT = 2;
-    size_t lds = 0;
-    int nslice = 1, cw = 0;    // output channels are computed in nslice slices of cw channels
-    // split-bf16 variant (null when not built for this layer)
-    uint4 *w16 = nullptr;
-    int TH16 = 0, TW16 = 0, NWIN16 = 1;
-    size_t lds16 = 0;
-    int nslice16 = 1, cw16 = 0;
-    bool masked16 = false;
-    double eff32 = 0, eff16 = 0;
-    // split-fp16 variant (null when not built for this layer); N-slicing as for split-bf16
-    uint4 *whs = nullptr;      // 32-wide N-slices: 16x16x32 fragments of tap pairs (conv_f16x3s_kernel)
-    int nsliceh = 1, cwh = 0;  // split-fp16 N-slicing: 32-wide slices unless the layer runs the masked form
-    int THh = 0, TWh = 0, NWINh = 1;
-    size_t ldsh = 0;
-    bool maskedh = false;
-    double effh = 0;
-    int sw = 0;                // weights scaled by 2^sw
-    // FFT-domain form (conv mode 3, amt_fftconv.hip): built on the first amt_rdcnn_set_mode(net, 3) for the
-    // 32 -> 32 (4 x 16) layers on images of at most 561 columns; k_host keeps the Keras-layout kernel for that
+    ConvPlan f32;              // f32 MFMA (always built; for the first layer only w: the [tap][cout] kernel as is)
+    int MT = 2;                //   its M-tiles per wave
+    ConvPlan bf16;             // split-bf16: 128 couts run as two 64-wide slices
+    ConvPlan f16;              // split-fp16: 32-wide N-slices, 16x16x32 fragments of tap pairs (conv_f16x3s_kernel)
+    int sw = 0;                //   its weights are scaled by 2^sw
+    // FFT-domain forms (conv mode 3), built on the first amt_rdcnn_set_mode(net, 3): the row form for the 32 -> 32
+    // (4 x 16) layers on images of at most 561 columns (amt_fftconv.hip), the packed-image form for the 64 -> 64
+    // (4 x 16) layers on 10 x 64 images (amt_fftpk.hip); k_host keeps the Keras-layout kernel for that
     std::vector<float> k_host;
-    amt_fftconv_layer *fft = nullptr;
-    // packed-image form of the 64 -> 64 (4 x 16) layers on 10 x 64 images (amt_fftpk.hip), same switch
-    amt_fftpk_layer *pk = nullptr;
+    FcLayer fc;
 };
 struct ProjOp {
     int cin, cout, H, W, ph, pw, HO, WO;
@@ -966,98 +74,107 @@ struct amt_rdcnn {
     mutable std::vector<std::vector<ProfAcc>> prof_acc;   // [tower][layer]
     amt_rdcnn_desc d;
     std::vector<Tower> towers;
-    std::vector<float *> allocs;
+    std::vector<void *> allocs;
     float *d1w = nullptr, *d1b = nullptr, *d2w = nullptr, *d2b = nullptr;
     int flat = 0;
     double flops = 0;
-    mutable int mode = 0;      // 0: f32 MFMA, 1: split-bf16 where built, 2: split-fp16 where built
+    mutable int mode = 0;      // 0: f32 MFMA, 1: split-bf16 where built, 2: split-fp16 where built, 3: 2 + FFT-domain forms
 };
 
-static int upload(amt_rdcnn *n, const std::vector<float> &h, float **out) {
-    float *d = nullptr;
-    if (hipMalloc(&d, h.size() * sizeof(float)) != hipSuccess) return AMT_E_NOMEM;
+// host bytes -> a new device allocation owned by the net
+template <class T>
+static int upload(amt_rdcnn *n, const void *h, size_t bytes, T **out) {
+    void *d = nullptr;
+    if (hipMalloc(&d, bytes) != hipSuccess) return AMT_E_NOMEM;
     n->allocs.push_back(d);
-    if (hipMemcpy(d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return AMT_E_HIP;
-    *out = d;
+    if (hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) != hipSuccess) return AMT_E_HIP;
+    *out = static_cast<T *>(d);
     return AMT_OK;
 }
-
-struct BN { const float *g, *b, *m, *v; };
-static void fold_bn(const BN &bn, int c, const float *bias, std::vector<float> &s, std::vector<float> &t) {
-    s.resize(c); t.resize(c);
+// BatchNormalization (bn: gamma, beta, mean, variance, c floats each) behind an optional bias, folded to y = s x + t
+static int upload_folded_bn(amt_rdcnn *n, const float *bn, int c, const float *bias, float **s_out, float **t_out) {
+    const float *g = bn, *b = bn + c, *m = bn + 2 * c, *v = bn + 3 * c;
+    std::vector<float> s(c), t(c);
     for (int i = 0; i < c; ++i) {
-        const float sc = bn.g[i] / sqrtf(bn.v[i] + RD_BN_EPS);
+        const float sc = g[i] / sqrtf(v[i] + RD_BN_EPS);
         s[i] = sc;
-        t[i] = bn.b[i] + ((bias ? bias[i] : 0.f) - bn.m[i]) * sc;
+        t[i] = b[i] + ((bias ? bias[i] : 0.f) - m[i]) * sc;
+    }
+    const int rc = upload(n, s.data(), c * sizeof(float), s_out);
+    return rc != AMT_OK ? rc : upload(n, t.data(), c * sizeof(float), t_out);
+}
+
+// Candidate tiles of at most pcap positions, in the order the choosers try them (a tie keeps the earlier one): whole
+// images of several windows, then for every tile height the widest tile and the narrowest one with as many column tiles
+template <class F>
+static void for_each_tile(int H, int W, int pcap, int max_win, F consider) {
+    if (H * W <= pcap)
+        for (int nw = std::min(pcap / (H * W), max_win); nw >= 1; --nw) consider(H, W, nw);
+    for (int TH = 1; TH <= H && TH <= pcap; ++TH) {
+        int TW = pcap / TH;
+        if (TW > W) TW = W;
+        if (TW >= 1) consider(TH, TW, 1);
+        const int nct = (W + TW - 1) / TW;
+        const int TW2 = (W + nct - 1) / nct;
+        if (TW2 >= 1 && TW2 <= TW) consider(TH, TW2, 1);
     }
 }
 
 static void choose_tile(ConvOp &c) {
+    ConvPlan &p = c.f32;
     double best = -1;
     for (int MT = 2; MT >= 1; --MT) {
         const int pcap = 128 * MT;
-        auto consider = [&](int TH, int TW, int NWIN) {
+        for_each_tile(c.H, c.W, pcap, pcap, [&](int TH, int TW, int NWIN) {
             const size_t posin = (size_t)NWIN * (TH + c.kh - 1) * (TW + c.kw - 1);
-            const size_t lds = posin * RD_CSTRIDE * 4 + 2 * (size_t)RD_CC * c.cw * 4 + (size_t)pcap * 8;
+            const size_t lds = posin * RD_CSTRIDE * 4 + 2 * (size_t)RD_CC * p.cw * 4 + (size_t)pcap * 8;
             if (lds > 150 * 1024) return;
             const double tiles = (double)((c.H + TH - 1) / TH) * ((c.W + TW - 1) / TW) / NWIN;
             double eff = (double)c.H * c.W / (tiles * pcap);
             if (lds > 78 * 1024) eff *= 0.93;          // prefer two workgroups per CU
-            if (eff > best + 1e-9) { best = eff; c.TH = TH; c.TW = TW; c.NWIN = NWIN; c.MT = MT; c.lds = lds; c.eff32 = eff; }
-        };
-        if (c.H * c.W <= pcap) {
-            for (int nw = pcap / (c.H * c.W); nw >= 1; --nw) consider(c.H, c.W, nw);
-        }
-        for (int TH = 1; TH <= c.H && TH <= pcap; ++TH) {
-            int TW = pcap / TH;
-            if (TW > c.W) TW = c.W;
-            if (TW >= 1) consider(TH, TW, 1);
-            // also the narrowest TW that keeps the same number of column tiles
-            const int nct = (c.W + TW - 1) / TW;
-            const int TW2 = (c.W + nct - 1) / nct;
-            if (TW2 >= 1 && TW2 <= TW) consider(TH, TW2, 1);
-        }
+            if (eff > best + 1e-9) { best = eff; p.TH = TH; p.TW = TW; p.NWIN = NWIN; c.MT = MT; p.lds = lds; p.eff = eff; }
+        });
     }
 }
 
-
-static size_t slab16_bytes(const ConvOp &c) {
-    const int NT = c.cw16 / 32, ntaps = c.kh * c.kw;
-    const int tps = (NT == 1 && ntaps % 2 == 0) ? 2 : 1;
-    return (size_t)tps * 3 * NT * 64 * 16;
-}
-static void choose_tile16(ConvOp &c) {
+// Tile of the split-bf16 / split-fp16 kernels: 256 positions, at most max_win windows, LDS for two workgroups per CU.
+// lds_of(staged positions) = the kernel's dynamic LDS bytes.
+template <class F>
+static void choose_tile_split(const ConvOp &c, ConvPlan &p, int max_win, F lds_of) {
     double best = -1;
     const int pcap = 256;
-    c.masked16 = false;
+    p.masked = false; p.TH = 0;
     if (c.H * c.W <= 64) {
-        // small image: halo-free (masked) tile of whole images
-        const int nw = pcap / (c.H * c.W);
-        const size_t lds = ((size_t)nw * c.H * c.W + 1) * BX_PSTRIDE + 3 * slab16_bytes(c) + (size_t)pcap * 8;
+        // small image: halo-free (masked) tile of whole images, plus one all-zero position
+        const int nw = std::min(pcap / (c.H * c.W), max_win);
+        const size_t lds = lds_of((size_t)nw * c.H * c.W + 1);
         if (lds <= 79 * 1024) {
-            c.masked16 = true; c.TH16 = c.H; c.TW16 = c.W; c.NWIN16 = nw; c.lds16 = lds;
-            c.eff16 = (double)nw * c.H * c.W / pcap;
+            p.masked = true; p.TH = c.H; p.TW = c.W; p.NWIN = nw; p.lds = lds;
+            p.eff = (double)nw * c.H * c.W / pcap;
             return;
         }
     }
-    auto consider = [&](int TH, int TW, int NWIN) {
-        const size_t posin = (size_t)NWIN * (TH + c.kh - 1) * bx_row_pitch(TW, TW + c.kw - 1);
-        const size_t lds = posin * BX_PSTRIDE + 3 * slab16_bytes(c) + (size_t)pcap * 8;
+    for_each_tile(c.H, c.W, pcap, max_win, [&](int TH, int TW, int NWIN) {
+        const size_t lds = lds_of((size_t)NWIN * (TH + c.kh - 1) * bx_row_pitch(TW, TW + c.kw - 1));
         if (lds > 79 * 1024) return;                    // two workgroups per CU
         const double tiles = (double)((c.H + TH - 1) / TH) * ((c.W + TW - 1) / TW) / NWIN;
         const double eff = (double)c.H * c.W / (tiles * pcap);
-        if (eff > best + 1e-9) { best = eff; c.TH16 = TH; c.TW16 = TW; c.NWIN16 = NWIN; c.lds16 = lds; c.eff16 = eff; }
-    };
-    if (c.H * c.W <= pcap)
-        for (int nw = pcap / (c.H * c.W); nw >= 1; --nw) consider(c.H, c.W, nw);
-    for (int TH = 1; TH <= c.H && TH <= pcap; ++TH) {
-        int TW = pcap / TH;
-        if (TW > c.W) TW = c.W;
-        if (TW >= 1) consider(TH, TW, 1);
-        const int nct = (c.W + TW - 1) / TW;
-        const int TW2 = (c.W + nct - 1) / nct;
-        if (TW2 >= 1 && TW2 <= TW) consider(TH, TW2, 1);
-    }
+        if (eff > best + 1e-9) { best = eff; p.TH = TH; p.TW = TW; p.NWIN = NWIN; p.lds = lds; p.eff = eff; }
+    });
+}
+static void choose_tile16(ConvOp &c) {
+    const int NT = c.bf16.cw / 32, ntaps = c.kh * c.kw;
+    const int tps = (NT == 1 && ntaps % 2 == 0) ? 2 : 1;
+    const size_t slab = (size_t)tps * 3 * NT * 64 * 16;  // bytes of one weight slab, three buffers
+    choose_tile_split(c, c.bf16, 256, [&](size_t npos) { return npos * BX_PSTRIDE + 3 * slab + (size_t)256 * 8; });
+}
+
+// the plan's workgroup tile into the launch parameters; returns the number of position tiles (gridDim.x)
+static unsigned apply_plan(ConvParams &p, const ConvPlan &pl) {
+    p.TH = pl.TH; p.TW = pl.TW; p.NWIN = pl.NWIN;
+    p.tiles_h = (p.H + p.TH - 1) / p.TH; p.tiles_w = (p.W + p.TW - 1) / p.TW;
+    const int groups = (p.B + p.NWIN - 1) / p.NWIN;
+    return (unsigned)((size_t)groups * p.tiles_h * p.tiles_w);
 }
 
 template <int KH, int KW, int CIN, int COUT, bool MASKED>
@@ -1069,27 +186,25 @@ static int launch_conv16_t(const ConvOp &c, ConvParams p, hipStream_t st) {
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)(80 * 1024)));
         attr_set = true;
     }
-    p.TH = c.TH16; p.TW = c.TW16; p.NWIN = c.NWIN16;
-    p.tiles_h = (p.H + p.TH - 1) / p.TH; p.tiles_w = (p.W + p.TW - 1) / p.TW;
-    const int groups = (p.B + p.NWIN - 1) / p.NWIN;
-    const unsigned grid = (unsigned)((size_t)groups * p.tiles_h * p.tiles_w);
-    kern<<<dim3(grid, c.nslice16), 512, c.lds16, st>>>(p, c.w16);
+    const unsigned grid = apply_plan(p, c.bf16);
+    kern<<<dim3(grid, c.bf16.nslice), 512, c.bf16.lds, st>>>(p, static_cast<const uint4 *>(c.bf16.w));
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }
 template <int KH, int KW>
 static int launch_conv16_k(const ConvOp &c, const ConvParams &p, hipStream_t st) {
 #define BX_CASE(CI, CO)                                                              \
-    if (c.cin == CI && c.cw16 == CO)                                                 \
-        return c.masked16 ? launch_conv16_t<KH, KW, CI, CO, true>(c, p, st)          \
+    if (c.cin == CI && c.bf16.cw == CO)                                              \
+        return c.bf16.masked ? launch_conv16_t<KH, KW, CI, CO, true>(c, p, st)          \
                           : launch_conv16_t<KH, KW, CI, CO, false>(c, p, st);
     BX_CASE(32, 32) BX_CASE(32, 64) BX_CASE(64, 64) BX_CASE(128, 64)
 #undef BX_CASE
     return AMT_E_UNSUPPORTED;
 }
-static bool conv16_supported(const ConvOp &c) {
-    return (c.cin == 32 && c.cout == 32) || (c.cin == 32 && c.cout == 64) || (c.cin == 64 && c.cout == 64) ||
-           (c.cin == 64 && c.cout == 128) || (c.cin == 128 && c.cout == 128);
+// channel pairs of the matrix-pipe convolutions (all three arithmetics)
+static bool conv_channels_supported(int cin, int cout) {
+    return (cin == 32 && cout == 32) || (cin == 32 && cout == 64) || (cin == 64 && cout == 64) ||
+           (cin == 64 && cout == 128) || (cin == 128 && cout == 128);
 }
 static int launch_conv16(const ConvOp &c, const ConvParams &p, hipStream_t st) {
     if (c.kh == 4 && c.kw == 16) return launch_conv16_k<4, 16>(c, p, st);
@@ -1103,74 +218,30 @@ static int launch_conv16(const ConvOp &c, const ConvParams &p, hipStream_t st) {
 #define HX_SLAB_BYTES 4096
 #define HX_XCHG_BYTES (8 * 32 * HX_TPITCH * 4)  // epilogue transposition patches (>= the K-split exchange, 8 x 4 KB)
 static void choose_tile_h(ConvOp &c) {
-    double best = -1;
-    const int pcap = 256;
-    c.maskedh = false; c.THh = 0;
     // two weight-group buffers (a group = min(4, steps per chunk) steps of 4 KB)
-    const int NTh = c.cwh / 32;
+    const int NTh = c.f16.cw / 32;
     const int nsteps = c.kh * c.kw / (NTh == 1 ? 2 : 1);
     const size_t wbytes = 2 * (size_t)std::min(4, nsteps) * HX_SLAB_BYTES;
-    auto total = [&](size_t posbytes) {
-        return std::max(posbytes, (size_t)HX_XCHG_BYTES) + wbytes + (size_t)pcap * 12 + (size_t)HX_MAXWIN * 8 + 512;      // + the slice's folded BN parameters
-    };
-    if (c.H * c.W <= 64) {
-        const int nw = std::min(pcap / (c.H * c.W), HX_MAXWIN);
-        const size_t lds = total(((size_t)nw * c.H * c.W + 1) * HX_PSTRIDE);
-        if (lds <= 79 * 1024) {
-            c.maskedh = true; c.THh = c.H; c.TWh = c.W; c.NWINh = nw; c.ldsh = lds;
-            c.effh = (double)nw * c.H * c.W / pcap;
-            return;
-        }
-    }
-    auto consider = [&](int TH, int TW, int NWIN) {
-        const size_t posin = (size_t)NWIN * (TH + c.kh - 1) * bx_row_pitch(TW, TW + c.kw - 1);
-        const size_t lds = total(posin * HX_PSTRIDE);
-        if (lds > 79 * 1024) return;                    // two workgroups per CU
-        const double tiles = (double)((c.H + TH - 1) / TH) * ((c.W + TW - 1) / TW) / NWIN;
-        const double eff = (double)c.H * c.W / (tiles * pcap);
-        if (eff > best + 1e-9) { best = eff; c.THh = TH; c.TWh = TW; c.NWINh = NWIN; c.ldsh = lds; c.effh = eff; }
-    };
-    if (c.H * c.W <= pcap)
-        for (int nw = std::min(pcap / (c.H * c.W), HX_MAXWIN); nw >= 1; --nw) consider(c.H, c.W, nw);
-    for (int TH = 1; TH <= c.H && TH <= pcap; ++TH) {
-        int TW = pcap / TH;
-        if (TW > c.W) TW = c.W;
-        if (TW >= 1) consider(TH, TW, 1);
-        const int nct = (c.W + TW - 1) / TW;
-        const int TW2 = (c.W + nct - 1) / nct;
-        if (TW2 >= 1 && TW2 <= TW) consider(TH, TW2, 1);
-    }
+    choose_tile_split(c, c.f16, HX_MAXWIN, [&](size_t npos) {
+        return std::max(npos * HX_PSTRIDE, (size_t)HX_XCHG_BYTES) + wbytes + (size_t)256 * 12 + (size_t)HX_MAXWIN * 8 + 512;      // + the slice's folded BN parameters
+    });
 }
 
-// AMT_CONV_MS=4 (diagnostic, 4 x 16 kernels only): four M-subtiles per wave -- 64 positions, 256 threads, 12 LDS
-// fragment reads per 24 MFMAs instead of 8 per 12.  Parity-green and 3 % SLOWER than the default (385 vs 397 TFLOP/s
-// on the 20 x 516 layers): the kernel is not bound by LDS reads, and two waves per SIMD hide less.
-static int conv_ms_choice() {
-    static int ms = -1;
-    if (ms < 0) {
-        const char *e = getenv("AMT_CONV_MS");
-        ms = (e && atoi(e) == 4) ? 4 : 2;
-    }
-    return ms;
-}
-template <int KH, int KW, int CIN, bool MASKED, int MS = 2>
+template <int KH, int KW, int CIN, bool MASKED>
 static int launch_convs_t(const ConvOp &c, ConvParams p, const float *amax_in, float *amax_out, hipStream_t st) {
-    auto kern = conv_f16x3s_kernel<KH, KW, CIN, MASKED, MS>;
+    auto kern = conv_f16x3s_kernel<KH, KW, CIN, MASKED>;
     static bool attr_set = false;
     if (!attr_set) {
         AMT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)(80 * 1024)));
         attr_set = true;
     }
-    p.TH = c.THh; p.TW = c.TWh; p.NWIN = c.NWINh;
-    p.tiles_h = (p.H + p.TH - 1) / p.TH; p.tiles_w = (p.W + p.TW - 1) / p.TW;
-    const int groups = (p.B + p.NWIN - 1) / p.NWIN;
-    const unsigned grid = (unsigned)((size_t)groups * p.tiles_h * p.tiles_w);
+    const unsigned grid = apply_plan(p, c.f16);
     HxScale hs{amax_in, amax_out, c.sw, nullptr};
     static const bool want_ts = getenv("AMT_CONV_TS") != nullptr;      // diagnostic: phase split of a workgroup's life
     static unsigned long long *ts_dev = nullptr;
     static size_t ts_cap = 0;
-    const size_t nwg = (size_t)grid * c.nsliceh;
+    const size_t nwg = (size_t)grid * c.f16.nslice;
     if (want_ts) {
         if (nwg > ts_cap) {
             if (ts_dev) (void)hipFree(ts_dev);
@@ -1179,7 +250,7 @@ static int launch_convs_t(const ConvOp &c, ConvParams p, const float *amax_in, f
         }
         hs.ts = ts_dev;
     }
-    kern<<<dim3(grid, c.nsliceh), 1024 / MS, c.ldsh, st>>>(p, c.whs, hs);
+    kern<<<dim3(grid, c.f16.nslice), 512, c.f16.lds, st>>>(p, static_cast<const uint4 *>(c.f16.w), hs);
     AMT_LAUNCH_CHECK();
     if (want_ts) {
         AMT_HIP_CHECK(hipStreamSynchronize(st));
@@ -1202,14 +273,11 @@ static int launch_convs_t(const ConvOp &c, ConvParams p, const float *amax_in, f
 template <int KH, int KW>
 static int launch_convh_k(const ConvOp &c, const ConvParams &p, const float *amax_in, float *amax_out, hipStream_t st) {
     // every layer runs 32-wide N-slices (blockIdx.y) of the single-tile kernel; small images its masked form
-    if (!c.whs || c.cwh != 32) return AMT_E_UNSUPPORTED;
+    if (!c.f16.w || c.f16.cw != 32) return AMT_E_UNSUPPORTED;
 #define HXS_CASE(CI)                                                                       \
-    if (c.cin == CI) {                                                                     \
-        if (c.maskedh) return launch_convs_t<KH, KW, CI, true>(c, p, amax_in, amax_out, st);              \
-        if constexpr (KW == 16)                                                            \
-            if (conv_ms_choice() == 4) return launch_convs_t<KH, KW, CI, false, 4>(c, p, amax_in, amax_out, st); \
-        return launch_convs_t<KH, KW, CI, false>(c, p, amax_in, amax_out, st);            \
-    }
+    if (c.cin == CI)                                                                       \
+        return c.f16.masked ? launch_convs_t<KH, KW, CI, true>(c, p, amax_in, amax_out, st)               \
+                            : launch_convs_t<KH, KW, CI, false>(c, p, amax_in, amax_out, st);
     HXS_CASE(32) HXS_CASE(64) HXS_CASE(128)
 #undef HXS_CASE
     return AMT_E_UNSUPPORTED;
@@ -1222,17 +290,16 @@ static int launch_convh(const ConvOp &c, const ConvParams &p, const float *amax_
 }
 
 template <int KH, int KW, int CIN, int COUT, int MT>
-static int launch_conv_t(const ConvOp &c, const ConvParams &p, hipStream_t st) {
+static int launch_conv_t(const ConvOp &c, ConvParams p, hipStream_t st) {
     auto kern = conv_mfma_kernel<KH, KW, CIN, COUT, MT>;
     static size_t attr_set = 0;
-    if (c.lds > attr_set) {
+    if (c.f32.lds > attr_set) {
         AMT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)(152 * 1024)));
         attr_set = 152 * 1024;
     }
-    const int groups = (p.B + p.NWIN - 1) / p.NWIN;
-    const unsigned grid = (unsigned)((size_t)groups * p.tiles_h * p.tiles_w);
-    kern<<<dim3(grid, c.nslice), 256, c.lds, st>>>(p);
+    const unsigned grid = apply_plan(p, c.f32);
+    kern<<<dim3(grid, c.f32.nslice), 256, c.f32.lds, st>>>(p);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }
@@ -1240,7 +307,7 @@ static int launch_conv_t(const ConvOp &c, const ConvParams &p, hipStream_t st) {
 template <int KH, int KW>
 static int launch_conv_k(const ConvOp &c, const ConvParams &p, hipStream_t st) {
 #define RD_CASE(CI, CO)                                                         \
-    if (c.cin == CI && c.cw == CO)                                              \
+    if (c.cin == CI && c.f32.cw == CO)                                          \
         return c.MT == 2 ? launch_conv_t<KH, KW, CI, CO, 2>(c, p, st)           \
                          : launch_conv_t<KH, KW, CI, CO, 1>(c, p, st);
     RD_CASE(32, 32) RD_CASE(32, 64) RD_CASE(64, 64) RD_CASE(64, 128) RD_CASE(128, 128)
@@ -1256,8 +323,74 @@ static int launch_conv(const ConvOp &c, const ConvParams &p, hipStream_t st) {
     return AMT_E_UNSUPPORTED;
 }
 
+static void choose_tile1(int H, int W, int *TH_, int *TW_) {
+    long best = -1;
+    for (int TH = 1; TH <= H && TH <= C1M_PCAP; ++TH) {
+        int TWmax = std::min(W, C1M_PCAP / TH);
+        for (int TW = std::max(1, TWmax - 40); TW <= TWmax; ++TW) {
+            const long tiles = (long)((H + TH - 1) / TH) * ((W + TW - 1) / TW);
+            const long cost = tiles * ((TH * TW + 31) / 32);
+            if (best < 0 || cost < best) { best = cost; *TH_ = TH; *TW_ = TW; }
+        }
+    }
+}
+
 static bool conv_supported(int kh, int kw) {
     return (kh == 4 && kw == 16) || (kh == 4 && kw == 2) || (kh == 2 && kw == 2);
+}
+
+static int launch_conv1_mfma(const ConvOp &c, const Conv1Params &cp, hipStream_t st) {
+    int TH1 = 1, TW1 = 1;
+    choose_tile1(cp.H, cp.W, &TH1, &TW1);
+    const int th = (cp.H + TH1 - 1) / TH1, twn = (cp.W + TW1 - 1) / TW1;
+    const size_t lds = (size_t)2 * C1M_PCAP * 4 + (size_t)4 * 32 * HX_TPITCH * 4 +
+                       (size_t)(TH1 + c.kh - 1) * (TW1 + c.kw - 1) * 4;
+    const unsigned grid = (unsigned)std::min<size_t>((size_t)cp.B * th * twn, 256 * 8);
+    if (c.kh == 4 && c.kw == 16) conv1_mfma_kernel<4, 16><<<grid, 256, lds, st>>>(cp, TH1, TW1, th, twn);
+    else if (c.kh == 4 && c.kw == 2) conv1_mfma_kernel<4, 2><<<grid, 256, lds, st>>>(cp, TH1, TW1, th, twn);
+    else conv1_mfma_kernel<2, 2><<<grid, 256, lds, st>>>(cp, TH1, TW1, th, twn);
+    AMT_LAUNCH_CHECK();
+    return AMT_OK;
+}
+static int launch_conv1(const ConvOp &c, const Conv1Params &cp, hipStream_t st) {
+    const int groups = 256 / c.cout;
+    const size_t lds = ((size_t)c.kh * c.kw * c.cout +
+                        (size_t)c.kh * (groups * C1_PPT + c.kw - 1)) * 4;
+    const size_t tiles = (size_t)cp.B * cp.H * ((cp.W + groups * C1_PPT - 1) / (groups * C1_PPT));
+    conv1_kernel<<<(unsigned)std::min<size_t>(tiles, 8192), 256, lds, st>>>(cp);
+    AMT_LAUNCH_CHECK();
+    return AMT_OK;
+}
+
+// ---- which implementation runs a layer ------------------------------------------------------------------------------
+// THE decision: the forward walk switches on it, and what else depends on the implementation (who forms a rank-1
+// shortcut, who measures its output, who needs frequency tensors in the workspace) is derived from it below.
+// Fall-backs: a variant that is not built for the layer (null weights / no FFT-domain layer) hands down to the next.
+enum ConvImpl {
+    IMPL_FIRST_MFMA,           // first layer (Cin = 1) on the matrix pipe, 32 filters
+    IMPL_FIRST_VALU,           // first layer, any other filter count or kernel size
+    IMPL_FFT_ROW,              // mode 3: 576-point row form
+    IMPL_FFT_PACKED,           // mode 3: 1152-point packed-image form
+    IMPL_F16X3,                // mode >= 2: split-fp16
+    IMPL_BF16X6,               // mode >= 1: split-bf16
+    IMPL_F32                   // f32 MFMA
+};
+static ConvImpl conv_impl(const ConvOp &c, int mode) {
+    if (c.cin == 1) return (c.cout == 32 && conv_supported(c.kh, c.kw)) ? IMPL_FIRST_MFMA : IMPL_FIRST_VALU;
+    if (mode == 3 && c.fc.row) return IMPL_FFT_ROW;
+    if (mode == 3 && c.fc.pk) return IMPL_FFT_PACKED;
+    if (mode >= 2 && c.f16.w) return IMPL_F16X3;
+    if (mode >= 1 && c.bf16.w) return IMPL_BF16X6;
+    return IMPL_F32;
+}
+static bool impl_is_fft(ConvImpl impl) { return impl == IMPL_FFT_ROW || impl == IMPL_FFT_PACKED; }
+// the epilogue can form a 1 x 1 projection of the one-channel network input itself (ConvParams::sc1, FcEpilogue::sc1)
+static bool impl_forms_rank1_shortcut(ConvImpl impl, const ConvOp &c) {
+    return impl == IMPL_FFT_ROW || (impl == IMPL_F16X3 && !c.f16.masked);
+}
+// the kernel leaves max |output| per window for the split-fp16 scaling of its consumer
+static bool impl_writes_amax(ConvImpl impl) {
+    return impl == IMPL_FIRST_MFMA || impl_is_fft(impl) || impl == IMPL_F16X3;
 }
 
 // number of f32 the canonical blob must hold; also validates the topology
@@ -1292,6 +425,122 @@ static long walk_count(const amt_rdcnn_desc &d, int *flat_out, std::string *err)
     return n;
 }
 
+// ---- weight packers: Keras-layout kernel [tap][cin][cout] -> the variant's layout, on the host ----------------------
+// f32 MFMA: [slice][cchunk][tap][c][j][ntw], cout = slice*cw + 32*ntw + j
+static std::vector<float> pack_f32(const float *kern, int ntap, int C, int fo, int nslice) {
+    const int nch = C / 32, cw = fo / nslice, NTW = cw / 32;
+    std::vector<float> wa((size_t)ntap * C * fo);
+    for (int sl = 0; sl < nslice; ++sl)
+        for (int ch = 0; ch < nch; ++ch)
+            for (int tap = 0; tap < ntap; ++tap)
+                for (int cc = 0; cc < 32; ++cc)
+                    for (int j = 0; j < 32; ++j)
+                        for (int nt = 0; nt < NTW; ++nt)
+                            wa[(((((size_t)sl * nch + ch) * ntap + tap) * 32 + cc) * 32 + j) * NTW + nt] =
+                                kern[((size_t)tap * C + ch * 32 + cc) * fo + sl * cw + nt * 32 + j];
+    return wa;
+}
+// split-bf16: [slice][chunk16][slab][tt][plane][nt][h][col][8] bf16
+static std::vector<unsigned short> pack_bf16x6(const float *kern, int ntap, int C, int fo, int nslice16) {
+    const int NT = fo / 32, cw16 = fo / nslice16, NT16 = cw16 / 32;
+    const int tps = (NT16 == 1 && ntap % 2 == 0) ? 2 : 1;
+    const int nslab = ntap / tps;
+    const int nch16 = C / BX_CC;
+    std::vector<unsigned short> w16((size_t)nch16 * ntap * 3 * NT * 2 * 32 * 8);
+    for (int sl = 0; sl < nslice16; ++sl)
+        for (int ch = 0; ch < nch16; ++ch)
+            for (int sb = 0; sb < nslab; ++sb)
+                for (int tt = 0; tt < tps; ++tt)
+                    for (int nt = 0; nt < NT16; ++nt)
+                        for (int h = 0; h < 2; ++h)
+                            for (int col = 0; col < 32; ++col)
+                                for (int jj = 0; jj < 8; ++jj) {
+                                    const int tap = sb * tps + tt;
+                                    const int cin_i = ch * BX_CC + 8 * h + jj;
+                                    const float wv = kern[((size_t)tap * C + cin_i) * fo + sl * cw16 + nt * 32 + col];
+                                    unsigned short hh[3];
+                                    amt_split3(wv, hh[0], hh[1], hh[2]);
+                                    for (int pl = 0; pl < 3; ++pl) {
+                                        const size_t idx =
+                                            ((((((((size_t)sl * nch16 + ch) * nslab + sb) * tps + tt) * 3 + pl) * NT16 + nt) * 2 + h) * 32 + col) * 8 + jj;
+                                        w16[idx] = hh[pl];
+                                    }
+                                }
+    return w16;
+}
+// split-fp16, weights scaled by wscale: [slice][chunk16][tap pair][plane][N-subtile][lane = col + 16 kgroup][8] f16,
+// kgroup g = (tap 2 tp + g % 2, channels 8 (g / 2) .. + 7); 32-wide slices
+static std::vector<unsigned short> pack_f16x3(const float *kern, int ntap, int C, int fo, float wscale) {
+    const int NT = fo / 32, nsliceh = fo / 32;
+    const int nch16 = C / BX_CC;
+    std::vector<unsigned short> ws((size_t)nch16 * ntap * 2 * NT * 2 * 32 * 8);
+    const int ntp = ntap / 2;
+    for (int sl = 0; sl < nsliceh; ++sl)
+        for (int ch = 0; ch < nch16; ++ch)
+            for (int tp = 0; tp < ntp; ++tp)
+                for (int ns = 0; ns < 2; ++ns)
+                    for (int ln = 0; ln < 64; ++ln)
+                        for (int jj = 0; jj < 8; ++jj) {
+                            const int col = ln & 15, kg = ln >> 4;
+                            const int tap = 2 * tp + (kg & 1);
+                            const int cin_i = ch * BX_CC + 8 * (kg >> 1) + jj;
+                            const float wv = kern[((size_t)tap * C + cin_i) * fo + sl * 32 + ns * 16 + col];
+                            unsigned short hh[2];
+                            amt_split_f16<true>(wv * wscale, hh[0], hh[1]);
+                            for (int pl = 0; pl < 2; ++pl) {
+                                const size_t idx =
+                                    ((((((size_t)sl * nch16 + ch) * ntp + tp) * 2 + pl) * 2 + ns) * 64 + ln) * 8 + jj;
+                                ws[idx] = hh[pl];
+                            }
+                        }
+    return ws;
+}
+
+// The matrix-pipe variants of one layer (Cin >= 32): plan and weights of the f32 MFMA kernel (always), of the split-bf16
+// kernel (where its tile efficiency pays) and of the split-fp16 kernel (where a tile fits and the weights are finite)
+static int build_conv_variants(amt_rdcnn *n, ConvOp &c, const float *kern) {
+    const int C = c.cin, fo = c.cout, H = c.H, W = c.W, kh = c.kh, kw = c.kw, ntap = kh * kw;
+    if (C % 32 || fo % 32 || !conv_supported(kh, kw) || !conv_channels_supported(C, fo)) return AMT_E_UNSUPPORTED;
+    if ((kh == 4 && kw == 16 && C == 32 && fo == 32 && W + 15 <= 576 && H <= 20) ||
+        (kh == 4 && kw == 16 && C == 64 && fo == 64 && W == 64 && H == 10))
+        c.k_host.assign(kern, kern + (size_t)ntap * C * fo);      // FFT-domain forms, built on demand (mode 3)
+    int rc;
+    // small late-stage layers (few output positions per window) cannot fill 256 CUs with
+    // position tiles alone: compute them in 32-channel output slices (blockIdx.y)
+    c.f32.nslice = (fo >= 128 && H * W <= 128) ? fo / 32 : 1;
+    c.f32.cw = fo / c.f32.nslice;
+    const std::vector<float> wa = pack_f32(kern, ntap, C, fo, c.f32.nslice);
+    if ((rc = upload(n, wa.data(), wa.size() * sizeof(float), &c.f32.w)) != AMT_OK) return rc;
+    choose_tile(c);
+    if (c.f32.TH == 0) return AMT_E_UNSUPPORTED;
+
+    c.bf16.nslice = fo > 64 ? fo / 64 : 1;                // 128 couts run as two 64-wide slices
+    c.bf16.cw = fo / c.bf16.nslice;
+    choose_tile16(c);
+    // worth it only if 2.67x fewer matrix cycles survive the tile efficiency
+    if (c.bf16.TH > 0 && c.bf16.eff * 2.67 > c.f32.eff * 1.15) {
+        const std::vector<unsigned short> w16 = pack_bf16x6(kern, ntap, C, fo, c.bf16.nslice);
+        if ((rc = upload(n, w16.data(), w16.size() * 2, &c.bf16.w)) != AMT_OK) return rc;
+    }
+
+    c.f16.cw = 32; c.f16.nslice = fo / 32;                // 32-wide N-slices
+    choose_tile_h(c);
+    float wmax = 0.f;
+    bool finite = true;
+    for (size_t q = 0; q < (size_t)ntap * C * fo; ++q) {
+        if (!std::isfinite(kern[q])) finite = false;
+        wmax = std::max(wmax, fabsf(kern[q]));
+    }
+    if (c.f16.TH > 0 && finite && wmax > 0.f) {
+        int ew = 0;
+        (void)frexpf(wmax, &ew);                          // wmax < 2^ew
+        c.sw = 4 - ew;                                     // max |w| 2^sw in [8, 16)
+        const std::vector<unsigned short> ws = pack_f16x3(kern, ntap, C, fo, ldexpf(1.0f, c.sw));
+        if ((rc = upload(n, ws.data(), ws.size() * 2, &c.f16.w)) != AMT_OK) return rc;
+    }
+    return AMT_OK;
+}
+
 extern "C" {
 
 size_t amt_rdcnn_param_count(const amt_rdcnn_desc *desc) {
@@ -1304,12 +553,12 @@ int amt_rdcnn_destroy(amt_rdcnn *net) {
     if (!net) return AMT_OK;
     for (const ProfPending &pp : net->prof_pending) { (void)hipEventDestroy(pp.e0); (void)hipEventDestroy(pp.e1); }
     for (hipEvent_t e : net->prof_free) (void)hipEventDestroy(e);
-    for (float *p : net->allocs) (void)hipFree(p);
+    for (void *p : net->allocs) (void)hipFree(p);
     for (Tower &t : net->towers)
         for (ConvOp &c : t.convs)
         {
-            if (c.fft) amt_fftconv_layer_destroy_internal(c.fft);
-            if (c.pk) amt_fftpk_layer_destroy_internal(c.pk);
+            if (c.fc.row) amt_fftconv_layer_destroy_internal(c.fc.row);
+            if (c.fc.pk) amt_fftpk_layer_destroy_internal(c.fc.pk);
         }
     delete net;
     return AMT_OK;
@@ -1344,131 +593,9 @@ int amt_rdcnn_create(amt_rdcnn **out, const amt_rdcnn_desc *desc, const float *w
             c.cin = C; c.cout = fo; c.H = H; c.W = W; c.kh = kh; c.kw = kw;
             const float *kern = take((size_t)kh * kw * C * fo);
             const float *bias = take(fo);
-            BN bn{take(fo), take(fo), take(fo), take(fo)};
-            std::vector<float> s, tt;
-            fold_bn(bn, fo, bias, s, tt);
-            RD_TRY(upload(n, s, &c.s1));
-            RD_TRY(upload(n, tt, &c.t1));
-            if (C == 1) {
-                std::vector<float> w1(kern, kern + (size_t)kh * kw * fo);    // [tap][cout] as is
-                RD_TRY(upload(n, w1, &c.w));
-            } else {
-                if (C % 32 || fo % 32 || !conv_supported(kh, kw) ||
-                    !((C == 32 && fo == 32) || (C == 32 && fo == 64) || (C == 64 && fo == 64) ||
-                      (C == 64 && fo == 128) || (C == 128 && fo == 128))) {
-                    amt_rdcnn_destroy(n);
-                    return AMT_E_UNSUPPORTED;
-                }
-                if ((kh == 4 && kw == 16 && C == 32 && fo == 32 && W + 15 <= 576 && H <= 20) ||
-                    (kh == 4 && kw == 16 && C == 64 && fo == 64 && W == 64 && H == 10))
-                    c.k_host.assign(kern, kern + (size_t)kh * kw * C * fo);      // FFT-domain forms, built on demand (mode 3)
-                const int NT = fo / 32, nch = C / 32, ntap = kh * kw;
-                // small late-stage layers (few output positions per window) cannot fill 256 CUs with
-                // position tiles alone: compute them in 32-channel output slices (blockIdx.y)
-                c.nslice = (fo >= 128 && H * W <= 128) ? fo / 32 : 1;
-                c.cw = fo / c.nslice;
-                const int NTW = c.cw / 32;
-                std::vector<float> wa((size_t)ntap * C * fo);
-                // [slice][cchunk][tap][c][j][ntw]  <-  keras [tap][cin][cout], cout = slice*cw + 32*ntw + j
-                for (int sl = 0; sl < c.nslice; ++sl)
-                    for (int ch = 0; ch < nch; ++ch)
-                        for (int tap = 0; tap < ntap; ++tap)
-                            for (int cc = 0; cc < 32; ++cc)
-                                for (int j = 0; j < 32; ++j)
-                                    for (int nt = 0; nt < NTW; ++nt)
-                                        wa[(((((size_t)sl * nch + ch) * ntap + tap) * 32 + cc) * 32 + j) * NTW + nt] =
-                                            kern[((size_t)tap * C + ch * 32 + cc) * fo + sl * c.cw + nt * 32 + j];
-                RD_TRY(upload(n, wa, &c.w));
-                choose_tile(c);
-                if (c.TH == 0) { amt_rdcnn_destroy(n); return AMT_E_UNSUPPORTED; }
-                if (conv16_supported(c)) {
-                    c.nslice16 = fo > 64 ? fo / 64 : 1;                // 128 couts run as two 64-wide slices
-                    c.cw16 = fo / c.nslice16;
-                    choose_tile16(c);
-                    // worth it only if 2.67x fewer matrix cycles survive the tile efficiency
-                    if (c.TH16 > 0 && c.eff16 * 2.67 > c.eff32 * 1.15) {
-                        const int NT16 = c.cw16 / 32;
-                        const int tps = (NT16 == 1 && ntap % 2 == 0) ? 2 : 1;
-                        const int nslab = ntap / tps;
-                        // [slice][chunk16][slab][tt][plane][nt][h][col][8] bf16
-                        const int nch16 = C / BX_CC;
-                        std::vector<unsigned short> w16((size_t)nch16 * ntap * 3 * NT * 2 * 32 * 8);
-                        for (int sl = 0; sl < c.nslice16; ++sl)
-                            for (int ch = 0; ch < nch16; ++ch)
-                                for (int sb = 0; sb < nslab; ++sb)
-                                    for (int tt = 0; tt < tps; ++tt)
-                                        for (int nt = 0; nt < NT16; ++nt)
-                                            for (int h = 0; h < 2; ++h)
-                                                for (int col = 0; col < 32; ++col)
-                                                    for (int jj = 0; jj < 8; ++jj) {
-                                                        const int tap = sb * tps + tt;
-                                                        const int cin_i = ch * BX_CC + 8 * h + jj;
-                                                        const float wv = kern[((size_t)tap * C + cin_i) * fo + sl * c.cw16 + nt * 32 + col];
-                                                        unsigned short hh[3];
-                                                        amt_split3(wv, hh[0], hh[1], hh[2]);
-                                                        for (int pl = 0; pl < 3; ++pl) {
-                                                            const size_t idx =
-                                                                ((((((((size_t)sl * nch16 + ch) * nslab + sb) * tps + tt) * 3 + pl) * NT16 + nt) * 2 + h) * 32 + col) * 8 + jj;
-                                                            w16[idx] = hh[pl];
-                                                        }
-                                                    }
-                        void *d16 = nullptr;
-                        if (hipMalloc(&d16, w16.size() * 2) != hipSuccess) { amt_rdcnn_destroy(n); return AMT_E_NOMEM; }
-                        n->allocs.push_back(static_cast<float *>(d16));
-                        if (hipMemcpy(d16, w16.data(), w16.size() * 2, hipMemcpyHostToDevice) != hipSuccess) {
-                            amt_rdcnn_destroy(n); return AMT_E_HIP;
-                        }
-                        c.w16 = static_cast<uint4 *>(d16);
-                    }
-                    // split-fp16 weights, scaled 2^sw (layout below)
-                    c.cwh = 32; c.nsliceh = fo / 32;                   // 32-wide N-slices
-                    choose_tile_h(c);
-                    float wmax = 0.f;
-                    bool finite = true;
-                    for (size_t q = 0; q < (size_t)ntap * C * fo; ++q) {
-                        if (!std::isfinite(kern[q])) finite = false;
-                        wmax = std::max(wmax, fabsf(kern[q]));
-                    }
-                    if (c.THh > 0 && finite && wmax > 0.f) {
-                        int ew = 0;
-                        (void)frexpf(wmax, &ew);                          // wmax < 2^ew
-                        c.sw = 4 - ew;                                     // max |w| 2^sw in [8, 16)
-                        const float wscale = ldexpf(1.0f, c.sw);
-                        const int nch16 = C / BX_CC;
-                        if (c.cwh == 32) {
-                            // [slice][chunk16][tap pair][plane][N-subtile][lane = col + 16 kgroup][8] f16:
-                            // kgroup g = (tap 2 tp + g % 2, channels 8 (g / 2) .. + 7)
-                            std::vector<unsigned short> ws((size_t)nch16 * ntap * 2 * NT * 2 * 32 * 8);
-                            const int ntp = ntap / 2;
-                            for (int sl = 0; sl < c.nsliceh; ++sl)
-                                for (int ch = 0; ch < nch16; ++ch)
-                                    for (int tp = 0; tp < ntp; ++tp)
-                                        for (int ns = 0; ns < 2; ++ns)
-                                            for (int ln = 0; ln < 64; ++ln)
-                                                for (int jj = 0; jj < 8; ++jj) {
-                                                    const int col = ln & 15, kg = ln >> 4;
-                                                    const int tap = 2 * tp + (kg & 1);
-                                                    const int cin_i = ch * BX_CC + 8 * (kg >> 1) + jj;
-                                                    const float wv = kern[((size_t)tap * C + cin_i) * fo + sl * 32 + ns * 16 + col];
-                                                    unsigned short hh[2];
-                                                    amt_split_f16<true>(wv * wscale, hh[0], hh[1]);
-                                                    for (int pl = 0; pl < 2; ++pl) {
-                                                        const size_t idx =
-                                                            ((((((size_t)sl * nch16 + ch) * ntp + tp) * 2 + pl) * 2 + ns) * 64 + ln) * 8 + jj;
-                                                        ws[idx] = hh[pl];
-                                                    }
-                                                }
-                            void *ds = nullptr;
-                            if (hipMalloc(&ds, ws.size() * 2) != hipSuccess) { amt_rdcnn_destroy(n); return AMT_E_NOMEM; }
-                            n->allocs.push_back(static_cast<float *>(ds));
-                            if (hipMemcpy(ds, ws.data(), ws.size() * 2, hipMemcpyHostToDevice) != hipSuccess) {
-                                amt_rdcnn_destroy(n); return AMT_E_HIP;
-                            }
-                            c.whs = static_cast<uint4 *>(ds);
-                        }
-                    }
-                }
-            }
+            RD_TRY(upload_folded_bn(n, take(4 * (size_t)fo), fo, bias, &c.s1, &c.t1));
+            if (C == 1) RD_TRY(upload(n, kern, (size_t)kh * kw * fo * sizeof(float), &c.f32.w));      // [tap][cout] as is
+            else RD_TRY(build_conv_variants(n, c, kern));
             n->flops += 2.0 * H * W * (double)kh * kw * C * fo;
             C = fo;
             tw.max_act = std::max(tw.max_act, (size_t)H * W * C);
@@ -1482,21 +609,13 @@ int amt_rdcnn_create(amt_rdcnn **out, const amt_rdcnn_desc *desc, const float *w
                     if (pr.HO != H || pr.WO != W) { amt_rdcnn_destroy(n); return AMT_E_UNSUPPORTED; }
                     const float *pk = nullptr, *pb = nullptr;
                     if (p0C != C) { pk = take((size_t)p0C * C); pb = take(C); }
-                    BN sbn{take(C), take(C), take(C), take(C)};
-                    std::vector<float> ps, pt;
-                    fold_bn(sbn, C, pb, ps, pt);
-                    if (pk) { std::vector<float> pw_(pk, pk + (size_t)p0C * C); RD_TRY(upload(n, pw_, &pr.w)); }
-                    RD_TRY(upload(n, ps, &pr.s));
-                    RD_TRY(upload(n, pt, &pr.t));
+                    RD_TRY(upload_folded_bn(n, take(4 * (size_t)C), C, pb, &pr.s, &pr.t));
+                    if (pk) RD_TRY(upload(n, pk, (size_t)p0C * C * sizeof(float), &pr.w));
                     n->flops += 2.0 * H * W * (double)p0C * C;
                     c.sc_proj = (int)tw.projs.size();
                     tw.projs.push_back(pr);
                 }
-                BN rbn{take(C), take(C), take(C), take(C)};
-                std::vector<float> rs, rt;
-                fold_bn(rbn, C, nullptr, rs, rt);
-                RD_TRY(upload(n, rs, &c.s2));
-                RD_TRY(upload(n, rt, &c.t2));
+                RD_TRY(upload_folded_bn(n, take(4 * (size_t)C), C, nullptr, &c.s2, &c.t2));
                 p0H = H; p0W = W; p0C = C;
             }
             if (d.pool_layer_frequency > 0 && i % d.pool_layer_frequency == 0) {
@@ -1514,11 +633,10 @@ int amt_rdcnn_create(amt_rdcnn **out, const amt_rdcnn_desc *desc, const float *w
         const float *b1 = take(d.dense_units);
         const float *k2 = take((size_t)d.dense_units * d.output_classes);
         const float *b2 = take(d.output_classes);
-        std::vector<float> a(k1, b1), b(b1, k2), c2(k2, b2), e(b2, cur);
-        RD_TRY(upload(n, a, &n->d1w));
-        RD_TRY(upload(n, b, &n->d1b));
-        RD_TRY(upload(n, c2, &n->d2w));
-        RD_TRY(upload(n, e, &n->d2b));
+        RD_TRY(upload(n, k1, (size_t)(b1 - k1) * sizeof(float), &n->d1w));
+        RD_TRY(upload(n, b1, (size_t)(k2 - b1) * sizeof(float), &n->d1b));
+        RD_TRY(upload(n, k2, (size_t)(b2 - k2) * sizeof(float), &n->d2w));
+        RD_TRY(upload(n, b2, (size_t)(cur - b2) * sizeof(float), &n->d2b));
         n->flops += 2.0 * flat * d.dense_units + 2.0 * d.dense_units * d.output_classes;
     }
 #undef RD_TRY
@@ -1536,10 +654,11 @@ int amt_rdcnn_set_mode(amt_rdcnn *net, int mode) {
         // the transformed kernel matrices are computed on the host in float64, once
         for (Tower &t : net->towers)
             for (ConvOp &c : t.convs)
-                if (!c.fft && !c.pk && !c.k_host.empty()) {
-                    const int rc = c.cin == 64 ? amt_fftpk_layer_create_internal(&c.pk, c.k_host.data())
-                                               : amt_fftconv_layer_create_internal(&c.fft, c.k_host.data());
+                if (!c.fc && !c.k_host.empty()) {
+                    const int rc = c.cin == 64 ? amt_fftpk_layer_create_internal(&c.fc.pk, c.k_host.data())
+                                               : amt_fftconv_layer_create_internal(&c.fc.row, c.k_host.data());
                     if (rc != AMT_OK) return rc;
+                    c.fc.H = c.H; c.fc.W = c.W;
                 }
     }
     net->mode = mode;
@@ -1589,40 +708,89 @@ int amt_rdcnn_profile_read(amt_rdcnn *net, int32_t *desc, double *ms, double *wi
     return AMT_OK;
 }
 
-#define RD_CHUNK_MAX 1024
-// windows per pass through the network (AMT_RD_CHUNK, diagnostic: smaller chunks keep the FFT-domain layers' frequency
-// tensors inside the Infinity Cache at the price of more, smaller launches)
-static int rd_chunk() {
-    static int c = 0;
-    if (!c) { const char *e = getenv("AMT_RD_CHUNK"); c = e ? std::max(1, std::min(atoi(e), RD_CHUNK_MAX)) : RD_CHUNK_MAX; }
-    return c;
-}
-#define RD_CHUNK rd_chunk()
-static size_t ws_floats(const amt_rdcnn *n, int Bc) {
-    size_t ma = 0;
-    for (const Tower &t : n->towers) ma = std::max(ma, t.max_act);
-    ma = (ma + 3) & ~(size_t)3;
-    // + per-window max |activation| of the network input and of every conv layer's output (split-fp16 scaling)
-    size_t fft = 0;                                      // mode 3: two frequency tensors + per-window max |Xf|
-    if (n->mode == 3)
-        for (const Tower &t : n->towers)
-            for (const ConvOp &c : t.convs)
-            {
-                if (c.fft) fft = std::max(fft, 2 * amt_fftconv_freq_floats(Bc, c.H) + (size_t)Bc + 8);
-                if (c.pk) fft = std::max(fft, 2 * amt_fftpk_freq_floats(Bc) + (size_t)Bc + 8);
-            }
-    return (size_t)Bc * (4 * ma + (size_t)((n->flat + 3) & ~3) + (size_t)((n->d.dense_units + 3) & ~3) +
-                         (size_t)((n->d.output_classes + 3) & ~3) + (size_t)(n->d.conv_layers + 1)) + 8 + fft;
+#define RD_CHUNK 1024          // windows per pass through the network
+
+// ---- workspace: THE layout, in floats from the workspace base --------------------------------------------------------
+struct WsLayout {
+    size_t act;                // floats per window of an activation buffer
+    size_t buf[4];             // activation buffers (ping-pong, shortcut source, projected shortcut)
+    size_t flat, dense, logits;
+    size_t amax;               // [conv_layers + 1][Bc] max |activation| per window: the network input and every conv
+                               // layer's output (split-fp16 scaling)
+    size_t Xf, Yf, amaxf;      // mode 3: two frequency tensors (16-byte aligned) + per-window max |Xf|
+    size_t total;
+};
+// base: the workspace the offsets will be applied to (only its 16-byte misalignment matters; the total does not
+// depend on it -- the 8 floats in front of Xf cover the round-up)
+static WsLayout ws_layout(const amt_rdcnn *n, int Bc, const void *base = nullptr) {
+    auto up4 = [](size_t v) { return (v + 3) & ~(size_t)3; };
+    WsLayout l;
+    l.act = 0;
+    for (const Tower &t : n->towers) l.act = std::max(l.act, t.max_act);
+    l.act = up4(l.act);
+    for (int i = 0; i < 4; ++i) l.buf[i] = (size_t)i * Bc * l.act;
+    l.flat = (size_t)4 * Bc * l.act;
+    l.dense = l.flat + (size_t)Bc * up4(n->flat);
+    l.logits = l.dense + (size_t)Bc * up4(n->d.dense_units);
+    l.amax = l.logits + (size_t)Bc * up4(n->d.output_classes);
+    l.Xf = l.amax + (size_t)(n->d.conv_layers + 1) * Bc + 8;
+    l.total = l.Xf;
+    l.Xf += ((16 - (reinterpret_cast<uintptr_t>(base) + l.Xf * sizeof(float)) % 16) % 16) / sizeof(float);
+    size_t freq = 0;                                     // the largest frequency tensor of the net
+    for (const Tower &t : n->towers)
+        for (const ConvOp &c : t.convs)
+            if (impl_is_fft(conv_impl(c, n->mode))) freq = std::max(freq, fc_freq_floats(c.fc, Bc));
+    l.Yf = l.Xf + freq;
+    l.amaxf = l.Yf + freq;
+    if (freq) l.total += 2 * freq + (size_t)Bc + 8;
+    return l;
 }
 
 size_t amt_rdcnn_workspace_bytes(const amt_rdcnn *net, int B) {
     if (!net || B <= 0) return 0;
-    return ws_floats(net, std::min(B, RD_CHUNK)) * sizeof(float);
+    return ws_layout(net, std::min(B, RD_CHUNK)).total * sizeof(float);
 }
 
 static int grid_for(size_t total) {
     size_t g = (total + 255) / 256;
     return (int)std::min<size_t>(g, 65536);
+}
+static int launch_absmax(const float *x, size_t n, size_t stride, int B, float *amax, hipStream_t st) {
+    absmax_kernel<<<dim3((unsigned)std::min<size_t>((n + 1023) / 1024, 64), B), 256, 0, st>>>(x, n, stride, amax);
+    AMT_LAUNCH_CHECK();
+    return AMT_OK;
+}
+
+// ---- per-layer event profiler (amt_rdcnn_profile): a begin and an end around a layer's launches ----------------------
+static int prof_begin(const amt_rdcnn *net, ProfPending &pp, hipStream_t st) {
+    if (!net->prof_on) return AMT_OK;
+    for (hipEvent_t *pe : {&pp.e0, &pp.e1}) {
+        if (!net->prof_free.empty()) { *pe = net->prof_free.back(); net->prof_free.pop_back(); }
+        else AMT_HIP_CHECK(hipEventCreate(pe));
+    }
+    AMT_HIP_CHECK(hipEventRecord(pp.e0, st));
+    return AMT_OK;
+}
+static int prof_end(const amt_rdcnn *net, const ProfPending &pp, hipStream_t st) {
+    if (!net->prof_on) return AMT_OK;
+    AMT_HIP_CHECK(hipEventRecord(pp.e1, st));
+    net->prof_pending.push_back(pp);
+    return AMT_OK;
+}
+
+// FFT-domain form, either kind: [forward transform of the spatial input, unless the previous layer left its output
+// transformed in Xf] -> per-frequency GEMM -> inverse + epilogue [+ forward transform for the next such layer]; the
+// spatial output is written only where something reads it (a later shortcut, a pooling, a layer of another kind)
+struct FcBufs { float *Xf, *Yf, *amaxf; };
+static int run_fc(const ConvOp &c, const float *in, size_t in_stride, bool have_xf, int Bc, const FcEpilogue &ep,
+                  const FcBufs &f, float *o, size_t o_stride, bool next_fc, float *amax_o, hipStream_t st) {
+    int rc = AMT_OK;
+    if (!have_xf) rc = fc_forward_fft(c.fc, in, in_stride, Bc, f.Xf, f.amaxf, st);
+    if (rc == AMT_OK) rc = fc_gemm(c.fc, f.Xf, f.amaxf, Bc, f.Yf, st);
+    if (rc != AMT_OK) return rc;
+    const bool need_sp = !next_fc || c.residual;
+    return fc_inverse_epilogue(c.fc, f.Yf, ep, Bc, need_sp ? o : nullptr, o_stride, next_fc ? f.Xf : nullptr, f.amaxf,
+                               next_fc ? nullptr : amax_o, st);
 }
 
 int amt_rdcnn_forward(const amt_rdcnn *net, const float *const *x, int B, float *y, float *logits,
@@ -1632,30 +800,28 @@ int amt_rdcnn_forward(const amt_rdcnn *net, const float *const *x, int B, float 
     for (int t = 0; t < d.n_towers; ++t) if (!x[t]) return AMT_E_INVALID;
     if (workspace_bytes < amt_rdcnn_workspace_bytes(net, B)) return AMT_E_NOMEM;
     hipStream_t st = (hipStream_t)stream;
-    size_t ma = 0;
-    for (const Tower &t : net->towers) ma = std::max(ma, t.max_act);
-    ma = (ma + 3) & ~(size_t)3;
-    const int K = d.output_classes, DU = d.dense_units, flat = net->flat;
+    const int K = d.output_classes, DU = d.dense_units, flat = net->flat, mode = net->mode;
+#define RD_TRY(x) do { const int rc_ = (x); if (rc_ != AMT_OK) return rc_; } while (0)
 
     for (int b0 = 0; b0 < B; b0 += RD_CHUNK) {
         const int Bc = std::min(RD_CHUNK, B - b0);
         float *ws = static_cast<float *>(workspace);
+        const WsLayout lay = ws_layout(net, Bc, workspace);
         float *buf[4];
-        for (int i = 0; i < 4; ++i) buf[i] = ws + (size_t)i * Bc * ma;
-        float *flatbuf = ws + (size_t)4 * Bc * ma;
-        float *d1 = flatbuf + (size_t)Bc * ((flat + 3) & ~3);
-        float *lg = d1 + (size_t)Bc * ((DU + 3) & ~3);
-        float *amax = lg + (size_t)Bc * ((K + 3) & ~3);              // [conv_layers + 1][Bc] max |activation| per window
+        for (int i = 0; i < 4; ++i) buf[i] = ws + lay.buf[i];
+        float *flatbuf = ws + lay.flat, *d1 = ws + lay.dense, *lg = ws + lay.logits;
+        // split-fp16 scaling: layer i reads amax row i (its input) and leaves row i + 1 (its output)
+        auto amax_row = [&](int i) { return ws + lay.amax + (size_t)i * Bc; };
+        const FcBufs fcb{ws + lay.Xf, ws + lay.Yf, ws + lay.amaxf};
         int flat_off = 0;
         for (int t = 0; t < d.n_towers; ++t) {
             const Tower &tw = net->towers[t];
             const float *cur = x[t] + (size_t)b0 * tw.in_h * tw.in_w;
-            if (net->mode >= 2) {
-                AMT_HIP_CHECK(hipMemsetAsync(amax, 0, (size_t)(d.conv_layers + 1) * Bc * sizeof(float), st));
-                const size_t nin = (size_t)tw.in_h * tw.in_w;
-                absmax_kernel<<<dim3((unsigned)std::min<size_t>((nin + 1023) / 1024, 64), Bc), 256, 0, st>>>(cur, nin, nin, amax);
-            }
             size_t cur_stride = (size_t)tw.in_h * tw.in_w;
+            if (mode >= 2) {
+                AMT_HIP_CHECK(hipMemsetAsync(amax_row(0), 0, (size_t)(d.conv_layers + 1) * Bc * sizeof(float), st));
+                RD_TRY(launch_absmax(cur, cur_stride, cur_stride, Bc, amax_row(0), st));
+            }
             const float *p0 = cur; size_t p0_stride = cur_stride;
             int H = tw.in_h, W = tw.in_w;
             const int L = (int)tw.convs.size();
@@ -1667,137 +833,69 @@ int amt_rdcnn_forward(const amt_rdcnn *net, const float *const *x, int B, float 
             };
             for (int i = 0; i < L; ++i) {
                 const ConvOp &c = tw.convs[i];
+                const ConvImpl impl = conv_impl(c, mode);
                 const bool last_op = (i == L - 1) && !c.pool_after;
                 float *o = last_op ? flatbuf + flat_off : pick(cur, p0, nullptr);
                 const size_t o_stride = last_op ? (size_t)flat : (size_t)H * W * c.cout;
+                // shortcut: the block's input as is, its projection (a kernel of its own), or -- a 1 x 1 projection of
+                // the one-channel network input -- formed in the consumer's epilogue (rank1)
                 const float *sc = nullptr; size_t sc_stride = 0;
                 const ProjOp *rank1 = nullptr;
-                if (c.residual) {
-                    if (c.sc_proj >= 0 && ((net->mode == 2 && c.whs && !c.maskedh) || (net->mode == 3 && (c.fft || (c.whs && !c.maskedh)))) &&
-                        tw.projs[c.sc_proj].cin == 1 &&
-                        tw.projs[c.sc_proj].ph == 1 && tw.projs[c.sc_proj].pw == 1 && tw.projs[c.sc_proj].w) {
-                        rank1 = &tw.projs[c.sc_proj];                 // formed in the consumer's epilogue
-                    } else if (c.sc_proj >= 0) {
-                        const ProjOp &pr = tw.projs[c.sc_proj];
+                if (c.residual && c.sc_proj >= 0) {
+                    const ProjOp &pr = tw.projs[c.sc_proj];
+                    if (impl_forms_rank1_shortcut(impl, c) && pr.cin == 1 && pr.ph == 1 && pr.pw == 1 && pr.w) {
+                        rank1 = &pr;
+                    } else {
                         float *sb = pick(cur, p0, o);
                         ProjParams pp{p0, p0_stride, sb, (size_t)pr.HO * pr.WO * pr.cout, pr.w, pr.s, pr.t,
                                       Bc, pr.H, pr.W, pr.cin, pr.cout, pr.ph, pr.pw, pr.HO, pr.WO};
                         proj_kernel<<<dim3((pr.WO + PJ_TW - 1) / PJ_TW, pr.HO, Bc), 256,
                                       (size_t)PJ_TW * pr.cin * sizeof(float), st>>>(pp);
                         sc = sb; sc_stride = (size_t)pr.HO * pr.WO * pr.cout;
-                    } else {
-                        sc = p0; sc_stride = p0_stride;
                     }
+                } else if (c.residual) {
+                    sc = p0; sc_stride = p0_stride;
                 }
-                hipEvent_t pe0 = nullptr, pe1 = nullptr;
-                if (net->prof_on) {
-                    for (hipEvent_t *pe : {&pe0, &pe1}) {
-                        if (!net->prof_free.empty()) { *pe = net->prof_free.back(); net->prof_free.pop_back(); }
-                        else AMT_HIP_CHECK(hipEventCreate(pe));
-                    }
-                    AMT_HIP_CHECK(hipEventRecord(pe0, st));
+                const float *s2 = c.residual ? c.s2 : nullptr, *t2 = c.residual ? c.t2 : nullptr;
+                float *amax_o = mode >= 2 ? amax_row(i + 1) : nullptr;
+                ProfPending prof{nullptr, nullptr, t, i, Bc};
+                RD_TRY(prof_begin(net, prof, st));
+                switch (impl) {
+                case IMPL_FIRST_MFMA:
+                    RD_TRY(launch_conv1_mfma(c, Conv1Params{cur, cur_stride, o, o_stride, sc, sc_stride, static_cast<const float *>(c.f32.w),
+                                                            c.s1, c.t1, s2, t2, Bc, H, W, c.kh, c.kw, c.cout, amax_o}, st));
+                    break;
+                case IMPL_FIRST_VALU:
+                    RD_TRY(launch_conv1(c, Conv1Params{cur, cur_stride, o, o_stride, sc, sc_stride, static_cast<const float *>(c.f32.w),
+                                                       c.s1, c.t1, s2, t2, Bc, H, W, c.kh, c.kw, c.cout}, st));
+                    break;
+                case IMPL_FFT_ROW:
+                case IMPL_FFT_PACKED: {
+                    FcEpilogue ep;
+                    ep.s1 = c.s1; ep.t1 = c.t1; ep.s2 = s2; ep.t2 = t2;
+                    if (rank1) { ep.sc1 = p0; ep.sc1_stride = p0_stride; ep.sc1_w = rank1->w; ep.sc1_s = rank1->s; ep.sc1_t = rank1->t; }
+                    else { ep.sc = sc; ep.sc_stride = sc_stride; }
+                    const bool next_fc = i + 1 < L && !c.pool_after && conv_impl(tw.convs[i + 1], mode) == impl;
+                    RD_TRY(run_fc(c, cur, cur_stride, xf_valid, Bc, ep, fcb, o, o_stride, next_fc, amax_o, st));
+                    xf_valid = next_fc;
+                    break;
                 }
-                // split-fp16 scaling: layer i reads amax[i] (its input) and leaves amax[i + 1] (its output)
-                float *amax_o = net->mode >= 2 ? amax + (size_t)(i + 1) * Bc : nullptr;
-                bool wrote_amax = false;
-                if (c.cin == 1 && c.cout == 32 && conv_supported(c.kh, c.kw)) {
-                    Conv1Params cp{cur, cur_stride, o, o_stride, sc, sc_stride, c.w, c.s1, c.t1,
-                                   c.residual ? c.s2 : nullptr, c.residual ? c.t2 : nullptr,
-                                   Bc, H, W, c.kh, c.kw, c.cout, amax_o};
-                    wrote_amax = true;
-                    int TH1 = 1, TW1 = 1;
-                    choose_tile1(H, W, &TH1, &TW1);
-                    const int th = (H + TH1 - 1) / TH1, twn = (W + TW1 - 1) / TW1;
-                    const size_t lds = (size_t)2 * C1M_PCAP * 4 + (size_t)4 * 32 * HX_TPITCH * 4 +
-                                       (size_t)(TH1 + c.kh - 1) * (TW1 + c.kw - 1) * 4;
-                    const unsigned grid = (unsigned)std::min<size_t>((size_t)Bc * th * twn, 256 * 8);
-                    if (c.kh == 4 && c.kw == 16) conv1_mfma_kernel<4, 16><<<grid, 256, lds, st>>>(cp, TH1, TW1, th, twn);
-                    else if (c.kh == 4 && c.kw == 2) conv1_mfma_kernel<4, 2><<<grid, 256, lds, st>>>(cp, TH1, TW1, th, twn);
-                    else conv1_mfma_kernel<2, 2><<<grid, 256, lds, st>>>(cp, TH1, TW1, th, twn);
-                    AMT_LAUNCH_CHECK();
-                } else if (c.cin == 1) {
-                    Conv1Params cp{cur, cur_stride, o, o_stride, sc, sc_stride, c.w, c.s1, c.t1,
-                                   c.residual ? c.s2 : nullptr, c.residual ? c.t2 : nullptr,
-                                   Bc, H, W, c.kh, c.kw, c.cout};
-                    const int groups = 256 / c.cout;
-                    const size_t lds = ((size_t)c.kh * c.kw * c.cout +
-                                        (size_t)c.kh * (groups * C1_PPT + c.kw - 1)) * 4;
-                    const size_t tiles = (size_t)Bc * H * ((W + groups * C1_PPT - 1) / (groups * C1_PPT));
-                    conv1_kernel<<<(unsigned)std::min<size_t>(tiles, 8192), 256, lds, st>>>(cp);
-                    AMT_LAUNCH_CHECK();
-                } else if (net->mode == 3 && c.fft) {
-                    // FFT-domain form: [forward transform of the spatial input, unless the previous layer left its
-                    // output transformed] -> per-frequency GEMM -> inverse + epilogue [+ forward transform for the next
-                    // such layer]; the spatial output is written only where something reads it (a later shortcut, a
-                    // pooling, a layer of another kind)
-                    float *Xf = amax + (size_t)(d.conv_layers + 1) * Bc + 8;
-                    Xf = reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(Xf) + 15) & ~(uintptr_t)15);
-                    float *Yf = Xf + amt_fftconv_freq_floats(Bc, H);
-                    float *amaxf = Yf + amt_fftconv_freq_floats(Bc, H);
-                    int rc = AMT_OK;
-                    if (!xf_valid) rc = amt_fftconv_forward_fft(c.fft, cur, cur_stride, Bc, H, W, Xf, amaxf, st);
-                    if (rc == AMT_OK) rc = amt_fftconv_gemm(c.fft, Xf, amaxf, Bc, H, Yf, st);
-                    if (rc != AMT_OK) return rc;
-                    const bool next_fft = i + 1 < L && !c.pool_after && tw.convs[i + 1].fft;
-                    const bool need_sp = !next_fft || c.residual;
-                    FcEpilogue ep;
-                    ep.s1 = c.s1; ep.t1 = c.t1;
-                    if (c.residual) {
-                        ep.s2 = c.s2; ep.t2 = c.t2;
-                        if (rank1) { ep.sc1 = p0; ep.sc1_stride = p0_stride; ep.sc1_w = rank1->w; ep.sc1_s = rank1->s; ep.sc1_t = rank1->t; }
-                        else { ep.sc = sc; ep.sc_stride = sc_stride; }
-                    }
-                    rc = amt_fftconv_inverse_epilogue(c.fft, Yf, ep, Bc, H, W, need_sp ? o : nullptr, o_stride,
-                                                      next_fft ? Xf : nullptr, amaxf, next_fft ? nullptr : amax_o, st);
-                    if (rc != AMT_OK) return rc;
-                    xf_valid = next_fft;
-                    wrote_amax = true;
-                } else if (net->mode == 3 && c.pk) {
-                    // packed-image form of a 10 x 64, 64 -> 64 layer: the same chaining, one GEMM row per window
-                    float *Xf = amax + (size_t)(d.conv_layers + 1) * Bc + 8;
-                    Xf = reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(Xf) + 15) & ~(uintptr_t)15);
-                    float *Yf = Xf + amt_fftpk_freq_floats(Bc);
-                    float *amaxf = Yf + amt_fftpk_freq_floats(Bc);
-                    int rc = AMT_OK;
-                    if (!xf_valid) rc = amt_fftpk_forward_fft(c.pk, cur, cur_stride, Bc, Xf, amaxf, st);
-                    if (rc == AMT_OK) rc = amt_fftpk_gemm(c.pk, Xf, amaxf, Bc, Yf, st);
-                    if (rc != AMT_OK) return rc;
-                    const bool next_pk = i + 1 < L && !c.pool_after && tw.convs[i + 1].pk;
-                    const bool need_sp = !next_pk || c.residual;
-                    FcEpilogue ep;
-                    ep.s1 = c.s1; ep.t1 = c.t1;
-                    if (c.residual) { ep.s2 = c.s2; ep.t2 = c.t2; ep.sc = sc; ep.sc_stride = sc_stride; }
-                    rc = amt_fftpk_inverse_epilogue(c.pk, Yf, ep, Bc, need_sp ? o : nullptr, o_stride, next_pk ? Xf : nullptr, amaxf,
-                                                    next_pk ? nullptr : amax_o, st);
-                    if (rc != AMT_OK) return rc;
-                    xf_valid = next_pk;
-                    wrote_amax = true;
-                } else {
-                    ConvParams cp{cur, cur_stride, o, o_stride, sc, sc_stride, c.w, c.s1, c.t1,
-                                  c.residual ? c.s2 : nullptr, c.residual ? c.t2 : nullptr,
-                                  Bc, H, W, c.TH, c.TW, c.NWIN, (H + c.TH - 1) / c.TH,
-                                  (W + c.TW - 1) / c.TW, c.cout};
+                default: {
+                    ConvParams cp{cur, cur_stride, o, o_stride, sc, sc_stride, static_cast<const float *>(c.f32.w), c.s1, c.t1, s2, t2,
+                                  Bc, H, W, 0, 0, 1, 0, 0, c.cout};          // the launcher fills in its variant's tile
                     if (rank1) {
                         cp.sc1 = p0; cp.sc1_win_stride = p0_stride;
                         cp.sc1_w = rank1->w; cp.sc1_s = rank1->s; cp.sc1_t = rank1->t;
                     }
-                    const bool fp16 = net->mode >= 2 && c.whs;
-                    const int rc = fp16 ? launch_convh(c, cp, amax + (size_t)i * Bc, amax_o, st)
-                                   : (net->mode >= 1 && c.w16) ? launch_conv16(c, cp, st) : launch_conv(c, cp, st);
-                    if (rc != AMT_OK) return rc;
-                    wrote_amax = fp16;
+                    RD_TRY(impl == IMPL_F16X3    ? launch_convh(c, cp, amax_row(i), amax_o, st)
+                           : impl == IMPL_BF16X6 ? launch_conv16(c, cp, st) : launch_conv(c, cp, st));
                 }
-                if (amax_o && !wrote_amax && i + 1 < L) {
+                }
+                if (amax_o && !impl_writes_amax(impl) && i + 1 < L)
                     // the producing kernel does not measure its output: one extra pass (layers the split-fp16
                     // kernel is not built for; none of the reference's head topologies)
-                    const size_t nout = (size_t)H * W * c.cout;
-                    absmax_kernel<<<dim3((unsigned)std::min<size_t>((nout + 1023) / 1024, 64), Bc), 256, 0, st>>>(
-                        o, nout, o_stride, amax_o);
-                }
-                if (net->prof_on) {
-                    AMT_HIP_CHECK(hipEventRecord(pe1, st));
-                    net->prof_pending.push_back(ProfPending{pe0, pe1, t, i, Bc});
-                }
+                    RD_TRY(launch_absmax(o, (size_t)H * W * c.cout, o_stride, Bc, amax_o, st));
+                RD_TRY(prof_end(net, prof, st));
                 if (c.residual) { p0 = o; p0_stride = o_stride; }
                 cur = o; cur_stride = o_stride;
                 if (c.pool_after) {
@@ -1812,7 +910,7 @@ int amt_rdcnn_forward(const amt_rdcnn *net, const float *const *x, int B, float 
             }
             flat_off += tw.out_h * tw.out_w * tw.out_c;
         }
-        if (flat >= 2048 && ma >= (size_t)DN_KSPLIT * DU) {
+        if (flat >= 2048 && lay.act >= (size_t)DN_KSPLIT * DU) {
             float *dpart = buf[0];                         // the activation buffers are dead by now
             dense_kernel<<<dim3((DU + 31) / 32, (Bc + 31) / 32, DN_KSPLIT), 256, 0, st>>>(
                 flatbuf, flat, net->d1w, net->d1b, DU, d1, Bc, 1, dpart);
@@ -1830,6 +928,7 @@ int amt_rdcnn_forward(const amt_rdcnn *net, const float *const *x, int B, float 
                                          hipMemcpyDeviceToDevice, st));
         AMT_LAUNCH_CHECK();
     }
+#undef RD_TRY
     return AMT_OK;
 }
 
@@ -1841,11 +940,11 @@ int amt_convh_plan_init(amt_convh_plan *pl, int kh, int kw, int cin, int cout, i
     if (!(cin == 32 || cin == 64 || cin == 128) || cout < 32 || cout % 32 != 0 || H < 1 || W < 1) return AMT_E_UNSUPPORTED;
     ConvOp c;
     c.cin = cin; c.cout = cout; c.H = H; c.W = W; c.kh = kh; c.kw = kw;
-    c.cwh = 32; c.nsliceh = cout / 32;
+    c.f16.cw = 32; c.f16.nslice = cout / 32;
     choose_tile_h(c);
-    if (c.THh <= 0) return AMT_E_UNSUPPORTED;
+    if (c.f16.TH <= 0) return AMT_E_UNSUPPORTED;
     pl->kh = kh; pl->kw = kw; pl->cin = cin; pl->cout = cout; pl->H = H; pl->W = W;
-    pl->TH = c.THh; pl->TW = c.TWh; pl->NWIN = c.NWINh; pl->masked = c.maskedh ? 1 : 0; pl->lds = c.ldsh;
+    pl->TH = c.f16.TH; pl->TW = c.f16.TW; pl->NWIN = c.f16.NWIN; pl->masked = c.f16.masked ? 1 : 0; pl->lds = c.f16.lds;
     return AMT_OK;
 }
 size_t amt_convh_packed_bytes(const amt_convh_plan *pl) {
@@ -1918,9 +1017,7 @@ int amt_convh_pack_all(const amt_convh_pack_job *jobs_dev, int n, int max_elems,
     return AMT_OK;
 }
 int amt_convh_absmax(const float *x, size_t n, int B, float *amax, hipStream_t st) {
-    absmax_kernel<<<dim3((unsigned)std::min<size_t>((n + 1023) / 1024, 64), B), 256, 0, st>>>(x, n, n, amax);
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
+    return launch_absmax(x, n, n, B, amax, st);
 }
 template <int KH, int KW, int CIN, bool MASKED>
 static int launch_convtr_t(const amt_convh_plan &pl, const ConvParams &p, const void *packed, const HxScale &hs, hipStream_t st) {

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-layer-class time of the timing head (conv mode 3) for one setting of AMT_RD_CHUNK (read by the library at first use):
+"""Per-layer-class time of the timing head (conv mode 3):
 python scripts/chunk_probe.py [B=1024].  Prints ms per 1024 windows for the FFT-domain layers, the 10 x 64 and the 5 x 8 classes."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,5 +28,5 @@ cls = {}
 for r in rows:
     k = '%dx%d' % (r['H'], r['W']) + (' L1' if r['layer'] == 1 else '')
     cls[k] = cls.get(k, 0.0) + r['ms'] / 3
-print('AMT_RD_CHUNK', os.environ.get('AMT_RD_CHUNK', '-'), 'B', B, 'forward %.2f ms;' % (ev0.elapsed_time(ev1) / 3),
+print('B', B, 'forward %.2f ms;' % (ev0.elapsed_time(ev1) / 3),
       '; '.join('%s %.2f' % kv for kv in cls.items()), flush=True)
