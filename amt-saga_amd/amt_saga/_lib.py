@@ -89,6 +89,12 @@ PROTOTYPES = {
                                   C.c_int, vp, vp, vp]),
     'amt_pack_events': (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     'amt_affine_i32': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+    'amt_song_decide': (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp,
+                                  vp, vp]),
+    'amt_song_wave': (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_size_t,
+                                C.c_int, vp]),
+    'amt_song_pack_events': (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    'amt_song_slide': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     'amt_synth_windows': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, C.c_size_t, vp, vp]),
     'amt_sf2_synth_windows': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp,
                                         C.c_size_t, vp, vp]),

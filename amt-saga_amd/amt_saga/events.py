@@ -52,6 +52,28 @@ def events_to_notes(events, n_frames, n_samples, sr=44100, window_start_s=None, 
     return notes
 
 
+def song_events_to_notes(events, song_frames, song_samples, sr=44100):
+    """Records of TranscriptionLoop.run_songs -- int array [..., 9] = {song, step, kind, pitch, program, velocity,
+    onset_frame, end_frame, offset_frame}, frames counted in the song -- to notes with absolute times.  Only kind 0
+    (detect) carries a note.  song_frames / song_samples: frames and samples of the song (or sequences indexed by the
+    record's song field); frames -> seconds is the reference's map on the SONG (util_audio.py:269-272).  One live window
+    per song sees every frame from one residual only: there are no overlap duplicates to merge."""
+    ev = np.asarray(events).reshape(-1, 9)
+    notes = []
+    for song, step, kind, pitch, program, velocity, on, off, offset in ev:
+        if kind != 0 or pitch < 0:
+            continue
+        T = song_frames[song] if np.ndim(song_frames) else song_frames
+        n = song_samples[song] if np.ndim(song_samples) else song_samples
+        notes.append(dict(pitch=int(pitch), program=int(max(program, 0)),
+                          velocity=int(velocity) if velocity > 0 else 64,
+                          start=float(frames_to_seconds(on, T, n, sr)),
+                          end=float(frames_to_seconds(max(off, on + 1), T, n, sr)),
+                          song=int(song), step=int(step), window=int(offset)))
+    notes.sort(key=lambda n: (n['song'], n['start'], n['pitch'], n['program']))
+    return notes
+
+
 def merge_overlap_duplicates(notes, merge_tol_s=0.05):
     """Drop the second report of a note seen by two overlapping windows."""
     out = []

@@ -34,12 +34,77 @@ import numpy as np
 import torch
 
 from . import _lib, synth
-from .audio import AudioBatch, cqt_slices, cqt_table, cqt_window_max, midi_to_hz
+from .audio import AudioBatch, cqt_slices, cqt_table, cqt_window_max, ldf_of, midi_to_hz
 from .device import empty, ptr, require_gpu, stream_ptr, to_dev, zeros
 from .heads import (InstrumentClassifier, VelocityClassifier, pitch_classifier,
                     timming_classifier)
 
 EVENT_FIELDS = ('window', 'iter', 'pitch', 'program', 'velocity', 'onset_frame', 'end_frame')
+# run_songs(): one record per step and song; onset / end / offset are song frames
+SONG_EVENT_FIELDS = ('song', 'step', 'kind', 'pitch', 'program', 'velocity', 'onset_frame', 'end_frame', 'offset_frame')
+SONG_DETECT, SONG_SLIDE, SONG_FORCED_SLIDE, SONG_FINISHED = 0, 1, 2, 3
+
+
+def song_wave_segments(lens, t_song, timing_frames, sr, positions, min_len=0):
+    """Which song samples audio_complete.wf of the live window holds while nothing has been subtracted from the song,
+    for every window position k = offset / half: the index arithmetic of section (util_audio.py:322-327: samples
+    floor(_frames_to_seconds(frame) * sr), zero-padded by wav_end - len), slice (:355-357: int(_frames_to_seconds(
+    frame) * sr) of the WINDOW's own length) and concat (:378), carried out on (source, length) pieces instead of
+    samples -- Python float arithmetic on lengths, as the reference does it, so it stays on the host.
+    Returns (int32 [B, positions, S, 3] pieces (first row sample, first song sample, length), row length)."""
+    half = timing_frames // 2
+    per_song, l_row, n_seg = [], int(min_len), 1
+    for n_samples, T in zip(lens, t_song):
+        def sample_of(frame):
+            return int(np.floor(frame / T / sr * n_samples * sr))
+
+        def section(first, last):
+            a, e = sample_of(first), sample_of(last)
+            got = max(min(e, n_samples) - min(a, n_samples), 0)
+            pieces = [(a, got)] if got else []
+            if got < e - a:
+                pieces.append((-1, e - got))                        # the reference pads by (wav_end - len)
+            return pieces
+
+        def cut(pieces, a, e):
+            out, at = [], 0
+            for src, n in pieces:
+                lo, hi = max(a, at), min(e, at + n)
+                if hi > lo:
+                    out.append((src + (lo - at) if src >= 0 else -1, hi - lo))
+                at += n
+            return out
+        w = section(0, timing_frames)
+        offset, rows = 0, []
+        for _ in range(positions):
+            row, at = [], 0
+            for src, n in w:
+                if src >= 0:
+                    if row and row[-1][1] + row[-1][2] == src and row[-1][0] + row[-1][2] == at:
+                        row[-1] = (row[-1][0], row[-1][1], row[-1][2] + n)
+                    else:
+                        row.append((at, src, n))
+                at += n
+            rows.append(row)
+            n_seg = max(n_seg, len(row))
+            l_row = max([l_row] + [d + n for d, _, n in row])
+            total = sum(n for _, n in w)
+            a = int(half / timing_frames / sr * total * sr)
+            e = int(2 * half / timing_frames / sr * total * sr)
+            offset += half
+            w = cut(w, a, e) + section(offset + half, offset + 2 * half)
+        per_song.append(rows)
+    seg = np.zeros((len(per_song), positions, n_seg, 3), dtype=np.int32)
+    for i, rows in enumerate(per_song):
+        for k, row in enumerate(rows):
+            for j, piece in enumerate(row):
+                seg[i, k, j] = piece
+    return seg, (l_row + 3) // 4 * 4
+
+
+class SongState:
+    """What prepare_songs() builds and walk_songs() advances: the packed song spectrograms and samples, the live
+    windows (`batch`), the per-song integers offset / count / finished / clean [B] and the song-level constants."""
 
 
 class TranscriptionLoop:
@@ -208,14 +273,18 @@ class TranscriptionLoop:
     def needs_phase(self):
         return self.iters > 1 and self.needs_wave
 
-    def iterate(self, b, it, events, window0=0):
+    def _step(self, b, wave_fn, fmax, before_subtract=None):
+        """One detect -> subtract step on the windows of `b` -- the head sequence both traversals share (iterate() for
+        independent windows, run_songs() for the song walk).  wave_fn() returns what the CQT heads read as the windows'
+        waveform; before_subtract(onset, end, guess_frames) runs after the guess has been selected and before it is
+        subtracted (run_songs decides there which songs detect).  Returns (onset, end, pitch, program, velocity)."""
         p = self.p
         B, T = b.mag.shape[0], b.mag.shape[1]
         st = stream_ptr()
         onset = end = pitch = program = velocity = None
         tr = {}
         if 'timing' in self.heads:
-            ct = b.compress_bands(p.timing_bands, self.refs['ref_mag'], p.timing_frames, fmax=self.span_subtract)
+            ct = b.compress_bands(p.timing_bands, self.refs['ref_mag'], p.timing_frames, fmax=fmax)
             if self.timing_streams == 2:
                 # the two timing networks read the same features and are independent: timing_end on a second stream
                 # fills the tails of timing_start's small-image launches (5 x 8 and 10 x 64 layers)
@@ -239,11 +308,7 @@ class TranscriptionLoop:
             onset = zeros((B,), torch.int32)
             end = torch.full((B,), p.pitch_frames, dtype=torch.int32, device=onset.device)
         src = self._resize_table(onset, end, T, p.pitch_frames)
-        need_wave = any(h in self.heads for h in ('pitch', 'instrument', 'velocity'))
-        wave_r = b.wave if (it == 0 and b.wave is not None and b.wave.shape[1] == p.H * (T - 1)) \
-            else None
-        if need_wave and wave_r is None:
-            wave_r = b.istft()
+        wave_r = wave_fn() if self.needs_wave else None
         if 'pitch' in self.heads:
             cp = cqt_slices(wave_r, src, self.tab_pitch, p.pitch_bands, p.H, ref=self.refs['ref_C_1'])
             tr['pitch'] = self.nets['pitch'].classify(cp)
@@ -262,6 +327,7 @@ class TranscriptionLoop:
                             ref=self.refs['ref_C_foc'])
             tr['velocity'] = self.nets['velocity'].classify(cv)
             velocity = self._round(tr['velocity'], 1, 127)
+        gidx = gfr = None
         if self.do_subtract:
             gidx = empty((B,), torch.int32)
             gfr = empty((B,), torch.int32)
@@ -269,6 +335,9 @@ class TranscriptionLoop:
                 ptr(program), ptr(pitch), ptr(onset), ptr(end), ptr(self.prog_group),
                 self.prog_group.shape[0], B, p.pitch_low, p.pitch_high - p.pitch_low + 1,
                 self.tail_frames, self.bank_frames, ptr(gidx), ptr(gfr), st))
+        if before_subtract is not None:
+            before_subtract(onset, end, gfr)
+        if self.do_subtract:
             if self.guess == 'bank':
                 b.subtract(self.bank_mag, self.bank_max, gidx, gfr, onset, normalize=True, relu=True,
                            span=self.span_subtract)
@@ -286,8 +355,20 @@ class TranscriptionLoop:
                 b.subtract(g.mag, g.ref_max, None, gfr, onset, normalize=True, relu=True, span=self.span_subtract)
         if self.trace is not None:
             self.trace.append({k: v.clone() for k, v in tr.items()})
-        _lib.check(self.lib.amt_pack_events(B, int(window0), int(it), ptr(pitch), ptr(program),
-                                            ptr(velocity), ptr(onset), ptr(end), ptr(events[it]), st))
+        return onset, end, pitch, program, velocity
+
+    def iterate(self, b, it, events, window0=0):
+        p = self.p
+        T = b.mag.shape[1]
+
+        def wave_fn():
+            # iteration 0 reads the original samples, later ones the iSTFT of the residual (util_audio.py:94-97)
+            if it == 0 and b.wave is not None and b.wave.shape[1] == p.H * (T - 1):
+                return b.wave
+            return b.istft()
+        onset, end, pitch, program, velocity = self._step(b, wave_fn, fmax=self.span_subtract)
+        _lib.check(self.lib.amt_pack_events(b.mag.shape[0], int(window0), int(it), ptr(pitch), ptr(program),
+                                            ptr(velocity), ptr(onset), ptr(end), ptr(events[it]), stream_ptr()))
 
     def run(self, wave, window0=0, refs=None):
         """All iterations for one batch.  Returns (events [iters, B, 7] int32 device,
@@ -297,6 +378,154 @@ class TranscriptionLoop:
         for it in range(self.iters):
             self.iterate(b, it, events, window0)
         return events, b
+
+    def prepare_songs(self, songs, refs=None, spectra=None):
+        """Set-up of the song walk, once per batch of songs: one STFT per song (training.py:265-269) packed frame-major
+        into one buffer, the song-level constants (:269-282), the first window of every song (section(0, None,
+        timing_frames), :284), the raw-sample table of amt_song_wave and the per-song integers.
+        songs: sequence of 1-d float32 waveforms of at least one hop.  refs: optional dict(ref_mag, ref_C_1, ref_C_inst,
+        ref_C_foc) of [B] tensors instead of the constants computed here.  spectra: optional AudioBatch that already
+        holds the songs' STFT (mag, ph, ref_max; songs of equal length, one per row) -- it is read, not changed.
+        Returns the state walk_songs() advances."""
+        if not self._dev_ready:
+            self.setup_device()
+        p = self.p
+        songs = list(songs)
+        if not songs:
+            raise ValueError('run_songs: no songs given')
+        if 'timing' not in self.heads or not self.do_subtract:
+            raise ValueError('run_songs: the walk needs the timing heads and the subtraction')
+        tf = p.timing_frames
+        if tf % 2:
+            raise ValueError('Invalid Input shape. run_songs needs an even timing_frames. Got: %d' % tf)
+        half, B = tf // 2, len(songs)
+        waves = [to_dev(s).reshape(-1) for s in songs]
+        for w in waves:
+            if w.numel() < p.H:
+                raise ValueError('Invalid Input shape. Expected: a song of at least one hop (%d samples) . Got: %d'
+                                 % (p.H, w.numel()))
+        lens = [int(w.numel()) for w in waves]
+        t_song = [1 + n // p.H for n in lens]
+        fbase = np.concatenate(([0], np.cumsum(t_song)))
+        sbase = np.concatenate(([0], np.cumsum(lens)))
+        ldf = ldf_of(p.N)
+        s_mag, s_ph = empty((int(fbase[-1]), ldf)), empty((int(fbase[-1]), ldf, 2))
+        b = AudioBatch(None, p.N, p.H)
+        b.mag, b.ph, b.ref_max = zeros((B, tf, ldf)), zeros((B, tf, ldf, 2)), empty((B,))
+        own = {}
+        normalisers = (('pitch', 'ref_C_1', self.tab_ref1), ('instrument', 'ref_C_inst', self.tab_refi),
+                       ('velocity', 'ref_C_foc', self.tab_reff))
+        for i, w in enumerate(waves):
+            if spectra is not None:
+                mag, ph, ref_max = spectra.mag[i], spectra.ph[i], spectra.ref_max[i]
+                if mag.shape[0] != t_song[i]:
+                    raise ValueError('Invalid Input shape. Expected: %d frames . Got: %d' % (t_song[i], mag.shape[0]))
+            else:
+                a = AudioBatch(w[None, :], p.N, p.H).stft(with_phase=True)
+                mag, ph, ref_max = a.mag[0], a.ph[0], a.ref_max[0]
+            f0, n0 = int(fbase[i]), min(tf, t_song[i])
+            s_mag[f0:f0 + t_song[i]], s_ph[f0:f0 + t_song[i]] = mag, ph
+            b.mag[i, :n0], b.ph[i, :n0] = mag[:n0], ph[:n0]
+            if refs is None:
+                own.setdefault('ref_mag', []).append(ref_max.clone())
+                for head, key, tab in normalisers:
+                    if head in self.heads:
+                        own.setdefault(key, []).append(cqt_window_max(w[None, :], tab, p.H)[0])
+        st = SongState()
+        st.refs = {k: torch.stack(v).contiguous() for k, v in own.items()} if refs is None else \
+            {k: to_dev(v).reshape(B).contiguous() for k, v in refs.items()}
+        st.batch, st.s_mag, st.s_ph, st.samples = b, s_mag, s_ph, torch.cat(waves)
+        st.positions = max(-(-t // half) for t in t_song)            # window positions of the longest song
+        seg, st.l_row = song_wave_segments(lens, t_song, tf, p.sr, st.positions, min_len=tf * p.H)
+        st.seg = to_dev(seg, torch.int32)
+        st.t_song = to_dev(np.asarray(t_song, dtype=np.int32), torch.int32)
+        st.frame_base = to_dev(fbase[:-1].astype(np.int64), torch.int64)
+        st.sample_base = to_dev(sbase[:-1].astype(np.int64), torch.int64)
+        st.offset, st.count, st.finished = (zeros((B,), torch.int32) for _ in range(3))
+        st.clean = torch.ones((B,), dtype=torch.int32, device=st.offset.device)
+        st.slide, st.detect, st.kind = (empty((B,), torch.int32) for _ in range(3))
+        st.wave = empty((B, st.l_row))
+        st.steps = 0
+        return st
+
+    def walk_songs(self, st, max_notes=8, silence=1e-3, poll=16, song0=0, max_steps=None):
+        """The steps of the song walk on a state from prepare_songs(); see run_songs().  max_steps: stop after that many
+        steps even if songs are unfinished (the state can be inspected, not resumed).  Returns events [steps, B, 9] int32
+        (device)."""
+        if int(max_notes) < 1:
+            raise ValueError('run_songs: max_notes must be at least 1')
+        if not float(silence) >= 0.0:
+            raise ValueError('run_songs: silence must be >= 0')
+        p, b, sp = self.p, st.batch, stream_ptr()
+        tf = p.timing_frames
+        half, B, ldf = tf // 2, b.mag.shape[0], b.mag.shape[2]
+        self.refs = st.refs
+        l_istft = p.H * (tf - 1)
+
+        def wave_fn():
+            # util_audio.py:94-97 for windows that had a subtraction (their _wf is None: the mag setter cleared it, slice
+            # and concat keep None); the raw samples section / slice / concat carry along for the others
+            _lib.check(self.lib.amt_istft(b.plan, ptr(b.mag), ptr(b.ph), B, tf, ldf, tf * ldf, ptr(st.wave), st.l_row,
+                                          sp))
+            _lib.check(self.lib.amt_song_wave(ptr(st.samples), ptr(st.sample_base), ptr(st.seg), B, st.positions,
+                                              int(st.seg.shape[2]), ptr(st.offset), half, ptr(st.clean),
+                                              ptr(st.finished), ptr(st.wave), st.l_row, st.l_row, l_istft, sp))
+            return st.wave
+
+        def decide(onset, end, gfr):
+            wmax = empty((B,))
+            _lib.check(self.lib.amt_song_decide(ptr(onset), ptr(b._fmax[0]), B, tf, ptr(st.refs['ref_mag']),
+                                                float(silence), half, int(max_notes), ptr(st.finished), ptr(st.count),
+                                                ptr(st.clean), ptr(st.slide), ptr(st.detect), ptr(st.kind), ptr(gfr),
+                                                ptr(wmax), sp))
+            b.ref_max = wmax                                         # np.max(audio_w.mag) at the subtraction (:170-174)
+
+        st.bound = st.positions * (int(max_notes) + 1)
+        if max_steps is not None:
+            st.bound = min(st.bound, int(max_steps))
+        events = empty((st.bound, B, len(SONG_EVENT_FIELDS)), torch.int32)
+        steps = 0
+        while steps < st.bound:
+            onset, end, pitch, program, velocity = self._step(b, wave_fn, fmax=True, before_subtract=decide)
+            _lib.check(self.lib.amt_song_pack_events(B, int(song0), steps, ptr(st.kind), ptr(pitch), ptr(program),
+                                                     ptr(velocity), ptr(onset), ptr(end), ptr(st.offset),
+                                                     ptr(events[steps]), sp))
+            _lib.check(self.lib.amt_song_slide(ptr(b.mag), ptr(b.ph), B, tf, ldf, tf * ldf, ptr(st.s_mag), ptr(st.s_ph),
+                                               ptr(st.frame_base), ptr(st.t_song), ptr(st.slide), ptr(st.offset),
+                                               ptr(st.count), ptr(st.finished), sp))
+            b._fmax = None                                           # the slid windows' per-frame maxima are stale
+            steps += 1
+            if steps % max(int(poll), 1) == 0 and int(st.finished.sum()) == B:
+                break
+        st.steps = steps
+        return events[:steps]
+
+    def run_songs(self, songs, max_notes=8, silence=1e-3, poll=16, song0=0, refs=None):
+        """The reference's own traversal (training.py:284, :296-328) with the predicted note where it has the gold
+        note, for B songs at once: ONE live window of timing_frames frames per song, cut from the song's spectrogram
+        (one STFT per song) and, whenever the predicted onset lies in its second half, slid by half a window with
+        the residual of every subtraction kept.  prepare_songs() + walk_songs().
+
+        songs: sequence of 1-d float32 waveforms (device tensors or arrays) of any lengths >= one hop.
+        Per step and unfinished song (amt_song_decide): onset >= half -> slide; else count == max_notes or
+        max(window) <= silence * ref_mag(song) -> forced slide; else detect (remaining heads, guess, subtraction as in
+        run(); count += 1).  A slide moves the second half of the window to the first, appends the next half window
+        of song frames (zeros past the end), offset += half, count = 0; the song is finished once offset >= its frames.
+        max_notes and silence are BUILD-DEFINED: they stand for the reference's "no gold note left in this window"
+        (training.py:313-314), which a transcriber cannot know.
+
+        Nothing is read back per step: decisions are device masks; the host polls the finished songs every `poll`
+        steps and stops at the bound positions * (max_notes + 1) steps at the latest.  Finished and sliding songs
+        keep their slot (their heads are computed and discarded; the batch is NOT compacted): batch songs of similar
+        length.  Requires the timing heads and an even timing_frames.
+
+        Returns (events [steps, B, 9] int32 device, SONG_EVENT_FIELDS; state): state.batch is the AudioBatch holding
+        every song's last window (residual magnitudes, unit phases, maxima), state.offset / count / finished /
+        t_song the per-song integers, state.refs the song-level constants."""
+        if int(max_notes) < 1:
+            raise ValueError('run_songs: max_notes must be at least 1')
+        st = self.prepare_songs(songs, refs=refs)
+        return self.walk_songs(st, max_notes=max_notes, silence=silence, poll=poll, song0=song0), st
 
     def run_stream(self, host_batches, refs=None, window0=0):
         """run() over a sequence of HOST batches with the host -> HBM copy of batch i+1 overlapped with the

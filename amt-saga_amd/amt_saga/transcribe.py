@@ -8,6 +8,7 @@ provide for the inference direction:
     flac.load_float / audio_from_file      util_audio.py:650-700 (file I/O)
     windows of p.timing_frames frames, hop = half a window        training.py:317-328
     TranscriptionLoop.run (all windows of the song in one batch)  the hot path
+    TranscriptionLoop.run_songs (traversal='song': ONE window sliding over the song's spectrogram)   training.py:284-328
     events.events_to_notes -> merge_overlap_duplicates -> write_midi   util_audio.py:594-639, 790-792
 
     python -m amt_saga.transcribe in.flac out.mid [--weights DIR] [--iters 5]
@@ -46,10 +47,17 @@ def cut_windows(wf, win_len, hop_len):
 
 
 def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument', 'velocity'),
-               groups=(0, 1, 2), weights_dir=None, guess='bank', loop=None, batch=1024):
+               groups=(0, 1, 2), weights_dir=None, guess='bank', loop=None, batch=1024, traversal='windows',
+               silence=1e-3):
     """wf: float32 mono waveform at params.sr.  Returns (notes, events) where notes is the
     merged list of dicts (pitch, program, velocity, start, end) and events the raw int32
-    [iters, n_windows, 7] records."""
+    [iters, n_windows, 7] records.
+    traversal='windows' (default): independent 50 %-overlapped windows, `iters` notes each, duplicates merged.
+    traversal='song': the reference's own walk (training.py:296-328, TranscriptionLoop.run_songs) -- one window that
+    lives on the song's spectrogram and slides by half, at most `iters` notes per position (max_notes), windows below
+    `silence` x the song's maximum skipped; events are then the [steps, 1, 9] song records and nothing needs merging."""
+    if traversal not in ('windows', 'song'):
+        raise ValueError('Requested attribute does not exist')
     p = params or Hyperparams(N=2048)
     if loop is None:
         loop = TranscriptionLoop(p, heads=heads, iters=iters, groups=groups, guess=guess)
@@ -59,6 +67,11 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
                 if os.path.exists(f):
                     net.load_weights(f)
         loop.setup_device()
+    if traversal == 'song':
+        wf32 = np.ascontiguousarray(wf, dtype=np.float32)
+        events, _ = loop.run_songs([wf32], max_notes=iters, silence=silence)
+        evs = events.cpu().numpy()
+        return ev.song_events_to_notes(evs, 1 + len(wf32) // p.H, len(wf32), sr=p.sr), evs
     L = p.H * (p.timing_frames - 1)
     wins, starts = cut_windows(np.asarray(wf, dtype=np.float32), L, L // 2)
     # song-level normalisers, as training.py:269-282 computes them: once per song, the maxima of the WHOLE song's
@@ -85,11 +98,14 @@ def main(argv=None):
     ap.add_argument('--weights', default=None)
     ap.add_argument('--iters', type=int, default=5)
     ap.add_argument('--guess', default='bank', choices=('bank', 'render'))
+    ap.add_argument('--traversal', default='windows', choices=('windows', 'song'),
+                    help="'song': one sliding window per song with the residual kept (run_songs)")
     a = ap.parse_args(argv)
     wf, sr = flac.load_float(a.infile)
     if wf.ndim > 1:
         wf = wf.mean(axis=1)                     # [n, channels] -> mono
-    notes, _ = transcribe(wf, Hyperparams(N=2048, sr=sr), iters=a.iters, weights_dir=a.weights, guess=a.guess)
+    notes, _ = transcribe(wf, Hyperparams(N=2048, sr=sr), iters=a.iters, weights_dir=a.weights, guess=a.guess,
+                          traversal=a.traversal)
     ev.write_midi(notes, a.outfile)
     print('%d notes -> %s' % (len(notes), a.outfile))
 

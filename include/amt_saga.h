@@ -249,6 +249,59 @@ int amt_pack_events(int n, int window0, int iter, const int32_t *pitch,
 int amt_affine_i32(const int32_t *x, int n, int mul, int add, int32_t *out, void *stream);
 
 /* ------------------------------------------------------------------------ *
+ * Song-resident sliding window (training.py:284, :296-328): one live window of
+ * T = 2 half frames per song, cut from the song's own spectrogram.  All songs'
+ * spectrograms are packed frame-major in one buffer (song b starts at frame
+ * frame_base[b] and has t_song[b] frames), all songs' samples in another
+ * (sample_base[b]).  Per-song state, int32 [B] on the device: offset (frames, a
+ * multiple of half), count (notes detected at this offset), finished, clean
+ * (1 until the first subtraction).  The predicted note stands where the
+ * reference has the gold note; max_notes and silence stand for "no gold note
+ * left in the window" (training.py:313-314) and are build-defined.
+ * ------------------------------------------------------------------------ */
+#define AMT_SONG_DETECT       0
+#define AMT_SONG_SLIDE        1   /* onset >= half (training.py:317) */
+#define AMT_SONG_FORCED_SLIDE 2   /* count == max_notes, or max(window) <= silence * ref_mag */
+#define AMT_SONG_FINISHED     3   /* the song was finished before this step: an idle slot */
+/* The step's decision for every song (training.py:313-317) from the rounded onset [B], the per-frame maxima of the
+ * window (frame_max [B][T], as amt_compress_bands_fmax leaves them), the song-level ref_mag [B] and the state:
+ *   finished                                      -> kind FINISHED
+ *   onset >= half                                 -> kind SLIDE,        slide = 1
+ *   count >= max_notes or window max <= silence * ref_mag (float32 product)
+ *                                                 -> kind FORCED_SLIDE, slide = 1
+ *   otherwise                                     -> kind DETECT, detect = 1, count += 1, clean = 0
+ * window_max [B] = np.max(window mag) (what audio_complete.ref_mag re-evaluates before a subtraction,
+ * util_audio.py:170-174).  guess_frames [B] (may be NULL) is set to 0 for every song that does not detect, which
+ * makes amt_subtract / amt_subtract_span leave that song's window untouched. */
+int amt_song_decide(const int32_t *onset, const float *frame_max, int B, int T, const float *ref_mag, float silence,
+                    int half, int max_notes, const int32_t *finished, int32_t *count, int32_t *clean, int32_t *slide,
+                    int32_t *detect, int32_t *kind, int32_t *guess_frames, float *window_max, void *stream);
+/* audio_complete.wf of the live window (what slice_C reads, util_audio.py:411-434) for songs nothing was subtracted
+ * from yet (clean != 0): the raw song samples that section (:322-327), slice (:355-357) and concat (:378) carry along.
+ * seg [B][K][S][3] int32 = up to S pieces (first sample in the row, first sample in the song, length; length 0 =
+ * unused) for each window position k = offset / half; the rest of the row is zero.  Rows of the other songs hold
+ * the caller's iSTFT (:94-97) in their first l_istft samples; their tail [l_istft, L) is zeroed. */
+int amt_song_wave(const float *samples, const int64_t *sample_base, const int32_t *seg, int B, int K, int S,
+                  const int32_t *offset, int half, const int32_t *clean, const int32_t *finished, float *wave, int L,
+                  size_t wave_stride, int l_istft, void *stream);
+/* events[i] = {song0+i, step, kind, pitch, program, velocity, onset_frame, end_frame, offset_frame} (int32 x 9);
+ * onset / end are song frames (offset + window frame); pitch / program / velocity are -1 unless kind == DETECT (and
+ * where the pointer is NULL), onset / end are -1 for kind FINISHED. */
+int amt_song_pack_events(int n, int song0, int step, const int32_t *kind, const int32_t *pitch, const int32_t *program,
+                         const int32_t *velocity, const int32_t *onset, const int32_t *end, const int32_t *offset,
+                         int32_t *events, void *stream);
+/* training.py:318-323 for every song with slide[b] != 0: audio_w.slice(half, 2 half) (util_audio.py:351-365), then
+ * concat (:374-382) of mid_wf.section(offset + half, None, half) (:286-328) at the advanced offset -- window rows
+ * half..T move to 0..half (magnitudes w_mag [B][T][ldf] and unit phases w_ph [B][T][ldf][2], residual kept), rows
+ * half..T are refilled with song frames [offset + T, offset + T + half), zero rows past t_song[b]; then
+ * offset += half, count = 0, finished = (offset >= t_song) (:296).  Other songs are not touched.  w_stride = floats
+ * between windows of w_mag (w_ph: twice that).  T must be even (the halves of an odd window overlap): AMT_E_INVALID.
+ * Any per-frame maxima cached for the window are stale afterwards. */
+int amt_song_slide(float *w_mag, float *w_ph, int B, int T, int ldf, size_t w_stride, const float *s_mag,
+                   const float *s_ph, const int64_t *frame_base, const int32_t *t_song, const int32_t *slide,
+                   int32_t *offset, int32_t *count, int32_t *finished, void *stream);
+
+/* ------------------------------------------------------------------------ *
  * Guess synthesis (stand-in for note_sequence.render(), util_audio.py:758-786:
  * fluidsynth + soundfont are not available).  Additive synth defined in
  * amt_saga/synth.py; window scaling follows render() (:778-781).
