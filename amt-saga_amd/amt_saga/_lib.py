@@ -46,6 +46,32 @@ class RdcnnDesc(C.Structure):
                 ('out_lo', C.c_float), ('out_hi', C.c_float)]
 
 
+class SongAdmitArgs(C.Structure):
+    _fields_ = [('w_mag', vp), ('w_ph', vp), ('s_mag', vp), ('s_ph', vp), ('admit', vp), ('new_frame_base', vp),
+                ('new_t_song', vp), ('new_sample_base', vp), ('new_song', vp), ('new_seg', vp), ('new_ref', vp * 4),
+                ('frame_base', vp), ('t_song', vp), ('sample_base', vp), ('slot_song', vp), ('seg', vp), ('ref', vp * 4),
+                ('offset', vp), ('count', vp), ('finished', vp), ('clean', vp), ('w_stride', C.c_size_t),
+                ('B', C.c_int32), ('n_new', C.c_int32), ('T', C.c_int32), ('ldf', C.c_int32), ('K', C.c_int32),
+                ('S', C.c_int32)]
+
+
+def song_admit_args(**fields):
+    """SongAdmitArgs from keyword arguments: a tensor gives its device pointer, None a NULL, a number itself; new_ref /
+    ref take sequences of up to four tensors (missing entries are NULL)."""
+    a = SongAdmitArgs()
+    known = {name for name, _ in SongAdmitArgs._fields_}
+    for k, v in fields.items():
+        if k not in known:
+            raise ValueError('Requested attribute does not exist')
+        if k in ('new_ref', 'ref'):
+            arr = getattr(a, k)
+            for i, t in enumerate(v):
+                arr[i] = t.data_ptr() if t is not None else None
+        else:
+            setattr(a, k, v.data_ptr() if hasattr(v, 'data_ptr') else v)
+    return a
+
+
 # name -> (restype, argtypes); every symbol include/amt_saga.h declares
 PROTOTYPES = {
     'amt_version': (C.c_int, []),
@@ -57,6 +83,8 @@ PROTOTYPES = {
     'amt_stft_frames': (C.c_int, [vp, C.c_int]),
     'amt_stft_mag': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, C.c_int,
                                C.c_int, C.c_size_t, vp]),
+    'amt_stft_mag_ragged': (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_longlong, vp, vp, vp, vp,
+                                      C.c_longlong, C.c_int, vp]),
     'amt_istft': (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp,
                             C.c_size_t, vp]),
     'amt_window_max': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp]),
@@ -94,6 +122,8 @@ PROTOTYPES = {
     'amt_song_wave': (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_size_t,
                                 C.c_int, vp]),
     'amt_song_pack_events': (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    'amt_song_admit': (C.c_int, [C.POINTER(SongAdmitArgs), vp]),
+    'amt_song_pack_events_slots': (C.c_int, [C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     'amt_song_slide': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     'amt_synth_windows': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, C.c_size_t, vp, vp]),
     'amt_sf2_synth_windows': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp,

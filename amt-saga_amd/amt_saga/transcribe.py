@@ -12,6 +12,7 @@ provide for the inference direction:
     events.events_to_notes -> merge_overlap_duplicates -> write_midi   util_audio.py:594-639, 790-792
 
     python -m amt_saga.transcribe in.flac out.mid [--weights DIR] [--iters 5]
+    python -m amt_saga.transcribe --songs a.flac b.flac ... --out-dir DIR [--slots N]     (song queue, one .mid per input)
 
 Weights: a directory with {timing_start,timing_end,pitch,instrument,velocity}.npz in the
 naming of amt_saga/rdcnn.py; without it the heads carry their seeded synthetic weights (the
@@ -46,6 +47,16 @@ def cut_windows(wf, win_len, hop_len):
     return out, starts
 
 
+def _make_loop(p, iters, heads, groups, weights_dir, guess):
+    loop = TranscriptionLoop(p, heads=heads, iters=iters, groups=groups, guess=guess)
+    if weights_dir:
+        for name, net in loop.nets.items():
+            f = os.path.join(weights_dir, name + '.npz')
+            if os.path.exists(f):
+                net.load_weights(f)
+    return loop.setup_device()
+
+
 def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument', 'velocity'),
                groups=(0, 1, 2), weights_dir=None, guess='bank', loop=None, batch=1024, traversal='windows',
                silence=1e-3):
@@ -60,13 +71,7 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
         raise ValueError('Requested attribute does not exist')
     p = params or Hyperparams(N=2048)
     if loop is None:
-        loop = TranscriptionLoop(p, heads=heads, iters=iters, groups=groups, guess=guess)
-        if weights_dir:
-            for name, net in loop.nets.items():
-                f = os.path.join(weights_dir, name + '.npz')
-                if os.path.exists(f):
-                    net.load_weights(f)
-        loop.setup_device()
+        loop = _make_loop(p, iters, heads, groups, weights_dir, guess)
     if traversal == 'song':
         wf32 = np.ascontiguousarray(wf, dtype=np.float32)
         events, _ = loop.run_songs([wf32], max_notes=iters, silence=silence)
@@ -89,9 +94,80 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
     return ev.merge_overlap_duplicates(notes), evs
 
 
+def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', 'instrument', 'velocity'),
+                          groups=(0, 1, 2), weights_dir=None, guess='bank', loop=None, slots=8, silence=1e-3, poll=16,
+                          pool_frames=None):
+    """The song queue behind transcribe_songs (TranscriptionLoop.iter_song_queue): yields (index, notes, events) as
+    each song finishes, in finishing order.  wfs: a sequence or an iterator of mono float32 waveforms at params.sr."""
+    p = params or Hyperparams(N=2048)
+    if loop is None:
+        loop = _make_loop(p, iters, heads, groups, weights_dir, guess)
+    lens = {}
+
+    def feed():
+        for i, wf in enumerate(wfs):
+            w = np.ascontiguousarray(wf, dtype=np.float32).reshape(-1)
+            lens[i] = len(w)
+            yield w
+    for i, evs in loop.iter_song_queue(feed(), slots, max_notes=iters, silence=silence, poll=poll,
+                                       pool_frames=pool_frames):
+        n = lens.pop(i)
+        one = evs.copy()
+        one[:, 0] = 0                                              # song_events_to_notes indexes scalars by song 0
+        notes = ev.song_events_to_notes(one, 1 + n // p.H, n, sr=p.sr)
+        for note in notes:
+            note['song'] = i
+        yield i, notes, evs
+
+
+def transcribe_songs(wfs, params=None, slots=8, **kw):
+    """A collection of songs through the song queue: `slots` live windows, a finished slot refilled with the next
+    song.  Returns [(notes, events [k, 9]), ...] in input order; a song's notes are those of
+    transcribe(wf, traversal='song') for it alone (with `song` = its index)."""
+    out = {i: (notes, evs) for i, notes, evs in iter_transcribe_songs(wfs, params, slots=slots, **kw)}
+    return [out[i] for i in range(len(out))]
+
+
+def main_songs(argv):
+    """The many-files mode: --songs a.flac b.flac ... --out-dir DIR [--slots N]; one .mid per input, written as its song
+    finishes."""
+    import argparse
+    from . import flac
+    ap = argparse.ArgumentParser(description='song queue: one MIDI file per input file')
+    ap.add_argument('--songs', nargs='+', required=True)
+    ap.add_argument('--out-dir', required=True)
+    ap.add_argument('--slots', type=int, default=8)
+    ap.add_argument('--weights', default=None)
+    ap.add_argument('--iters', type=int, default=5)
+    ap.add_argument('--guess', default='bank', choices=('bank', 'render'))
+    a = ap.parse_args(argv)
+    os.makedirs(a.out_dir, exist_ok=True)
+    stems = [os.path.splitext(os.path.basename(f))[0] for f in a.songs]
+    if len(set(stems)) != len(stems):
+        raise SystemExit('--songs: two inputs would write the same .mid (equal file names)')
+    first = flac.load_float(a.songs[0])
+    sr0 = first[1]
+
+    def load():
+        for k, f in enumerate(a.songs):
+            wf, sr = first if k == 0 else flac.load_float(f)
+            if sr != sr0:
+                raise SystemExit('%s: sample rate %d differs from the first file\'s %d; one queue runs at one rate'
+                                 % (f, sr, sr0))
+            yield wf.mean(axis=1) if wf.ndim > 1 else wf
+    for i, notes, _ in iter_transcribe_songs(load(), Hyperparams(N=2048, sr=sr0), iters=a.iters, weights_dir=a.weights,
+                                             guess=a.guess, slots=a.slots):
+        out = os.path.join(a.out_dir, stems[i] + '.mid')
+        ev.write_midi(notes, out)
+        print('%d notes -> %s' % (len(notes), out))
+
+
 def main(argv=None):
     import argparse
     from . import flac
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if '--songs' in argv:
+        return main_songs(argv)
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('infile')
     ap.add_argument('outfile')

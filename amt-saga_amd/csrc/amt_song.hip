@@ -144,7 +144,120 @@ __global__ void song_advance_kernel(int n, int half, const int32_t *__restrict__
     if (o >= t_song[i]) finished[i] = 1;                           // training.py:296
 }
 
+// ---- admission (song queue) ------------------------------------------------------------------------------------------
+// A finished slot is handed to the next song of the queue: admit[b] = 0 leaves slot b alone, admit[b] = 1 + j gives it
+// the j-th newly admitted song (the new_* arrays are in admission order, the order the ragged STFT wrote them in).
+// The window becomes song.section(0, None, T) (training.py:284): rows [0, T) = song frames [0, T), zero rows past the
+// song's last frame.  Same shape as the slide: grid (chunks, B), a workgroup of a slot that is not admitted returns at
+// once, a row is 3 ldf / 4 float4 (magnitudes, then phases), each byte moves once.  The slot's integers and tables are
+// written by a second, small grid (one workgroup per slot); this kernel reads none of them -- only admit and the
+// new_* arrays -- so the order of the two launches carries no meaning.
+__global__ __launch_bounds__(256) void song_admit_kernel(
+        float *__restrict__ w_mag, float *__restrict__ w_ph, size_t w_stride, const float *__restrict__ s_mag,
+        const float *__restrict__ s_ph, const int32_t *__restrict__ admit, int n_new,
+        const int64_t *__restrict__ new_frame_base, const int32_t *__restrict__ new_t_song, int T, int ld4) {
+    const int b = blockIdx.y;
+    const int j = admit[b] - 1;
+    if (j < 0 || j >= n_new) return;                              // whole workgroup: the window stays as it is
+    const int row4 = 3 * ld4;
+    const int n4 = T * row4;
+    const int ts = new_t_song[j];
+    const int64_t fb = new_frame_base[j];
+    float4 *wm = reinterpret_cast<float4 *>(w_mag + (size_t)b * w_stride);
+    float4 *wp = reinterpret_cast<float4 *>(w_ph + (size_t)b * w_stride * 2);
+    const float4 *sm = reinterpret_cast<const float4 *>(s_mag);
+    const float4 *sp = reinterpret_cast<const float4 *>(s_ph);
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        const int r = i / row4, c = i - r * row4;
+        const bool have = r < ts;
+        float4 fresh = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (c < ld4) {
+            if (have) fresh = sm[(size_t)(fb + r) * ld4 + c];
+            wm[(size_t)r * ld4 + c] = fresh;
+        } else {
+            const int c2 = c - ld4;
+            if (have) fresh = sp[(size_t)(fb + r) * 2 * ld4 + c2];
+            wp[(size_t)r * 2 * ld4 + c2] = fresh;
+        }
+    }
+}
+
+// one workgroup per slot: the slot's scalars by thread 0, its K x S x 3 rows of the piece table by all threads
+__global__ __launch_bounds__(256) void song_admit_state_kernel(amt_song_admit_args a) {
+    const int b = blockIdx.x;
+    const int j = a.admit[b] - 1;
+    if (j < 0 || j >= a.n_new) return;
+    const int row = a.K * a.S * 3;
+    if (a.seg && a.new_seg)
+        for (int i = threadIdx.x; i < row; i += 256) a.seg[(size_t)b * row + i] = a.new_seg[(size_t)j * row + i];
+    if (threadIdx.x != 0) return;
+    a.frame_base[b] = a.new_frame_base[j];
+    a.t_song[b] = a.new_t_song[j];
+    if (a.sample_base) a.sample_base[b] = a.new_sample_base[j];
+    if (a.slot_song) a.slot_song[b] = a.new_song[j];
+    for (int k = 0; k < 4; ++k)
+        if (a.ref[k] && a.new_ref[k]) a.ref[k][b] = a.new_ref[k][j];
+    a.offset[b] = 0;
+    a.count[b] = 0;
+    a.finished[b] = 0;
+    a.clean[b] = 1;
+}
+
+// song_pack_kernel with the song index read per slot (a slot carries one song after the other)
+__global__ void song_pack_slots_kernel(int n, const int32_t *__restrict__ slot_song, int step,
+                                       const int32_t *__restrict__ kind, const int32_t *__restrict__ pitch,
+                                       const int32_t *__restrict__ program, const int32_t *__restrict__ velocity,
+                                       const int32_t *__restrict__ onset, const int32_t *__restrict__ end,
+                                       const int32_t *__restrict__ offset, int32_t *__restrict__ events /* [n][9] */) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int k = kind[i];
+    const bool det = k == AMT_SONG_DETECT, live = k != AMT_SONG_FINISHED;
+    int32_t *e = events + (size_t)i * 9;
+    e[0] = slot_song[i];
+    e[1] = step;
+    e[2] = k;
+    e[3] = det && pitch ? pitch[i] : -1;
+    e[4] = det && program ? program[i] : -1;
+    e[5] = det && velocity ? velocity[i] : -1;
+    e[6] = live ? offset[i] + onset[i] : -1;
+    e[7] = live ? offset[i] + end[i] : -1;
+    e[8] = offset[i];
+}
+
 extern "C" {
+
+int amt_song_admit(const amt_song_admit_args *args, void *stream) {
+    if (!args) return AMT_E_INVALID;
+    const amt_song_admit_args &a = *args;
+    if (!a.w_mag || !a.w_ph || !a.s_mag || !a.s_ph || !a.admit || !a.new_frame_base || !a.new_t_song || !a.frame_base ||
+        !a.t_song || !a.offset || !a.count || !a.finished || !a.clean)
+        return AMT_E_INVALID;
+    if ((a.sample_base && !a.new_sample_base) || (a.slot_song && !a.new_song) || (a.seg && !a.new_seg))
+        return AMT_E_INVALID;
+    if (a.B <= 0 || a.B > 65535 || a.n_new <= 0 || a.T <= 0) return AMT_E_INVALID;
+    if (a.ldf <= 0 || (a.ldf & 3) || (a.w_stride & 3) || a.w_stride < (size_t)a.T * a.ldf) return AMT_E_SHAPE;
+    if (a.seg && (a.K <= 0 || a.S <= 0)) return AMT_E_SHAPE;
+    const int ld4 = a.ldf >> 2;
+    hipStream_t st = (hipStream_t)stream;
+    int gx = (a.T * 3 * ld4 + 256 * 4 - 1) / (256 * 4);          // ~4 float4 (one read, one write each) per thread
+    if (gx < 1) gx = 1;
+    song_admit_kernel<<<dim3(gx, a.B), 256, 0, st>>>(a.w_mag, a.w_ph, a.w_stride, a.s_mag, a.s_ph, a.admit, a.n_new,
+                                                     a.new_frame_base, a.new_t_song, a.T, ld4);
+    song_admit_state_kernel<<<a.B, 256, 0, st>>>(a);
+    AMT_LAUNCH_CHECK();
+    return AMT_OK;
+}
+
+int amt_song_pack_events_slots(int n, const int32_t *slot_song, int step, const int32_t *kind, const int32_t *pitch,
+                               const int32_t *program, const int32_t *velocity, const int32_t *onset, const int32_t *end,
+                               const int32_t *offset, int32_t *events, void *stream) {
+    if (!slot_song || !kind || !onset || !end || !offset || !events || n <= 0) return AMT_E_INVALID;
+    song_pack_slots_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(n, slot_song, step, kind, pitch, program,
+                                                                              velocity, onset, end, offset, events);
+    AMT_LAUNCH_CHECK();
+    return AMT_OK;
+}
 
 int amt_song_decide(const int32_t *onset, const float *frame_max, int B, int T, const float *ref_mag, float silence,
                     int half, int max_notes, const int32_t *finished, int32_t *count, int32_t *clean, int32_t *slide,

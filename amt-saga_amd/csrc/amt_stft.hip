@@ -36,12 +36,15 @@ thread_local char amt_hip_err_buf[256] = {0};
 // Measured negative: the inter-stage twiddles are per-thread constants too (butterfly index = thread index), but
 // holding all of them costs 40 registers -> 138, three waves per SIMD: 1.43 ms against 1.20; capped at 128 / 96 registers
 // the compiler spills 8 / 37 of them.
+// stft_pairs: the frame pairs [pair0, pair0 + pairs_per_block) of ONE signal (wv, L samples, T frames, spectra at mg /
+// ph, maximum into *ref_slot) by the calling workgroup -- the body both kernels below share, so that a signal gives
+// the same bits whether it is one row of a batch of equal lengths (stft_mag_kernel) or one of n signals of unequal
+// lengths packed in one buffer (stft_ragged_kernel).
 template <int N, bool WITH_PHASE>
-__global__ __launch_bounds__(AMT_FFT_THREADS, (N == 2048 && !WITH_PHASE) ? 6 : 1) void stft_mag_kernel(
-    const float *__restrict__ wave, int L, size_t wave_stride,
-    float *__restrict__ mag, float2 *__restrict__ phase, float *__restrict__ ref_max,
-    int T, int ldf, size_t spec_stride, const float2 *__restrict__ tw_global,
-    int hop, int center, int pairs_per_block, int reuse_ok) {
+__device__ __forceinline__ void stft_pairs(
+    const float *__restrict__ wv, int L, float *__restrict__ mg, float2 *__restrict__ ph, float *__restrict__ ref_slot,
+    int T, int ldf, const float2 *__restrict__ tw_global, int hop, int center, int pair0, int pairs_per_block,
+    int reuse_ok) {
     // the first pass of fft_block reads elements tid + r * (N / 8) (radix 8, one butterfly per thread for N = 2048):
     // the same eight positions of every frame pair, so their Hann weights are formed once per workgroup, straight from
     // the global table -- and the LDS copy then only needs the entries the inter-stage twiddles touch: k * N / (NS R)
@@ -55,16 +58,12 @@ __global__ __launch_bounds__(AMT_FFT_THREADS, (N == 2048 && !WITH_PHASE) ? 6 : 1
     // the reduction scratch aliases the FFT buffer (used once, after the last transform)
     float *red = reinterpret_cast<float *>(buf);
     const int tid = threadIdx.x;
-    const int b = blockIdx.y;
     for (int i = tid; i < TWN; i += AMT_FFT_THREADS) tw[i] = tw_global[i];
     float wn[8];
 #pragma unroll
     for (int r = 0; r < 8; ++r) wn[r] = HOIST ? 0.25f - 0.25f * tw_global[tid + r * NB1].x : 0.f;   // Hann / 2 (below)
     __syncthreads();
 
-    const float *wv = wave + (size_t)b * wave_stride;
-    float *mg = mag + (size_t)b * spec_stride;
-    float2 *ph = WITH_PHASE ? phase + (size_t)b * spec_stride : nullptr;
     const int pad = center ? N / 2 : 0;
     float lmax = 0.f;
     // Interior pairs of the hoisted form (N = 8 x 256 threads) with hop = N / 4: thread `tid` needs samples s0 + tid + 256 j,
@@ -79,7 +78,7 @@ __global__ __launch_bounds__(AMT_FFT_THREADS, (N == 2048 && !WITH_PHASE) ? 6 : 1
 #pragma unroll
     for (int j = 0; j < 10; ++j) sw[j] = 0.f;
     for (int p = 0; p < pairs_per_block; ++p) {
-        const int t0 = 2 * (blockIdx.x * pairs_per_block + p);
+        const int t0 = 2 * (pair0 + p);
         if (t0 >= T) break;                       // uniform across the block
         const bool has2 = (t0 + 1) < T;
         const int s0 = t0 * hop - pad;            // first sample of frame t0
@@ -186,11 +185,48 @@ __global__ __launch_bounds__(AMT_FFT_THREADS, (N == 2048 && !WITH_PHASE) ? 6 : 1
         }
         // the next pair's first pass barriers before it overwrites `buf`
     }
-    if (ref_max) {
+    if (ref_slot) {
         __syncthreads();                                 // every wave is done with `buf`
         lmax = block_max(lmax, red);
-        if (tid == 0) atomicMax(reinterpret_cast<int *>(ref_max) + b, __float_as_int(lmax));
+        if (tid == 0) atomicMax(reinterpret_cast<int *>(ref_slot), __float_as_int(lmax));
     }
+}
+
+template <int N, bool WITH_PHASE>
+__global__ __launch_bounds__(AMT_FFT_THREADS, (N == 2048 && !WITH_PHASE) ? 6 : 1) void stft_mag_kernel(
+    const float *__restrict__ wave, int L, size_t wave_stride,
+    float *__restrict__ mag, float2 *__restrict__ phase, float *__restrict__ ref_max,
+    int T, int ldf, size_t spec_stride, const float2 *__restrict__ tw_global,
+    int hop, int center, int pairs_per_block, int reuse_ok) {
+    const int b = blockIdx.y;
+    stft_pairs<N, WITH_PHASE>(wave + (size_t)b * wave_stride, L, mag + (size_t)b * spec_stride,
+                              WITH_PHASE ? phase + (size_t)b * spec_stride : nullptr, ref_max ? ref_max + b : nullptr,
+                              T, ldf, tw_global, hop, center, blockIdx.x * pairs_per_block, pairs_per_block, reuse_ok);
+}
+
+// n signals of unequal lengths in one launch: signal b = samples[sample_base[b] .. + length[b]), its 1 + length / hop
+// frames (center) written frame-major from frame frame_base[b] of the packed spectrogram pool.  Grid (workgroups of the
+// longest signal, n): a workgroup past its own signal's last frame pair returns before it touches anything.  A
+// workgroup never leaves its signal, so the reflect padding is applied at that signal's own ends and the register
+// carry of samples (stft_pairs: interior pairs only) stops there.  A signal that does not lie inside the two
+// buffers, or is too short for the reflect padding, is skipped as a whole (the host checks the same and raises).
+template <int N, bool WITH_PHASE>
+__global__ __launch_bounds__(AMT_FFT_THREADS, (N == 2048 && !WITH_PHASE) ? 6 : 1) void stft_ragged_kernel(
+    const float *__restrict__ samples, const int64_t *__restrict__ sample_base, const int32_t *__restrict__ length,
+    long long n_samples, float *__restrict__ mag, float2 *__restrict__ phase, float *__restrict__ ref_max,
+    const int64_t *__restrict__ frame_base, long long pool_frames, int ldf, const float2 *__restrict__ tw_global,
+    int hop, int center, int pairs_per_block, int reuse_ok) {
+    const int b = blockIdx.y;
+    const int L = length[b];
+    const long long s0 = sample_base[b], f0 = frame_base[b];
+    if (L <= 0 || (center ? L <= N / 2 : L < N)) return;
+    const int T = center ? 1 + L / hop : 1 + (L - N) / hop;
+    const int pair0 = blockIdx.x * pairs_per_block;
+    if (2 * pair0 >= T) return;                                   // whole workgroup: past this signal's last pair
+    if (s0 < 0 || s0 + L > n_samples || f0 < 0 || f0 + T > pool_frames) return;
+    stft_pairs<N, WITH_PHASE>(samples + s0, L, mag + (size_t)f0 * ldf, WITH_PHASE ? phase + (size_t)f0 * ldf : nullptr,
+                              ref_max ? ref_max + b : nullptr, T, ldf, tw_global, hop, center, pair0, pairs_per_block,
+                              reuse_ok);
 }
 
 // ---------------------------------------------------------------------------------
@@ -419,19 +455,29 @@ __global__ void ordered_decode_kernel(unsigned int *p, int n) {
 }
 
 // host launchers
+// diagnostics both STFT launchers read: AMT_STFT_PPB = most frame pairs per workgroup (default 16), AMT_STFT_REUSE=0 =
+// every pair loads its 16 samples per thread instead of carrying ten of them in registers
+static int stft_ppb_max() {
+    static int v = 0;
+    if (!v) { const char *e = getenv("AMT_STFT_PPB"); v = (e && atoi(e) > 0) ? atoi(e) : 16; }
+    return v;
+}
+static int stft_reuse_ok() {
+    static int v = -1;
+    if (v < 0) { const char *e = getenv("AMT_STFT_REUSE"); v = !(e && atoi(e) == 0); }
+    return v;
+}
+
 template <int N>
 static int launch_stft(const amt_stft_plan *plan, const float *wave, int B, int L,
                        size_t wave_stride, float *mag, float *phase, float *ref_max, int T,
                        int ldf, size_t spec_stride, hipStream_t st) {
     const int pairs = (T + 1) / 2;
-    static int ppb_max = 0;                              // AMT_STFT_PPB: frame pairs per workgroup (diagnostic)
-    if (!ppb_max) { const char *e = getenv("AMT_STFT_PPB"); ppb_max = (e && atoi(e) > 0) ? atoi(e) : 16; }
-    int ppb = ppb_max;
+    int ppb = stft_ppb_max();
     // at least ~8 rounds of the 2048 workgroups the chip holds (8 per CU): fewer, longer workgroups leave a tail
     while (ppb > 1 && (size_t)((pairs + ppb - 1) / ppb) * B < 16384) ppb >>= 1;
     dim3 grid((pairs + ppb - 1) / ppb, B);
-    static int reuse_ok = -1;                            // AMT_STFT_REUSE=0: every pair loads its 16 samples per thread (diagnostic)
-    if (reuse_ok < 0) { const char *e = getenv("AMT_STFT_REUSE"); reuse_ok = !(e && atoi(e) == 0); }
+    const int reuse_ok = stft_reuse_ok();
     if (phase)
         stft_mag_kernel<N, true><<<grid, AMT_FFT_THREADS, 0, st>>>(
             wave, L, wave_stride, mag, reinterpret_cast<float2 *>(phase), ref_max, T, ldf,
@@ -440,6 +486,32 @@ static int launch_stft(const amt_stft_plan *plan, const float *wave, int B, int 
         stft_mag_kernel<N, false><<<grid, AMT_FFT_THREADS, 0, st>>>(
             wave, L, wave_stride, mag, nullptr, ref_max, T, ldf, spec_stride, plan->tw_dev,
             plan->hop, plan->center, ppb, reuse_ok);
+    AMT_LAUNCH_CHECK();
+    return AMT_OK;
+}
+
+template <int N>
+static int launch_stft_ragged(const amt_stft_plan *plan, const float *samples, const int64_t *sample_base,
+                              const int32_t *length, int n, int max_len, long long n_samples, long long total_len,
+                              float *mag, float *phase, float *ref_max, const int64_t *frame_base,
+                              long long pool_frames, int ldf, hipStream_t st) {
+    const int hop = plan->hop;
+    const int pairs_max = ((plan->center ? 1 + max_len / hop : 1 + (max_len - N) / hop) + 1) / 2;
+    // frame pairs per workgroup as launch_stft chooses them, from the pairs there are in all (the value changes no
+    // result: every pair is transformed on its own, and the carried samples are the samples a reload would fetch)
+    const long long pairs_all = (total_len / hop + 2 * (long long)n + 1) / 2;
+    int ppb = stft_ppb_max();
+    while (ppb > 1 && (pairs_all + ppb - 1) / ppb < 16384) ppb >>= 1;
+    const int reuse_ok = stft_reuse_ok();
+    dim3 grid((pairs_max + ppb - 1) / ppb, n);
+    if (phase)
+        stft_ragged_kernel<N, true><<<grid, AMT_FFT_THREADS, 0, st>>>(
+            samples, sample_base, length, n_samples, mag, reinterpret_cast<float2 *>(phase), ref_max, frame_base,
+            pool_frames, ldf, plan->tw_dev, hop, plan->center, ppb, reuse_ok);
+    else
+        stft_ragged_kernel<N, false><<<grid, AMT_FFT_THREADS, 0, st>>>(
+            samples, sample_base, length, n_samples, mag, nullptr, ref_max, frame_base, pool_frames, ldf, plan->tw_dev,
+            hop, plan->center, ppb, reuse_ok);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }
@@ -567,6 +639,31 @@ int amt_stft_mag(const amt_stft_plan *plan, const float *wave, int B, int L, siz
         case 2048: return launch_stft<2048>(plan, wave, B, L, wave_stride, mag, phase_ri, ref_max, T, ldf, spec_stride, st);
         case 4096: return launch_stft<4096>(plan, wave, B, L, wave_stride, mag, phase_ri, ref_max, T, ldf, spec_stride, st);
     }
+    return AMT_E_UNSUPPORTED;
+}
+
+int amt_stft_mag_ragged(const amt_stft_plan *plan, const float *samples, const int64_t *sample_base,
+                        const int32_t *length, int n, int max_len, long long n_samples, long long total_len,
+                        float *mag, float *phase_ri, float *ref_max, const int64_t *frame_base, long long pool_frames,
+                        int ldf, void *stream) {
+    if (!plan || !samples || !sample_base || !length || !mag || !frame_base || n <= 0 || n > 65535)
+        return AMT_E_INVALID;
+    const int F = plan->n_fft / 2 + 1;
+    if (ldf < F || (ldf & 3) || max_len <= 0 || n_samples < max_len || total_len < max_len || pool_frames <= 0)
+        return AMT_E_SHAPE;
+    if (plan->center ? max_len <= plan->n_fft / 2 : max_len < plan->n_fft) return AMT_E_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    if (ref_max) AMT_HIP_CHECK(hipMemsetAsync(ref_max, 0, sizeof(float) * n, st));
+#define AMT_RAGGED(NF) launch_stft_ragged<NF>(plan, samples, sample_base, length, n, max_len, n_samples, total_len, mag, \
+                                              phase_ri, ref_max, frame_base, pool_frames, ldf, st)
+    switch (plan->n_fft) {
+        case 256:  return AMT_RAGGED(256);
+        case 512:  return AMT_RAGGED(512);
+        case 1024: return AMT_RAGGED(1024);
+        case 2048: return AMT_RAGGED(2048);
+        case 4096: return AMT_RAGGED(4096);
+    }
+#undef AMT_RAGGED
     return AMT_E_UNSUPPORTED;
 }
 

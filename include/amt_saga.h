@@ -69,6 +69,19 @@ int amt_stft_mag(const amt_stft_plan *plan, const float *wave, int B, int L,
                  size_t wave_stride, float *mag, float *phase_ri, float *ref_max,
                  int T, int ldf, size_t spec_stride, void *stream);
 
+/* amt_stft_mag for n signals of unequal lengths in ONE launch -- one STFT per song (training.py:265-269), center
+ * (reflect) padding at each signal's own ends: signal i = samples[sample_base[i] .. + length[i]) of a packed buffer
+ * of n_samples floats; its 1 + length[i] / hop frames are written frame-major from frame frame_base[i] of the packed
+ * pool mag [pool_frames][ldf] / phase [pool_frames][ldf] float2 (may be NULL); ref_max [n] (may be NULL).
+ * sample_base / frame_base int64 [n], length int32 [n]: device.  max_len = the longest length, total_len = the sum
+ * of the lengths (host values: they size the grid).  The per-frame arithmetic is amt_stft_mag's: every signal's
+ * result is bit-identical to amt_stft_mag on that signal alone.  A signal outside the buffers or too short for the
+ * padding (length <= n_fft / 2) is left unwritten; the caller checks lengths and regions beforehand. */
+int amt_stft_mag_ragged(const amt_stft_plan *plan, const float *samples, const int64_t *sample_base,
+                        const int32_t *length, int n, int max_len, long long n_samples, long long total_len,
+                        float *mag, float *phase_ri, float *ref_max, const int64_t *frame_base, long long pool_frames,
+                        int ldf, void *stream);
+
 /* audio_complete.wf getter, the `mag * ph -> librosa.istft` branch
  * (util_audio.py:94-97): wave_out[b][0 .. hop*(T-1)) f32.  phase_ri may be
  * NULL (then `mag` is taken as interleaved complex F with pitch 2*ldf). */
@@ -300,6 +313,42 @@ int amt_song_pack_events(int n, int song0, int step, const int32_t *kind, const 
 int amt_song_slide(float *w_mag, float *w_ph, int B, int T, int ldf, size_t w_stride, const float *s_mag,
                    const float *s_ph, const int64_t *frame_base, const int32_t *t_song, const int32_t *slide,
                    int32_t *offset, int32_t *count, int32_t *finished, void *stream);
+
+/* Song queue: a finished slot takes the next song (the reference walks one song after the other per worker,
+ * training.py:623-634; here B slots do).  admit [B]: 0 = leave the slot alone, 1 + j = the slot takes the j-th of
+ * the n_new songs described by the new_* arrays (device, admission order).  For an admitted slot:
+ *   window rows [0, T) = song frames [0, T) of s_mag / s_ph from new_frame_base[j] (audio_w = section(0, None,
+ *   timing_frames), training.py:284), zero rows past new_t_song[j];
+ *   frame_base, t_song, sample_base, slot_song, ref[k] (the song-level constants of training.py:269-282, up to four,
+ *   NULL = unused), the slot's [K][S][3] rows of amt_song_wave's piece table <- the new song's;
+ *   offset = 0, count = 0, finished = 0, clean = 1.
+ * Other slots are not touched.  Two launches, independent of each other: the window rows, then the slot's integers
+ * and tables (the first reads none of them).  Any per-frame maxima cached for the windows are stale afterwards. */
+typedef struct amt_song_admit_args {
+    float *w_mag, *w_ph;                 /* [B][T][ldf], [B][T][ldf][2] */
+    const float *s_mag, *s_ph;           /* the packed spectrogram pool */
+    const int32_t *admit;                /* [B] */
+    const int64_t *new_frame_base;       /* [n_new] */
+    const int32_t *new_t_song;           /* [n_new] */
+    const int64_t *new_sample_base;      /* [n_new] */
+    const int32_t *new_song;             /* [n_new] song indices */
+    const int32_t *new_seg;              /* [n_new][K][S][3] or NULL */
+    const float *new_ref[4];             /* [n_new] each or NULL */
+    int64_t *frame_base;                 /* [B] per-slot tables ... */
+    int32_t *t_song;
+    int64_t *sample_base;
+    int32_t *slot_song;
+    int32_t *seg;                        /* [B][K][S][3] or NULL */
+    float *ref[4];
+    int32_t *offset, *count, *finished, *clean;   /* [B] per-slot state */
+    size_t w_stride;                     /* floats between windows of w_mag */
+    int32_t B, n_new, T, ldf, K, S;
+} amt_song_admit_args;
+int amt_song_admit(const amt_song_admit_args *args, void *stream);
+/* amt_song_pack_events with the song index of record i read from slot_song[i] (device) instead of song0 + i */
+int amt_song_pack_events_slots(int n, const int32_t *slot_song, int step, const int32_t *kind, const int32_t *pitch,
+                               const int32_t *program, const int32_t *velocity, const int32_t *onset, const int32_t *end,
+                               const int32_t *offset, int32_t *events, void *stream);
 
 /* ------------------------------------------------------------------------ *
  * Guess synthesis (stand-in for note_sequence.render(), util_audio.py:758-786:
