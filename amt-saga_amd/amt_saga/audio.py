@@ -146,8 +146,10 @@ class AudioBatch:
         B, T = self.mag.shape[0], self.mag.shape[1]
         lout = self.hl * (T - 1) if self.center else self.N + self.hl * (T - 1)
         out = empty((B, lout))
+        # without phases `mag` is interleaved complex [B, T, ldf, 2] and the stride counts its floats
+        stride = T * self.ldf * (1 if self.ph is not None else 2)
         _lib.check(self.lib.amt_istft(self.plan, ptr(self.mag), ptr(self.ph), B, T, self.ldf,
-                                      T * self.ldf, ptr(out), lout, stream_ptr()))
+                                      stride, ptr(out), lout, stream_ptr()))
         return out
 
     def window_max(self):

@@ -674,6 +674,8 @@ int amt_istft(const amt_stft_plan *plan, const float *mag, const float *phase_ri
     if (ldf < F) return AMT_E_SHAPE;
     const int Lout = plan->center ? plan->hop * (T - 1) : plan->n_fft + plan->hop * (T - 1);
     if (Lout <= 0 || wave_stride < (size_t)Lout) return AMT_E_SHAPE;
+    // spec_stride: bins with a phase array; floats of the interleaved complex array without one (a float2 per bin)
+    if (spec_stride < (size_t)T * ldf * (phase_ri ? 1 : 2) || (!phase_ri && (spec_stride & 1))) return AMT_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     switch (plan->n_fft) {
         case 256:  return launch_istft<256>(plan, mag, phase_ri, B, T, ldf, spec_stride, wave_out, wave_stride, Lout, st);

@@ -83,8 +83,15 @@ int amt_stft_mag_ragged(const amt_stft_plan *plan, const float *samples, const i
                         int ldf, void *stream);
 
 /* audio_complete.wf getter, the `mag * ph -> librosa.istft` branch
- * (util_audio.py:94-97): wave_out[b][0 .. hop*(T-1)) f32.  phase_ri may be
- * NULL (then `mag` is taken as interleaved complex F with pitch 2*ldf). */
+ * (util_audio.py:94-97): wave_out[b][0 .. Lout) f32, Lout = hop*(T-1) centred,
+ * n_fft + hop*(T-1) otherwise; wave_stride >= Lout.
+ *   mag   [B][T][ldf] f32 and phase_ri [B][T][ldf] float2: spec_stride counts
+ *         bins, as in amt_stft_mag (>= T*ldf; both arrays use it).
+ *   phase_ri == NULL: `mag` is interleaved complex F, [B][T][ldf] float2 (row
+ *         pitch 2*ldf floats).  spec_stride then counts FLOATS of that array,
+ *         the elements as stored: one window is 2*T*ldf, and spec_stride must
+ *         be even and >= 2*T*ldf.
+ * A stride below one window (or odd, complex input) is AMT_E_SHAPE. */
 int amt_istft(const amt_stft_plan *plan, const float *mag, const float *phase_ri,
               int B, int T, int ldf, size_t spec_stride, float *wave_out,
               size_t wave_stride, void *stream);
