@@ -26,133 +26,21 @@ Everything numeric is a HIP kernel behind the C ABI; torch only holds the
 buffers.  Song-level constants (ref_mag_song, ref_C_*) are computed once in
 prepare(), as the reference computes them once per song (training.py:269-282).
 """
-import ctypes as C
-
 import os
 
 import numpy as np
 import torch
 
-from . import _lib, synth
-from .audio import AudioBatch, cqt_slices, cqt_table, cqt_window_max, ldf_of, midi_to_hz
+from . import _lib, song_walk, synth
+from .audio import AudioBatch, cqt_slices, cqt_table, cqt_window_max, midi_to_hz
 from .device import empty, ptr, require_gpu, stream_ptr, to_dev, zeros
 from .heads import (InstrumentClassifier, VelocityClassifier, pitch_classifier,
                     timming_classifier)
+# the song walk (run_songs, run_song_queue) lives in song_walk.py; its names stay importable from here
+from .song_walk import (SONG_DETECT, SONG_EVENT_FIELDS, SONG_FINISHED, SONG_FORCED_SLIDE, SONG_SLIDE,  # noqa: F401
+                        FramePool, SongState, admission_plan, song_wave_segments)  # noqa: F401
 
 EVENT_FIELDS = ('window', 'iter', 'pitch', 'program', 'velocity', 'onset_frame', 'end_frame')
-# run_songs(): one record per step and song; onset / end / offset are song frames
-SONG_EVENT_FIELDS = ('song', 'step', 'kind', 'pitch', 'program', 'velocity', 'onset_frame', 'end_frame', 'offset_frame')
-SONG_DETECT, SONG_SLIDE, SONG_FORCED_SLIDE, SONG_FINISHED = 0, 1, 2, 3
-
-
-def song_wave_segments(lens, t_song, timing_frames, sr, positions, min_len=0):
-    """Which song samples audio_complete.wf of the live window holds while nothing has been subtracted from the song,
-    for every window position k = offset / half: the index arithmetic of section (util_audio.py:322-327: samples
-    floor(_frames_to_seconds(frame) * sr), zero-padded by wav_end - len), slice (:355-357: int(_frames_to_seconds(
-    frame) * sr) of the WINDOW's own length) and concat (:378), carried out on (source, length) pieces instead of
-    samples -- Python float arithmetic on lengths, as the reference does it, so it stays on the host.
-    Returns (int32 [B, positions, S, 3] pieces (first row sample, first song sample, length), row length)."""
-    half = timing_frames // 2
-    per_song, l_row, n_seg = [], int(min_len), 1
-    for n_samples, T in zip(lens, t_song):
-        def sample_of(frame):
-            return int(np.floor(frame / T / sr * n_samples * sr))
-
-        def section(first, last):
-            a, e = sample_of(first), sample_of(last)
-            got = max(min(e, n_samples) - min(a, n_samples), 0)
-            pieces = [(a, got)] if got else []
-            if got < e - a:
-                pieces.append((-1, e - got))                        # the reference pads by (wav_end - len)
-            return pieces
-
-        def cut(pieces, a, e):
-            out, at = [], 0
-            for src, n in pieces:
-                lo, hi = max(a, at), min(e, at + n)
-                if hi > lo:
-                    out.append((src + (lo - at) if src >= 0 else -1, hi - lo))
-                at += n
-            return out
-        w = section(0, timing_frames)
-        offset, rows = 0, []
-        for _ in range(positions):
-            row, at = [], 0
-            for src, n in w:
-                if src >= 0:
-                    if row and row[-1][1] + row[-1][2] == src and row[-1][0] + row[-1][2] == at:
-                        row[-1] = (row[-1][0], row[-1][1], row[-1][2] + n)
-                    else:
-                        row.append((at, src, n))
-                at += n
-            rows.append(row)
-            n_seg = max(n_seg, len(row))
-            l_row = max([l_row] + [d + n for d, _, n in row])
-            total = sum(n for _, n in w)
-            a = int(half / timing_frames / sr * total * sr)
-            e = int(2 * half / timing_frames / sr * total * sr)
-            offset += half
-            w = cut(w, a, e) + section(offset + half, offset + 2 * half)
-        per_song.append(rows)
-    seg = np.zeros((len(per_song), positions, n_seg, 3), dtype=np.int32)
-    for i, rows in enumerate(per_song):
-        for k, row in enumerate(rows):
-            for j, piece in enumerate(row):
-                seg[i, k, j] = piece
-    return seg, (l_row + 3) // 4 * 4
-
-
-def admission_plan(finished, next_song, songs_left):
-    """The admission policy of the song queue, as data: `finished` = one flag per slot (true: the slot is free),
-    next_song = queue index of the next song, songs_left = how many songs the queue still holds.  Free slots in
-    ascending slot order take the next songs in queue order.  Returns [(slot, song), ...]."""
-    free = [b for b, f in enumerate(finished) if f]
-    n = min(len(free), max(int(songs_left), 0))
-    return [(free[i], int(next_song) + i) for i in range(n)]
-
-
-class FramePool:
-    """Host-side first-fit free list over the `frames` frames of the packed spectrogram pool: alloc(n) returns the
-    first frame of the lowest free region of at least n frames (None: nothing fits now), release(first) takes a region
-    back and merges it with free neighbours.  A request larger than the pool can never fit: ValueError."""
-
-    def __init__(self, frames):
-        self.frames = int(frames)
-        if self.frames < 1:
-            raise ValueError('run_song_queue: pool_frames must be at least 1')
-        self.free = [(0, self.frames)]                             # (first, length), ascending, never adjacent
-        self.used = {}
-
-    def alloc(self, n):
-        n = int(n)
-        if n > self.frames:
-            raise ValueError('run_song_queue: a song of %d frames is longer than the pool (%d frames)' % (n, self.frames))
-        for i, (a, m) in enumerate(self.free):
-            if m >= n:
-                if m == n:
-                    del self.free[i]
-                else:
-                    self.free[i] = (a + n, m - n)
-                self.used[a] = n
-                return a
-        return None
-
-    def release(self, first):
-        n = self.used.pop(first)
-        self.free.append((first, n))
-        self.free.sort()
-        merged = []
-        for a, m in self.free:
-            if merged and merged[-1][0] + merged[-1][1] == a:
-                merged[-1] = (merged[-1][0], merged[-1][1] + m)
-            else:
-                merged.append((a, m))
-        self.free = merged
-
-
-class SongState:
-    """What prepare_songs() builds and walk_songs() advances: the packed song spectrograms and samples, the live
-    windows (`batch`), the per-song integers offset / count / finished / clean [B] and the song-level constants."""
 
 
 class TranscriptionLoop:
@@ -427,135 +315,23 @@ class TranscriptionLoop:
             self.iterate(b, it, events, window0)
         return events, b
 
-    def prepare_songs(self, songs, refs=None, spectra=None):
-        """Set-up of the song walk, once per batch of songs: one STFT per song (training.py:265-269) packed frame-major
-        into one buffer, the song-level constants (:269-282), the first window of every song (section(0, None,
-        timing_frames), :284), the raw-sample table of amt_song_wave and the per-song integers.
-        songs: sequence of 1-d float32 waveforms of at least one hop.  refs: optional dict(ref_mag, ref_C_1, ref_C_inst,
-        ref_C_foc) of [B] tensors instead of the constants computed here.  spectra: optional AudioBatch that already
-        holds the songs' STFT (mag, ph, ref_max; songs of equal length, one per row) -- it is read, not changed.
-        Returns the state walk_songs() advances."""
-        if not self._dev_ready:
-            self.setup_device()
-        p = self.p
-        songs = list(songs)
-        if not songs:
-            raise ValueError('run_songs: no songs given')
-        if 'timing' not in self.heads or not self.do_subtract:
-            raise ValueError('run_songs: the walk needs the timing heads and the subtraction')
-        tf = p.timing_frames
-        if tf % 2:
-            raise ValueError('Invalid Input shape. run_songs needs an even timing_frames. Got: %d' % tf)
-        half, B = tf // 2, len(songs)
-        waves = [to_dev(s).reshape(-1) for s in songs]
-        for w in waves:
-            if w.numel() < p.H:
-                raise ValueError('Invalid Input shape. Expected: a song of at least one hop (%d samples) . Got: %d'
-                                 % (p.H, w.numel()))
-        lens = [int(w.numel()) for w in waves]
-        t_song = [1 + n // p.H for n in lens]
-        fbase = np.concatenate(([0], np.cumsum(t_song)))
-        sbase = np.concatenate(([0], np.cumsum(lens)))
-        ldf = ldf_of(p.N)
-        s_mag, s_ph = empty((int(fbase[-1]), ldf)), empty((int(fbase[-1]), ldf, 2))
-        b = AudioBatch(None, p.N, p.H)
-        b.mag, b.ph, b.ref_max = zeros((B, tf, ldf)), zeros((B, tf, ldf, 2)), empty((B,))
-        own = {}
-        normalisers = (('pitch', 'ref_C_1', self.tab_ref1), ('instrument', 'ref_C_inst', self.tab_refi),
-                       ('velocity', 'ref_C_foc', self.tab_reff))
-        for i, w in enumerate(waves):
-            if spectra is not None:
-                mag, ph, ref_max = spectra.mag[i], spectra.ph[i], spectra.ref_max[i]
-                if mag.shape[0] != t_song[i]:
-                    raise ValueError('Invalid Input shape. Expected: %d frames . Got: %d' % (t_song[i], mag.shape[0]))
-            else:
-                a = AudioBatch(w[None, :], p.N, p.H).stft(with_phase=True)
-                mag, ph, ref_max = a.mag[0], a.ph[0], a.ref_max[0]
-            f0, n0 = int(fbase[i]), min(tf, t_song[i])
-            s_mag[f0:f0 + t_song[i]], s_ph[f0:f0 + t_song[i]] = mag, ph
-            b.mag[i, :n0], b.ph[i, :n0] = mag[:n0], ph[:n0]
-            if refs is None:
-                own.setdefault('ref_mag', []).append(ref_max.clone())
-                for head, key, tab in normalisers:
-                    if head in self.heads:
-                        own.setdefault(key, []).append(cqt_window_max(w[None, :], tab, p.H)[0])
-        st = SongState()
-        st.refs = {k: torch.stack(v).contiguous() for k, v in own.items()} if refs is None else \
-            {k: to_dev(v).reshape(B).contiguous() for k, v in refs.items()}
-        st.batch, st.s_mag, st.s_ph, st.samples = b, s_mag, s_ph, torch.cat(waves)
-        st.positions = max(-(-t // half) for t in t_song)            # window positions of the longest song
-        seg, st.l_row = song_wave_segments(lens, t_song, tf, p.sr, st.positions, min_len=tf * p.H)
-        st.seg = to_dev(seg, torch.int32)
-        st.t_song = to_dev(np.asarray(t_song, dtype=np.int32), torch.int32)
-        st.frame_base = to_dev(fbase[:-1].astype(np.int64), torch.int64)
-        st.sample_base = to_dev(sbase[:-1].astype(np.int64), torch.int64)
-        st.offset, st.count, st.finished = (zeros((B,), torch.int32) for _ in range(3))
-        st.clean = torch.ones((B,), dtype=torch.int32, device=st.offset.device)
-        st.slide, st.detect, st.kind = (empty((B,), torch.int32) for _ in range(3))
-        st.wave = empty((B, st.l_row))
-        st.steps = 0
-        return st
-
-    def _song_step_fns(self, st, max_notes, silence):
-        """What _step() needs from the song walk (walk_songs and the song queue share it): wave_fn() = the windows'
-        waveform for the CQT heads, decide(onset, end, guess_frames) = the step's slide / detect masks."""
-        p, b, sp = self.p, st.batch, stream_ptr()
-        tf = p.timing_frames
-        half, B, ldf = tf // 2, b.mag.shape[0], b.mag.shape[2]
-        self.refs = st.refs
-        l_istft = p.H * (tf - 1)
-
-        def wave_fn():
-            # util_audio.py:94-97 for windows that had a subtraction (their _wf is None: the mag setter cleared it, slice
-            # and concat keep None); the raw samples section / slice / concat carry along for the others
-            _lib.check(self.lib.amt_istft(b.plan, ptr(b.mag), ptr(b.ph), B, tf, ldf, tf * ldf, ptr(st.wave), st.l_row,
-                                          sp))
-            _lib.check(self.lib.amt_song_wave(ptr(st.samples), ptr(st.sample_base), ptr(st.seg), B, int(st.seg.shape[1]),
-                                              int(st.seg.shape[2]), ptr(st.offset), half, ptr(st.clean),
-                                              ptr(st.finished), ptr(st.wave), st.l_row, st.l_row, l_istft, sp))
-            return st.wave
-
-        def decide(onset, end, gfr):
-            wmax = empty((B,))
-            _lib.check(self.lib.amt_song_decide(ptr(onset), ptr(b._fmax[0]), B, tf, ptr(st.refs['ref_mag']),
-                                                float(silence), half, int(max_notes), ptr(st.finished), ptr(st.count),
-                                                ptr(st.clean), ptr(st.slide), ptr(st.detect), ptr(st.kind), ptr(gfr),
-                                                ptr(wmax), sp))
-            b.ref_max = wmax                                         # np.max(audio_w.mag) at the subtraction (:170-174)
-
-        return wave_fn, decide
+    def prepare_songs(self, songs, refs=None, spectra=None, song0=0):
+        """Set-up of the song walk, once per batch of songs: a song_walk.SongState of one slot per song and ONE admission
+        of song i into slot i (SongState.admit: the songs' STFT, training.py:265-269, the song-level constants, :269-282,
+        the first windows, section(0, None, timing_frames), :284, the raw-sample table and the per-song integers).
+        songs: sequence of 1-d float32 waveforms of more than n_fft / 2 samples.  refs: optional dict(ref_mag, ref_C_1,
+        ref_C_inst, ref_C_foc) of [B] tensors instead of the constants computed here.  spectra: optional AudioBatch that
+        already holds the songs' STFT (mag, ph, ref_max; songs of equal length, one per row) -- it is read, not changed.
+        song0: the index of the first song (state.slot_song).  Returns the state walk_songs() advances."""
+        song_walk.check_walk(self)
+        return song_walk.prepare_songs(self, songs, refs=refs, spectra=spectra, song0=song0)
 
     def walk_songs(self, st, max_notes=8, silence=1e-3, poll=16, song0=0, max_steps=None):
         """The steps of the song walk on a state from prepare_songs(); see run_songs().  max_steps: stop after that many
         steps even if songs are unfinished (the state can be inspected, not resumed).  Returns events [steps, B, 9] int32
         (device)."""
-        if int(max_notes) < 1:
-            raise ValueError('run_songs: max_notes must be at least 1')
-        if not float(silence) >= 0.0:
-            raise ValueError('run_songs: silence must be >= 0')
-        p, b, sp = self.p, st.batch, stream_ptr()
-        tf = p.timing_frames
-        half, B, ldf = tf // 2, b.mag.shape[0], b.mag.shape[2]
-        wave_fn, decide = self._song_step_fns(st, max_notes, silence)
-        st.bound = st.positions * (int(max_notes) + 1)
-        if max_steps is not None:
-            st.bound = min(st.bound, int(max_steps))
-        events = empty((st.bound, B, len(SONG_EVENT_FIELDS)), torch.int32)
-        steps = 0
-        while steps < st.bound:
-            onset, end, pitch, program, velocity = self._step(b, wave_fn, fmax=True, before_subtract=decide)
-            _lib.check(self.lib.amt_song_pack_events(B, int(song0), steps, ptr(st.kind), ptr(pitch), ptr(program),
-                                                     ptr(velocity), ptr(onset), ptr(end), ptr(st.offset),
-                                                     ptr(events[steps]), sp))
-            _lib.check(self.lib.amt_song_slide(ptr(b.mag), ptr(b.ph), B, tf, ldf, tf * ldf, ptr(st.s_mag), ptr(st.s_ph),
-                                               ptr(st.frame_base), ptr(st.t_song), ptr(st.slide), ptr(st.offset),
-                                               ptr(st.count), ptr(st.finished), sp))
-            b._fmax = None                                           # the slid windows' per-frame maxima are stale
-            steps += 1
-            if steps % max(int(poll), 1) == 0 and int(st.finished.sum()) == B:
-                break
-        st.steps = steps
-        return events[:steps]
+        song_walk.check_walk(self, max_notes, silence)
+        return song_walk.walk_songs(st, max_notes, silence, poll=poll, song0=song0, max_steps=max_steps)
 
     def run_songs(self, songs, max_notes=8, silence=1e-3, poll=16, song0=0, refs=None):
         """The reference's own traversal (training.py:284, :296-328) with the predicted note where it has the gold
@@ -563,7 +339,7 @@ class TranscriptionLoop:
         (one STFT per song) and, whenever the predicted onset lies in its second half, slid by half a window with
         the residual of every subtraction kept.  prepare_songs() + walk_songs().
 
-        songs: sequence of 1-d float32 waveforms (device tensors or arrays) of any lengths >= one hop.
+        songs: sequence of 1-d float32 waveforms (device tensors or arrays) of any lengths > n_fft / 2 samples.
         Per step and unfinished song (amt_song_decide): onset >= half -> slide; else count == max_notes or
         max(window) <= silence * ref_mag(song) -> forced slide; else detect (remaining heads, guess, subtraction as in
         run(); count += 1).  A slide moves the second half of the window to the first, appends the next half window
@@ -579,21 +355,21 @@ class TranscriptionLoop:
         Returns (events [steps, B, 9] int32 device, SONG_EVENT_FIELDS; state): state.batch is the AudioBatch holding
         every song's last window (residual magnitudes, unit phases, maxima), state.offset / count / finished /
         t_song the per-song integers, state.refs the song-level constants."""
-        if int(max_notes) < 1:
-            raise ValueError('run_songs: max_notes must be at least 1')
-        st = self.prepare_songs(songs, refs=refs)
-        return self.walk_songs(st, max_notes=max_notes, silence=silence, poll=poll, song0=song0), st
+        song_walk.check_walk(self, max_notes, silence)
+        st = song_walk.prepare_songs(self, songs, refs=refs, song0=song0)
+        return song_walk.walk_songs(st, max_notes, silence, poll=poll, song0=song0), st
 
     def iter_song_queue(self, songs, slots, max_notes=8, silence=1e-3, poll=16, pool_frames=None, on_finish=None):
         """Continuous batching of the song walk: any number of songs of any lengths walked through `slots` live windows,
         a finished slot handed to the next song of the queue (the reference's unit of work is a dataset of songs, one
-        song after the other per worker, training.py:623-634).  The step is run_songs' step, unchanged; a song's records
-        are those run_songs([song]) gives for it alone, whatever shares the batch with it.
+        song after the other per worker, training.py:623-634).  State, admission and step are run_songs' own
+        (song_walk.SongState); a song's records are those run_songs([song]) gives for it alone, whatever shares the
+        batch with it.
 
         songs: a sequence or an iterator of 1-d float32 waveforms (arrays or tensors), consumed lazily -- only the
-        songs in a slot, and up to `slots` waiting ones, are held.  Yields (song_index, events [k, 9] int32 host array)
-        as each song finishes: the song's own records in step order (kinds DETECT / SLIDE / FORCED_SLIDE), `step`
-        counted from 0 within the song, `song` = its index in the queue.
+        songs in a slot, and up to `slots` waiting ones, are held; a song is checked when it is pulled.  Yields
+        (song_index, events [k, 9] int32 host array) as each song finishes: the song's own records in step order (kinds
+        DETECT / SLIDE / FORCED_SLIDE), `step` counted from 0 within the song, `song` = its index in the queue.
 
         Admission happens where the walk polls anyway (before the first step, then every `poll` steps): the host reads
         `finished` and the last `poll` steps' records in one pinned copy, yields the finished songs, and the free slots,
@@ -606,7 +382,7 @@ class TranscriptionLoop:
         and the songs behind it wait with it (queue order is kept) while its slot idles -- with no song active the pool
         is empty and the next song fits, so the walk cannot stall.  Default pool_frames: slots x the frames of the
         longest of the first `slots` songs of the queue.
-        The per-slot tables that run_songs sizes from its whole batch (window positions and pieces of the raw-sample
+        The per-slot tables that run_songs sizes from its one admission (window positions and pieces of the raw-sample
         table, the row length of the CQT heads' waveform) grow at an admission that needs more; no record depends on them.
         ONE compute stream: the admission's STFT and normaliser kernels run on the stream of the networks, between two
         steps.  They are built with packed-FP32 instructions and must not overlap the networks' MFMA kernels on a side
@@ -620,179 +396,9 @@ class TranscriptionLoop:
         started on this loop; a second queue replaces it) -- dict(steps, songs, admissions, waits = admissions that
         stopped at a song without a free region, bound = the step cap so far, slot_steps = step slots per kind
         [detect, slide, forced slide, idle])."""
-        if int(slots) < 1:
-            raise ValueError('run_song_queue: slots must be at least 1')
-        if int(max_notes) < 1:
-            raise ValueError('run_songs: max_notes must be at least 1')
-        if not float(silence) >= 0.0:
-            raise ValueError('run_songs: silence must be >= 0')
-        if 'timing' not in self.heads or not self.do_subtract:
-            raise ValueError('run_songs: the walk needs the timing heads and the subtraction')
-        tf = self.p.timing_frames
-        if tf % 2:
-            raise ValueError('Invalid Input shape. run_songs needs an even timing_frames. Got: %d' % tf)
-        if pool_frames is not None and int(pool_frames) < 1:
-            raise ValueError('run_song_queue: pool_frames must be at least 1')
-        if not self._dev_ready:
-            self.setup_device()
-        p, B, poll = self.p, int(slots), max(int(poll), 1)
-        it, ahead, pulled = iter(songs), [], [0]
-
-        def pull(n):
-            """Songs waiting for a slot: up to n, validated as run_songs validates them."""
-            while len(ahead) < n:
-                w = next(it, None)
-                if w is None:
-                    break
-                w = to_dev(w).reshape(-1)
-                if w.numel() < p.H:
-                    raise ValueError('Invalid Input shape. Expected: a song of at least one hop (%d samples) . Got: %d'
-                                     % (p.H, w.numel()))
-                if w.numel() <= p.N // 2:                          # what amt_stft_mag answers for it in run_songs
-                    raise ValueError('Invalid Input shape. Expected: a song of more than n_fft / 2 = %d samples '
-                                     '(reflect padding) . Got: %d' % (p.N // 2, w.numel()))
-                ahead.append((pulled[0], w))
-                pulled[0] += 1
-
-        pull(B)
-        if not ahead:
-            raise ValueError('run_songs: no songs given')
-        if pool_frames is None:
-            pool_frames = B * max(1 + w.numel() // p.H for _, w in ahead)
-        return self._walk_song_queue(pull, ahead, pulled, B, int(max_notes), float(silence), poll, int(pool_frames),
-                                     on_finish)
-
-    def _walk_song_queue(self, pull, ahead, pulled, B, max_notes, silence, poll, pool_frames, on_finish):
-        p, sp = self.p, stream_ptr()
-        tf, ldf, dev = p.timing_frames, ldf_of(p.N), require_gpu()
-        half = tf // 2
-        st = SongState()
-        st.pool = FramePool(pool_frames)
-        st.s_mag, st.s_ph = empty((pool_frames, ldf)), empty((pool_frames, ldf, 2))
-        st.samples = empty((pool_frames * p.H,))                   # a song of T frames has fewer than T hops of samples
-        b = AudioBatch(None, p.N, p.H)
-        b.mag, b.ph, b.ref_max = zeros((B, tf, ldf)), zeros((B, tf, ldf, 2)), zeros((B,))
-        ref_keys = ['ref_mag'] + [k for h, k in (('pitch', 'ref_C_1'), ('instrument', 'ref_C_inst'),
-                                                 ('velocity', 'ref_C_foc')) if h in self.heads]
-        tabs = {'ref_C_1': self.tab_ref1, 'ref_C_inst': self.tab_refi, 'ref_C_foc': self.tab_reff}
-        st.refs = {k: torch.ones((B,), dtype=torch.float32, device=dev) for k in ref_keys}   # idle slots divide by 1
-        st.batch = b
-        st.t_song, st.offset, st.count = (zeros((B,), torch.int32) for _ in range(3))
-        st.frame_base, st.sample_base = zeros((B,), torch.int64), zeros((B,), torch.int64)
-        st.finished, st.clean = (torch.ones((B,), dtype=torch.int32, device=dev) for _ in range(2))
-        st.slot_song = torch.full((B,), -1, dtype=torch.int32, device=dev)
-        st.slide, st.detect, st.kind = (empty((B,), torch.int32) for _ in range(3))
-        st.seg = zeros((B, 1, 1, 3), torch.int32)
-        st.l_row = (tf * p.H + 3) // 4 * 4
-        st.wave = empty((B, st.l_row))
-        st.steps = 0
-        wave_fn, decide = self._song_step_fns(st, max_notes, silence)
-        chunk = empty((poll, B, len(SONG_EVENT_FIELDS)), torch.int32)
-        host_chunk = torch.empty(tuple(chunk.shape), dtype=torch.int32, pin_memory=True)
-        host_fin = torch.empty((B,), dtype=torch.int32, pin_memory=True)
-        slot_song, region, records = [-1] * B, [None] * B, {}
-        stats = self.queue_stats = st.stats = dict(steps=0, songs=0, admissions=0, waits=0, bound=0,
-                                        slot_steps=[0, 0, 0, 0])   # per kind: detect, slide, forced slide, idle
-
-        def admit():
-            pull(sum(s < 0 for s in slot_song))
-            plan = admission_plan([s < 0 for s in slot_song], ahead[0][0] if ahead else pulled[0], len(ahead))
-            new = []
-            for slot, idx in plan:
-                w = ahead[0][1]
-                f0 = st.pool.alloc(1 + w.numel() // p.H)
-                if f0 is None:                                     # waits for a region; the songs behind it wait too
-                    stats['waits'] += 1
-                    break
-                ahead.pop(0)
-                new.append((slot, idx, w, f0))
-            if not new:
-                return
-            n = len(new)
-            lens = [int(w.numel()) for _, _, w, _ in new]
-            t_song = [1 + L // p.H for L in lens]
-            fbase = np.asarray([f0 for _, _, _, f0 in new], np.int64)
-            for (_, _, w, f0), L in zip(new, lens):
-                st.samples[f0 * p.H:f0 * p.H + L].copy_(w)
-            d_fb, d_sb = to_dev(fbase, torch.int64), to_dev(fbase * p.H, torch.int64)
-            d_len = to_dev(np.asarray(lens, np.int32), torch.int32)
-            new_refs = {'ref_mag': empty((n,))}
-            _lib.check(self.lib.amt_stft_mag_ragged(b.plan, ptr(st.samples), ptr(d_sb), ptr(d_len), n, max(lens),
-                                                    st.samples.numel(), sum(lens), ptr(st.s_mag), ptr(st.s_ph),
-                                                    ptr(new_refs['ref_mag']), ptr(d_fb), pool_frames, ldf, sp))
-            for k in ref_keys[1:]:
-                new_refs[k] = torch.cat([cqt_window_max(st.samples[f0 * p.H:f0 * p.H + L][None, :], tabs[k], p.H)
-                                         for (_, _, _, f0), L in zip(new, lens)]).contiguous()
-            seg, l_row = song_wave_segments(lens, t_song, tf, p.sr, max(-(-t // half) for t in t_song),
-                                            min_len=tf * p.H)
-            K, S = max(seg.shape[1], st.seg.shape[1]), max(seg.shape[2], st.seg.shape[2])
-            if (K, S) != tuple(st.seg.shape[1:3]):                 # the per-slot piece table grows, its rows are kept
-                grown = zeros((B, K, S, 3), torch.int32)
-                grown[:, :st.seg.shape[1], :st.seg.shape[2]] = st.seg
-                st.seg = grown
-            if l_row > st.l_row:
-                st.l_row, st.wave = l_row, empty((B, l_row))
-            seg_new = np.zeros((n, K, S, 3), np.int32)
-            seg_new[:, :seg.shape[1], :seg.shape[2]] = seg
-            mask = np.zeros(B, np.int32)
-            for j, (slot, idx, _, f0) in enumerate(new):
-                mask[slot] = 1 + j
-                slot_song[slot], region[slot], records[idx] = idx, f0, []
-                stats['bound'] += -(-(-(-t_song[j] // half) * (max_notes + 1)) // poll) * poll
-            d_mask, d_seg = to_dev(mask, torch.int32), to_dev(seg_new, torch.int32)
-            d_ts, d_song = to_dev(np.asarray(t_song, np.int32), torch.int32), \
-                to_dev(np.asarray([idx for _, idx, _, _ in new], np.int32), torch.int32)
-            a = _lib.song_admit_args(
-                w_mag=b.mag, w_ph=b.ph, s_mag=st.s_mag, s_ph=st.s_ph, admit=d_mask, new_frame_base=d_fb, new_t_song=d_ts,
-                new_sample_base=d_sb, new_song=d_song, new_seg=d_seg, new_ref=[new_refs[k] for k in ref_keys],
-                frame_base=st.frame_base, t_song=st.t_song, sample_base=st.sample_base, slot_song=st.slot_song,
-                seg=st.seg, ref=[st.refs[k] for k in ref_keys], offset=st.offset, count=st.count,
-                finished=st.finished, clean=st.clean, w_stride=tf * ldf, B=B, n_new=n, T=tf, ldf=ldf, K=K, S=S)
-            _lib.check(self.lib.amt_song_admit(C.byref(a), sp))
-            b._fmax = None                                         # the admitted windows' per-frame maxima are stale
-            stats['admissions'] += 1
-            stats['songs'] += n
-
-        admit()
-        while any(s >= 0 for s in slot_song):
-            for r in range(poll):
-                onset, end, pitch, program, velocity = self._step(b, wave_fn, fmax=True, before_subtract=decide)
-                _lib.check(self.lib.amt_song_pack_events_slots(B, ptr(st.slot_song), st.steps, ptr(st.kind), ptr(pitch),
-                                                               ptr(program), ptr(velocity), ptr(onset), ptr(end),
-                                                               ptr(st.offset), ptr(chunk[r]), sp))
-                _lib.check(self.lib.amt_song_slide(ptr(b.mag), ptr(b.ph), B, tf, ldf, tf * ldf, ptr(st.s_mag),
-                                                   ptr(st.s_ph), ptr(st.frame_base), ptr(st.t_song), ptr(st.slide),
-                                                   ptr(st.offset), ptr(st.count), ptr(st.finished), sp))
-                b._fmax = None
-                st.steps += 1
-            host_chunk.copy_(chunk, non_blocking=True)
-            host_fin.copy_(st.finished, non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-            ev = host_chunk.numpy()
-            stats['steps'] = st.steps
-            kinds = np.bincount(ev[:, :, 2].ravel(), minlength=4)
-            for k in range(4):
-                stats['slot_steps'][k] += int(kinds[k])
-            done = []
-            for slot, idx in enumerate(slot_song):
-                if idx < 0:
-                    continue
-                rows = ev[:, slot, :]
-                records[idx].append(rows[rows[:, 2] != SONG_FINISHED].copy())
-                if host_fin[slot]:
-                    done.append((slot, idx))
-            for slot, idx in done:
-                if on_finish is not None:
-                    on_finish(idx, slot, st)
-                out = np.concatenate(records.pop(idx))
-                out[:, 1] = np.arange(len(out))
-                st.pool.release(region[slot])
-                slot_song[slot], region[slot] = -1, None
-                yield idx, out
-            admit()
-            if st.steps > stats['bound']:
-                raise RuntimeError('run_song_queue: %d steps, past the bound of the admitted songs (%d)'
-                                   % (st.steps, stats['bound']))
+        song_walk.check_walk(self, max_notes, silence, slots, pool_frames)
+        return song_walk.iter_song_queue(self, songs, slots, max_notes, silence, poll=poll, pool_frames=pool_frames,
+                                         on_finish=on_finish)
 
     def run_song_queue(self, songs, slots, max_notes=8, silence=1e-3, poll=16, pool_frames=None, on_finish=None):
         """iter_song_queue() run to its end.  Returns the list of the songs' records, events [k, 9] int32 host arrays,

@@ -70,18 +70,19 @@ __global__ __launch_bounds__(256) void song_wave_kernel(
 // ---- events ----------------------------------------------------------------------------------------------------------
 // {song, step, kind, pitch, program, velocity, onset_frame, end_frame, offset_frame}; onset / end are song frames
 // (offset + the window frame); the note fields are -1 unless kind == detect, everything but song / step / kind / offset
-// is -1 for a finished song.
-__global__ void song_pack_kernel(int n, int song0, int step, const int32_t *__restrict__ kind,
-                                 const int32_t *__restrict__ pitch, const int32_t *__restrict__ program,
-                                 const int32_t *__restrict__ velocity, const int32_t *__restrict__ onset,
-                                 const int32_t *__restrict__ end, const int32_t *__restrict__ offset,
-                                 int32_t *__restrict__ events /* [n][9] */) {
+// is -1 for a finished song.  The song index is read per slot where a slot carries one song after the other (slot_song,
+// the song queue), song0 + slot where it does not.
+__global__ void song_pack_kernel(int n, const int32_t *__restrict__ slot_song, int song0, int step,
+                                 const int32_t *__restrict__ kind, const int32_t *__restrict__ pitch,
+                                 const int32_t *__restrict__ program, const int32_t *__restrict__ velocity,
+                                 const int32_t *__restrict__ onset, const int32_t *__restrict__ end,
+                                 const int32_t *__restrict__ offset, int32_t *__restrict__ events /* [n][9] */) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int k = kind[i];
     const bool det = k == AMT_SONG_DETECT, live = k != AMT_SONG_FINISHED;
     int32_t *e = events + (size_t)i * 9;
-    e[0] = song0 + i;
+    e[0] = slot_song ? slot_song[i] : song0 + i;
     e[1] = step;
     e[2] = k;
     e[3] = det && pitch ? pitch[i] : -1;
@@ -203,28 +204,6 @@ __global__ __launch_bounds__(256) void song_admit_state_kernel(amt_song_admit_ar
     a.clean[b] = 1;
 }
 
-// song_pack_kernel with the song index read per slot (a slot carries one song after the other)
-__global__ void song_pack_slots_kernel(int n, const int32_t *__restrict__ slot_song, int step,
-                                       const int32_t *__restrict__ kind, const int32_t *__restrict__ pitch,
-                                       const int32_t *__restrict__ program, const int32_t *__restrict__ velocity,
-                                       const int32_t *__restrict__ onset, const int32_t *__restrict__ end,
-                                       const int32_t *__restrict__ offset, int32_t *__restrict__ events /* [n][9] */) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int k = kind[i];
-    const bool det = k == AMT_SONG_DETECT, live = k != AMT_SONG_FINISHED;
-    int32_t *e = events + (size_t)i * 9;
-    e[0] = slot_song[i];
-    e[1] = step;
-    e[2] = k;
-    e[3] = det && pitch ? pitch[i] : -1;
-    e[4] = det && program ? program[i] : -1;
-    e[5] = det && velocity ? velocity[i] : -1;
-    e[6] = live ? offset[i] + onset[i] : -1;
-    e[7] = live ? offset[i] + end[i] : -1;
-    e[8] = offset[i];
-}
-
 extern "C" {
 
 int amt_song_admit(const amt_song_admit_args *args, void *stream) {
@@ -253,8 +232,8 @@ int amt_song_pack_events_slots(int n, const int32_t *slot_song, int step, const 
                                const int32_t *program, const int32_t *velocity, const int32_t *onset, const int32_t *end,
                                const int32_t *offset, int32_t *events, void *stream) {
     if (!slot_song || !kind || !onset || !end || !offset || !events || n <= 0) return AMT_E_INVALID;
-    song_pack_slots_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(n, slot_song, step, kind, pitch, program,
-                                                                              velocity, onset, end, offset, events);
+    song_pack_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(n, slot_song, 0, step, kind, pitch, program, velocity,
+                                                                        onset, end, offset, events);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }
@@ -288,8 +267,8 @@ int amt_song_pack_events(int n, int song0, int step, const int32_t *kind, const 
                          const int32_t *velocity, const int32_t *onset, const int32_t *end, const int32_t *offset,
                          int32_t *events, void *stream) {
     if (!kind || !onset || !end || !offset || !events || n <= 0) return AMT_E_INVALID;
-    song_pack_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(n, song0, step, kind, pitch, program, velocity,
-                                                                        onset, end, offset, events);
+    song_pack_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(n, nullptr, song0, step, kind, pitch, program,
+                                                                        velocity, onset, end, offset, events);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }

@@ -193,6 +193,48 @@ def test_one_window_song_equals_run(env):
     assert ev_s.shape[0] == iters and torch.equal(st.batch.mag, b.mag) and torch.equal(st.batch.ref_max, b.ref_max)
 
 
+def test_spectra_and_refs_go_through_the_admission(env):
+    """prepare_songs(refs=, spectra=) is the one admission with two of its inputs given.  As the test above with three
+    songs and two iterations, on a spectrogram that is NOT the songs' STFT (magnitudes, maxima and ref_mag halved: exact,
+    so the features are the same floats), so that only a copy from `spectra` can put it into the windows: the AudioBatch
+    is unchanged afterwards, the state's normalisers are the given ones, and none is computed -- the loop's normaliser
+    tables are None during the call."""
+    torch, synth = env['torch'], env['synth']
+    p = env['hp'].Hyperparams(N=2048, window_size_note_time=1)
+    heads, iters, B = ('timing', 'pitch', 'instrument', 'velocity'), 2, 3
+    lp = env['loop'].TranscriptionLoop(p, heads=heads, iters=iters, groups=(0, 1, 2)).setup_device()
+    L = p.H * (p.timing_frames - 1)
+    wave, _ = synth.make_windows(B, L, seed=21, notes_per_window=(1, 3), groups=(0, 1, 2), max_onset=0.3, device='cuda')
+    b = lp.prepare(wave)
+    b.mag.mul_(0.5)
+    b.ref_max.mul_(0.5)
+    refs = {k: v.clone() for k, v in lp.refs.items()}
+    refs['ref_mag'].mul_(0.5)
+    before = (b.mag.clone(), b.ph.clone(), b.ref_max.clone())
+    given = {k: v.clone() for k, v in refs.items()}
+    tabs = (lp.tab_ref1, lp.tab_refi, lp.tab_reff)
+    lp.tab_ref1 = lp.tab_refi = lp.tab_reff = None
+    try:
+        st = lp.prepare_songs([w for w in wave], refs=refs, spectra=b)
+    finally:
+        lp.tab_ref1, lp.tab_refi, lp.tab_reff = tabs
+    assert torch.equal(b.mag, before[0]) and torch.equal(b.ph, before[1]) and torch.equal(b.ref_max, before[2])
+    assert torch.equal(st.batch.mag, b.mag) and torch.equal(st.batch.ph, b.ph)
+    assert set(st.refs) == set(given)
+    for k, v in given.items():
+        assert torch.equal(st.refs[k], v) and torch.equal(refs[k], v), k
+    assert st.slot_song.tolist() == [0, 1, 2] and st.finished.tolist() == [0, 0, 0]
+    ev_s = lp.walk_songs(st, max_notes=iters, silence=0.0, poll=1, max_steps=iters).cpu().numpy()
+    lp.refs = refs
+    ev_r = torch.empty((iters, B, 7), dtype=torch.int32, device='cuda')
+    for it in range(iters):
+        lp.iterate(b, it, ev_r)
+    ev_r = ev_r.cpu().numpy()
+    assert np.all(ev_s[:iters, :, 2] == so.DETECT), ev_s[:iters, :, 2]
+    assert np.array_equal(ev_s[:iters, :, 3:8], ev_r[:, :, 2:7])
+    assert ev_s.shape[0] == iters and torch.equal(st.batch.mag, b.mag) and torch.equal(st.batch.ref_max, b.ref_max)
+
+
 def test_full_depth_fixture(env):
     """The walk at the production window (516 frames, half = 258, the real 33-layer heads) against the committed CPU
     restatement (tests/golden/gen_song_fixtures.py): integer events bit-exact, every pre-rounding head float inside

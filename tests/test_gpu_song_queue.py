@@ -286,6 +286,16 @@ def test_admit_kernel_vs_numpy(env):
                                           on.data_ptr(), en.data_ptr(), off.data_ptr(), ev.data_ptr(), None) == _lib.AMT_OK
     assert ev.cpu().tolist() == [[7, 21, 0, 60, -1, -1, 48, 52, 43], [3, 21, 1, -1, -1, -1, 50, 60, 0],
                                  [-1, 21, 3, -1, -1, -1, -1, -1, 86], [12, 21, 2, -1, -1, -1, 138, 149, 129]]
+    # ... and with song0 + slot: one kernel behind both entries, so song0 = 7 and slot_song = 7 .. 10 write the same
+    ev0, ev1 = (torch.full((4, 9), -5, dtype=torch.int32, device='cuda') for _ in range(2))
+    assert lib.amt_song_pack_events(4, 7, 21, kind.data_ptr(), pit.data_ptr(), None, None, on.data_ptr(), en.data_ptr(),
+                                    off.data_ptr(), ev0.data_ptr(), None) == _lib.AMT_OK
+    assert lib.amt_song_pack_events_slots(4, i32([7, 8, 9, 10]).data_ptr(), 21, kind.data_ptr(), pit.data_ptr(), None,
+                                          None, on.data_ptr(), en.data_ptr(), off.data_ptr(), ev1.data_ptr(),
+                                          None) == _lib.AMT_OK
+    assert torch.equal(ev0, ev1)
+    assert ev0.cpu().tolist() == [[7, 21, 0, 60, -1, -1, 48, 52, 43], [8, 21, 1, -1, -1, -1, 50, 60, 0],
+                                  [9, 21, 3, -1, -1, -1, -1, -1, 86], [10, 21, 2, -1, -1, -1, 138, 149, 129]]
 
 
 @pytest.mark.parametrize('case', list(so.WALK_CASES))
@@ -395,3 +405,80 @@ def test_song_queue_argument_checks(env):
         env['loop'].TranscriptionLoop(p, heads=('pitch',)).setup_device().run_song_queue([song], 2)
     evs = lp.run_song_queue([song], 3, max_notes=1)                 # a silent song: forced slides only, the walk ends
     assert len(evs) == 1 and set(evs[0][:, 2].tolist()) <= {so.SLIDE, so.FORCED_SLIDE}
+
+
+SYNTHETIC = ('timing', 'pitch', 'velocity')
+
+
+def test_fixed_batch_is_one_admission(env):
+    """prepare_songs is a state of one slot per song and one admission of song i into slot i: for a song shorter than
+    the first window (zero rows after its end), one of exactly hop x (timing_frames - 1) samples and one of 2.3 windows
+    off the hop grid, its state and a queue's state after the first admission (3 slots, the queue's default pool) hold
+    bit-identical windows, equal integers and normalisers and the same raw samples for the CQT heads; the queue's own
+    state, seen in on_finish, has the same song lengths and normalisers.  Then run_songs against run_song_queue: equal
+    live records, and run_songs' song column is song0 + slot in every row, FINISHED ones included."""
+    torch, lib, _lib, loop = env['torch'], env['lib'], env['_lib'], env['loop']
+    p, lp = _make_loop(env, 2048, 1, 'bank', heads=SYNTHETIC)
+    tf, half = p.timing_frames, p.timing_frames // 2
+    L = p.H * (tf - 1)
+    n = [int(0.7 * L), L, int(2.3 * L)]
+    assert 1 + n[0] // p.H < tf and n[2] % p.H and (tf, half) == (86, 43)
+    songs = [s[:k].copy() for s, k in zip(so.make_songs(p, 61, (1.5, 2.1, 4.7)), n)]
+    assert [len(s) for s in songs] == n
+    fixed = lp.prepare_songs(songs)
+    queue = loop.SongState(lp, 3, 3 * max(1 + k // p.H for k in n))
+    assert len(queue.admit([(i, i, torch.from_numpy(s).cuda()) for i, s in enumerate(songs)])) == 3
+    assert torch.equal(fixed.batch.mag, queue.batch.mag) and torch.equal(fixed.batch.ph, queue.batch.ph)
+    assert bool((fixed.batch.mag[0, 1 + n[0] // p.H:] == 0).all()) and bool((fixed.batch.mag[0, n[0] // p.H] != 0).any())
+    for name in ('t_song', 'offset', 'count', 'finished', 'clean', 'slot_song'):
+        assert torch.equal(getattr(fixed, name), getattr(queue, name)), name
+    assert fixed.t_song.tolist() == [1 + k // p.H for k in n] and fixed.finished.tolist() == [0, 0, 0]
+    assert set(fixed.refs) == set(queue.refs) == {'ref_mag', 'ref_C_1', 'ref_C_foc'}
+    for k in fixed.refs:
+        assert torch.equal(fixed.refs[k], queue.refs[k]), k
+    assert fixed.l_row == queue.l_row
+    rows = []
+    for st in (fixed, queue):
+        out = torch.zeros((3, st.l_row), device='cuda')
+        assert lib.amt_song_wave(st.samples.data_ptr(), st.sample_base.data_ptr(), st.seg.data_ptr(), 3,
+                                 int(st.seg.shape[1]), int(st.seg.shape[2]), st.offset.data_ptr(), half,
+                                 st.clean.data_ptr(), st.finished.data_ptr(), out.data_ptr(), st.l_row, st.l_row, L,
+                                 None) == _lib.AMT_OK
+        rows.append(out)
+    assert torch.equal(rows[0], rows[1]) and bool((rows[0] != 0).any(dim=1).all())
+    seen = []
+
+    def look(idx, slot, st):
+        seen.append(idx)
+        assert torch.equal(st.t_song, fixed.t_song) and st.pool.frames == queue.pool.frames
+        for k in fixed.refs:
+            assert torch.equal(st.refs[k], fixed.refs[k]), k
+    ev, st = lp.run_songs(songs, max_notes=2, silence=1e-4, poll=1, song0=5)
+    evs = lp.run_song_queue(songs, 3, max_notes=2, silence=1e-4, poll=1, on_finish=look)
+    assert sorted(seen) == [0, 1, 2] and st.slot_song.tolist() == [5, 6, 7]
+    e = ev.cpu().numpy()
+    assert bool((e[:, 0, 2] == so.FINISHED).any()) and bool((e[:, :, 2] == so.DETECT).any())
+    for i in range(3):
+        assert np.all(e[:, i, 0] == 5 + i), i
+        live = e[:, i][e[:, i, 2] != so.FINISHED]
+        assert np.array_equal(live[:, 2:], evs[i][:, 2:]), (i, live.tolist(), evs[i].tolist())
+
+
+def test_one_refusal_for_short_songs(env):
+    """A song of one hop and a song of n_fft / 2 samples (too short for the reflect padding) are refused by run_songs and
+    by the queue with one and the same text; n_fft / 2 + 1 samples are walked to the end by both, with equal records."""
+    p, lp = _make_loop(env, 2048, 1, 'bank', heads=SYNTHETIC)
+    rng = np.random.default_rng(5)
+    for n in (p.H, p.N // 2):
+        s = rng.standard_normal(n).astype(np.float32)
+        with pytest.raises(ValueError, match='Invalid Input shape') as fixed:
+            lp.run_songs([s])
+        with pytest.raises(ValueError, match='Invalid Input shape') as queue:
+            lp.run_song_queue([s], 2)
+        assert str(fixed.value) == str(queue.value) and str(n) in str(fixed.value)
+    s = (0.1 * rng.standard_normal(p.N // 2 + 1)).astype(np.float32)
+    ev, st = lp.run_songs([s], max_notes=2, silence=1e-4, poll=1)
+    e = ev.cpu().numpy()[:, 0, :]
+    evs = lp.run_song_queue([s], 2, max_notes=2, silence=1e-4, poll=1)
+    assert st.finished.tolist() == [1] and len(evs) == 1
+    assert len(evs[0]) >= 1 and np.array_equal(e[e[:, 2] != so.FINISHED], evs[0])
