@@ -1,5 +1,5 @@
-// RDCNN forward (res_net.predict) for gfx950, host side: topology walk, weight folding and pre-arrangement, the
-// per-layer launch plan, and the forward walk.  The convolutions are implicit GEMMs on the matrix pipe with fused
+// RDCNN forward (res_net.predict) for gfx950, host side: weight folding and pre-arrangement over the topology
+// (amt_rdcnn_topology.h), the per-layer launch plan, and the forward walk.  The convolutions are implicit GEMMs on the matrix pipe with fused
 // BN + sigmoid (+ shortcut add + BN) epilogues, in three f32-equivalent arithmetics:
 //   mode 2 (default) split-fp16, amt_conv_f16x3.h;  mode 1 split-bf16, amt_conv_bf16x6.h;  mode 0 f32 MFMA,
 //   amt_conv_f32.h;  mode 3 = mode 2 with the large 4 x 16 layers in the FFT domain (amt_fftconv.h).
@@ -12,6 +12,7 @@
 #include "amt_common.h"
 #include "amt_fftconv.h"
 #include "amt_convh.h"
+#include "amt_rdcnn_topology.h"
 #include <vector>
 #include <algorithm>
 #include <cmath>
@@ -25,7 +26,7 @@
 #define RD_BN_EPS 1e-3f
 
 // =====================================================================================
-// Host side: topology walk, weight folding / pre-arrangement, launch plan
+// Host side: weight folding / pre-arrangement, launch plan
 // =====================================================================================
 // Launch plan of one convolution variant: workgroup tile, LDS bytes, N-slicing and the weights in the variant's layout
 struct ConvPlan {
@@ -393,38 +394,6 @@ static bool impl_writes_amax(ConvImpl impl) {
     return impl == IMPL_FIRST_MFMA || impl_is_fft(impl) || impl == IMPL_F16X3;
 }
 
-// number of f32 the canonical blob must hold; also validates the topology
-static long walk_count(const amt_rdcnn_desc &d, int *flat_out, std::string *err) {
-    long n = 0;
-    int flat = 0;
-    for (int t = 0; t < d.n_towers; ++t) {
-        int H = d.in_h[t], W = d.in_w[t], C = 1, fo = 32;
-        int p0H = H, p0W = W, p0C = 1;
-        for (int i = 1; i <= d.conv_layers; ++i) {
-            n += (long)d.kh[t] * d.kw[t] * C * fo + fo + 4 * fo;
-            C = fo;
-            if (d.residual_frequency > 0 && i % d.residual_frequency == 0) {
-                if (!(p0H == H && p0W == W && p0C == C)) {
-                    if (p0C != C) n += (long)p0C * C + C;
-                    n += 4 * C;
-                }
-                n += 4 * C;
-                p0H = H; p0W = W; p0C = C;
-            }
-            if (d.pool_layer_frequency > 0 && i % d.pool_layer_frequency == 0) {
-                H /= d.pool_h[t]; W /= d.pool_w[t];
-                if (H < 1 || W < 1) { if (err) *err = "pooling collapses the activation"; return -1; }
-            }
-            if (d.feature_expand_frequency > 0 && i % d.feature_expand_frequency == 0) fo *= 2;
-        }
-        flat += H * W * C;
-    }
-    n += (long)flat * d.dense_units + d.dense_units;
-    n += (long)d.dense_units * d.output_classes + d.output_classes;
-    if (flat_out) *flat_out = flat;
-    return n;
-}
-
 // ---- weight packers: Keras-layout kernel [tap][cin][cout] -> the variant's layout, on the host ----------------------
 // f32 MFMA: [slice][cchunk][tap][c][j][ntw], cout = slice*cw + 32*ntw + j
 static std::vector<float> pack_f32(const float *kern, int ntap, int C, int fo, int nslice) {
@@ -544,9 +513,8 @@ static int build_conv_variants(amt_rdcnn *n, ConvOp &c, const float *kern) {
 extern "C" {
 
 size_t amt_rdcnn_param_count(const amt_rdcnn_desc *desc) {
-    if (!desc || desc->n_towers < 1 || desc->n_towers > 2) return 0;
-    long n = walk_count(*desc, nullptr, nullptr);
-    return n < 0 ? 0 : (size_t)n;
+    RdTopology tp;
+    return desc && amt_rdcnn_topology(*desc, &tp) == AMT_OK ? tp.total : 0;
 }
 
 int amt_rdcnn_destroy(amt_rdcnn *net) {
@@ -570,77 +538,53 @@ int amt_rdcnn_create(amt_rdcnn **out, const amt_rdcnn_desc *desc, const float *w
     if (d.n_towers < 1 || d.n_towers > 2 || d.conv_layers < 1 || d.dense_units < 1 ||
         d.output_classes < 1)
         return AMT_E_INVALID;
-    int flat = 0;
-    const long need = walk_count(d, &flat, nullptr);
-    if (need < 0) return AMT_E_UNSUPPORTED;
-    if ((size_t)need != n_floats) return AMT_E_SHAPE;
+    RdTopology tp;
+    if (amt_rdcnn_topology(d, &tp) != AMT_OK) return AMT_E_UNSUPPORTED;
+    if (tp.total != n_floats) return AMT_E_SHAPE;
+    if (!tp.shortcut_ok) return AMT_E_UNSUPPORTED;
     amt_rdcnn *n = new amt_rdcnn();
     n->d = d;
-    n->flat = flat;
-    const float *cur = wh;
-    auto take = [&](size_t k) { const float *r = cur; cur += k; return r; };
+    n->flat = tp.flat;
+    n->towers.resize(d.n_towers);
+    for (int t = 0; t < d.n_towers; ++t) {
+        Tower &tw = n->towers[t];
+        tw.in_h = d.in_h[t]; tw.in_w = d.in_w[t]; tw.ph = d.pool_h[t]; tw.pw = d.pool_w[t];
+        tw.max_act = (size_t)tw.in_h * tw.in_w;
+        tw.out_h = tp.out_h[t]; tw.out_w = tp.out_w[t]; tw.out_c = tp.out_c[t];
+    }
     int rc = AMT_OK;
 #define RD_TRY(x) do { rc = (x); if (rc != AMT_OK) { amt_rdcnn_destroy(n); return rc; } } while (0)
-    for (int t = 0; t < d.n_towers; ++t) {
-        Tower tw;
-        tw.in_h = d.in_h[t]; tw.in_w = d.in_w[t]; tw.ph = d.pool_h[t]; tw.pw = d.pool_w[t];
-        int H = tw.in_h, W = tw.in_w, C = 1, fo = 32;
-        int p0H = H, p0W = W, p0C = 1;
-        tw.max_act = (size_t)H * W;
-        const int kh = d.kh[t], kw = d.kw[t];
-        for (int i = 1; i <= d.conv_layers; ++i) {
-            ConvOp c;
-            c.cin = C; c.cout = fo; c.H = H; c.W = W; c.kh = kh; c.kw = kw;
-            const float *kern = take((size_t)kh * kw * C * fo);
-            const float *bias = take(fo);
-            RD_TRY(upload_folded_bn(n, take(4 * (size_t)fo), fo, bias, &c.s1, &c.t1));
-            if (C == 1) RD_TRY(upload(n, kern, (size_t)kh * kw * fo * sizeof(float), &c.f32.w));      // [tap][cout] as is
-            else RD_TRY(build_conv_variants(n, c, kern));
-            n->flops += 2.0 * H * W * (double)kh * kw * C * fo;
-            C = fo;
-            tw.max_act = std::max(tw.max_act, (size_t)H * W * C);
-            if (d.residual_frequency > 0 && i % d.residual_frequency == 0) {
-                c.residual = true;
-                if (!(p0H == H && p0W == W && p0C == C)) {
-                    ProjOp pr;
-                    pr.cin = p0C; pr.cout = C; pr.H = p0H; pr.W = p0W;
-                    pr.ph = p0H / H; pr.pw = p0W / W;            // floor(sh1/sh2), RDCNN.py:325-326
-                    pr.HO = p0H / pr.ph; pr.WO = p0W / pr.pw;    // valid avg-pool output
-                    if (pr.HO != H || pr.WO != W) { amt_rdcnn_destroy(n); return AMT_E_UNSUPPORTED; }
-                    const float *pk = nullptr, *pb = nullptr;
-                    if (p0C != C) { pk = take((size_t)p0C * C); pb = take(C); }
-                    RD_TRY(upload_folded_bn(n, take(4 * (size_t)C), C, pb, &pr.s, &pr.t));
-                    if (pk) RD_TRY(upload(n, pk, (size_t)p0C * C * sizeof(float), &pr.w));
-                    n->flops += 2.0 * H * W * (double)p0C * C;
-                    c.sc_proj = (int)tw.projs.size();
-                    tw.projs.push_back(pr);
-                }
-                RD_TRY(upload_folded_bn(n, take(4 * (size_t)C), C, nullptr, &c.s2, &c.t2));
-                p0H = H; p0W = W; p0C = C;
-            }
-            if (d.pool_layer_frequency > 0 && i % d.pool_layer_frequency == 0) {
-                c.pool_after = 1;
-                H /= tw.ph; W /= tw.pw;
-            }
-            if (d.feature_expand_frequency > 0 && i % d.feature_expand_frequency == 0) fo *= 2;
-            tw.convs.push_back(c);
+    for (const RdLayer &l : tp.layers) {
+        Tower &tw = n->towers[l.tower];
+        ConvOp c;
+        c.cin = l.cin; c.cout = l.cout; c.H = l.H; c.W = l.W; c.kh = l.kh; c.kw = l.kw;
+        const float *kern = wh + l.kernel;
+        RD_TRY(upload_folded_bn(n, wh + l.bn, l.cout, wh + l.bias, &c.s1, &c.t1));
+        if (l.cin == 1) RD_TRY(upload(n, kern, (size_t)l.kh * l.kw * l.cout * sizeof(float), &c.f32.w));      // [tap][cout] as is
+        else RD_TRY(build_conv_variants(n, c, kern));
+        n->flops += 2.0 * l.H * l.W * (double)l.kh * l.kw * l.cin * l.cout;
+        tw.max_act = std::max(tw.max_act, (size_t)l.H * l.W * l.cout);
+        c.residual = l.residual;
+        if (l.residual && l.sc_bn) {
+            ProjOp pr;
+            pr.cin = l.sC; pr.cout = l.cout; pr.H = l.sH; pr.W = l.sW;
+            pr.ph = l.sc_ph; pr.pw = l.sc_pw; pr.HO = l.H; pr.WO = l.W;      // valid avg-pool output (shortcut_ok)
+            RD_TRY(upload_folded_bn(n, wh + l.sc_bnorm, l.cout, l.sc_proj ? wh + l.sc_bias : nullptr, &pr.s, &pr.t));
+            if (l.sc_proj) RD_TRY(upload(n, wh + l.sc_kernel, (size_t)l.sC * l.cout * sizeof(float), &pr.w));
+            n->flops += 2.0 * l.H * l.W * (double)l.sC * l.cout;
+            c.sc_proj = (int)tw.projs.size();
+            tw.projs.push_back(pr);
         }
-        tw.out_h = H; tw.out_w = W; tw.out_c = C;
-        n->towers.push_back(tw);
+        if (l.residual) RD_TRY(upload_folded_bn(n, wh + l.res_bn, l.cout, nullptr, &c.s2, &c.t2));
+        c.pool_after = l.pool_after ? 1 : 0;
+        tw.convs.push_back(c);
     }
-    {
-        const float *k1 = take((size_t)flat * d.dense_units);
-        const float *b1 = take(d.dense_units);
-        const float *k2 = take((size_t)d.dense_units * d.output_classes);
-        const float *b2 = take(d.output_classes);
-        RD_TRY(upload(n, k1, (size_t)(b1 - k1) * sizeof(float), &n->d1w));
-        RD_TRY(upload(n, b1, (size_t)(k2 - b1) * sizeof(float), &n->d1b));
-        RD_TRY(upload(n, k2, (size_t)(b2 - k2) * sizeof(float), &n->d2w));
-        RD_TRY(upload(n, b2, (size_t)(cur - b2) * sizeof(float), &n->d2b));
-        n->flops += 2.0 * flat * d.dense_units + 2.0 * d.dense_units * d.output_classes;
-    }
+    RD_TRY(upload(n, wh + tp.d1_kernel, (size_t)tp.flat * d.dense_units * sizeof(float), &n->d1w));
+    RD_TRY(upload(n, wh + tp.d1_bias, (size_t)d.dense_units * sizeof(float), &n->d1b));
+    RD_TRY(upload(n, wh + tp.d2_kernel, (size_t)d.dense_units * d.output_classes * sizeof(float), &n->d2w));
+    RD_TRY(upload(n, wh + tp.d2_bias, (size_t)d.output_classes * sizeof(float), &n->d2b));
+    n->flops += 2.0 * tp.flat * d.dense_units + 2.0 * d.dense_units * d.output_classes;
 #undef RD_TRY
-    if ((size_t)(cur - wh) != n_floats) { amt_rdcnn_destroy(n); return AMT_E_SHAPE; }
     *out = n;
     return AMT_OK;
 }

@@ -1,6 +1,6 @@
 // RDCNN training step for gfx950: forward in training mode, backward, Adagrad.
 //
-// Replaces, for the graph of /root/reference/RDCNN.py:176-233, what ``res_net.train`` /
+// Replaces, for the graph of the reference's RDCNN.py:176-233, what ``res_net.train`` /
 // ``res_net.test`` run through Keras (RDCNN.py:503-526, :559-589): ``model.train_on_batch`` /
 // ``test_on_batch`` of a model compiled with ``keras.optimizers.Adagrad()`` and
 // ``mean_squared_error`` (one output) or ``sparse_categorical_crossentropy`` (RDCNN.py:245-254).
@@ -19,14 +19,14 @@
 //   * sigmoid, shortcut add, max / average pooling and their gradients are elementwise / gather kernels;
 //   * Adagrad (a += g^2, p -= lr g / (sqrt(a) + eps); accumulators start at 0 as in Keras 2.2 / tf.keras 1.13 or
 //     at 0.1 as in tf.keras >= 1.14 -- the reference pins neither) is one elementwise kernel per tensor.
-// A small tape (list of ops over numbered tensors) is built from the topology descriptor once; a step
+// A small tape (list of ops over numbered tensors) is built from the topology (amt_rdcnn_topology.h) once; a step
 // walks it forwards, then backwards accumulating gradients per tensor (the shortcut source receives two).
 #include "amt_common.h"
 #include "amt_convh.h"
+#include "amt_rdcnn_topology.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <string>
 #include <vector>
 
 typedef float tf32x16 __attribute__((ext_vector_type(16)));
@@ -604,10 +604,6 @@ __global__ void add_kernel(const float *__restrict__ a, const float *__restrict_
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
         y[i] = a[i] + b[i];
 }
-__global__ void accumulate_kernel(float *__restrict__ dst, const float *__restrict__ src, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        dst[i] += src[i];
-}
 // pooling (valid, stride = pool); out rows may be written with a row pitch (flatten into the dense input)
 __global__ void pool_fwd_kernel(const float *__restrict__ x, int B, int H, int W, int C, int PH, int PW, int is_max,
                                 float *__restrict__ y, size_t y_stride) {
@@ -710,17 +706,53 @@ __global__ void adagrad_kernel(float *__restrict__ p, const float *__restrict__ 
 // =====================================================================================
 namespace {
 
-struct Param { float *w = nullptr, *g = nullptr, *acc = nullptr; size_t n = 0; bool trainable = true; };
+#define TR_TRY(x) do { const int rc_ = (x); if (rc_ != AMT_OK) return rc_; } while (0)
 
-enum OpKind { OP_CONV, OP_BN, OP_SIGMOID, OP_ADD, OP_POOL, OP_FLATTEN, OP_DENSE };
+// The AMT_TRAIN_* environment, read once: when a trainer (which holds one of these) is created
+bool env_is_zero(const char *name) { const char *e = getenv(name); return e && atoi(e) == 0; }
+size_t env_size(const char *name, size_t dflt) { const char *e = getenv(name); return e && atol(e) >= 0 ? (size_t)atol(e) : dflt; }
+struct TrainOptions {
+    bool fast = !env_is_zero("AMT_TRAIN_FAST");              // =0: every convolution on im2col + f32 GEMM (+ col2im)
+    bool wgrad_direct = !env_is_zero("AMT_TRAIN_WGRAD");     // =0: weight gradients through im2col + GEMM
+    bool fused_bn = !env_is_zero("AMT_TRAIN_FUSED_BN");      // =0: the generic column-reduction BatchNormalization
+    size_t fast_min_m = env_size("AMT_TRAIN_FAST_MIN_M", 2048);   // fewest output positions (B H W) for the fast forms
+    bool trace = getenv("AMT_TRAIN_TRACE") != nullptr;       // set: synchronise and report after every op
+};
+
+// Per-batch device storage: knows its capacity and frees what it replaces when it grows.  Reads as the pointer.
+struct DevBuf {
+    float *p = nullptr;
+    size_t cap = 0;                      // floats
+    operator float *() const { return p; }
+    // At least n floats; the contents do not survive growth.  hipFree synchronises the device, so no kernel of this or
+    // an earlier step still reads the block that goes and freeing needs no ordering of its own; whoever derived a
+    // pointer from p derives it again (ensure_batch: the tensors' am_slot / gam_slot; everything else is re-read from
+    // the buffer at each use).
+    int reserve(size_t n) {
+        if (p && n <= cap) return AMT_OK;
+        release();
+        if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(float)) != hipSuccess) { p = nullptr; return AMT_E_NOMEM; }
+        cap = n;
+        return AMT_OK;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr; cap = 0;
+    }
+};
+
+struct Param { float *w = nullptr, *g = nullptr, *acc = nullptr; size_t n = 0, off = 0 /* in the canonical blob */; bool trainable = true; };
+
+enum OpKind { OP_CONV /* and Dense: a 1 x 1 convolution over one position */, OP_BN, OP_SIGMOID, OP_ADD, OP_POOL, OP_FLATTEN, OP_KINDS };
 struct Op {
     OpKind kind;
     int in0 = -1, in1 = -1, out = -1;             // tensor ids
-    int H = 0, W = 0, Cin = 0, Cout = 0, kh = 1, kw = 1;    // conv / dense (H = W = 1) / pool (kh, kw = pool)
+    int H = 0, W = 0, Cin = 0, Cout = 0, kh = 1, kw = 1;    // conv / pool (kh, kw = pool)
     int is_max = 0;
-    int p0 = -1, p1 = -1, p2 = -1, p3 = -1;       // params: conv/dense (kernel, bias); bn (gamma, beta, mean, var)
+    int p0 = -1, p1 = -1, p2 = -1, p3 = -1;       // params: conv (kernel, bias); bn (gamma, beta, mean, var)
     int flat_off = 0;                              // OP_FLATTEN: column offset in the dense input
     float *bmu = nullptr, *binv = nullptr, *bvar = nullptr;      // BN batch statistics of the last forward
+    bool is_input = false;                         // OP_CONV reading a tower's input: no data gradient
     // OP_CONV on the split-fp16 kernels (amt_convh.h): forward and, when the transposed shape is covered too, the data
     // gradient; job = index of the layer's weight-preparation job (-1: the GEMM path)
     int job = -1;
@@ -738,10 +770,14 @@ struct Op {
 // ever written into the destination's own buffer, never in place into a source, so such a view stays valid).
 // am / gam: per-window max |v| / max |g| left by the producing kernel this step (null: not measured)
 struct Tensor {
-    int H, W, C; bool flat = false;
-    float *v = nullptr, *g = nullptr, *gptr = nullptr; bool g_set = false;
+    int H, W, C;
+    DevBuf v, g;
+    float *gptr = nullptr; bool g_set = false;
     float *am_slot = nullptr, *gam_slot = nullptr, *am = nullptr, *gam = nullptr;
+    size_t numel(int B) const { return (size_t)B * H * W * C; }
 };
+
+struct Step { int B; bool training; hipStream_t st; };
 
 static unsigned grid1(size_t n) { return (unsigned)std::min<size_t>((n + 255) / 256, 65535); }
 
@@ -749,32 +785,30 @@ static unsigned grid1(size_t n) { return (unsigned)std::min<size_t>((n + 255) / 
 
 struct amt_trainer {
     amt_rdcnn_desc d;
+    TrainOptions opt;
     std::vector<Param> params;                    // canonical order (rdcnn.py pack_weights)
     std::vector<Op> ops;
     std::vector<Tensor> tensors;
     std::vector<int> inputs;                      // tensor id of each tower's input
     int t_flat = -1, t_logits = -1;
     int flat = 0, capB = 0;
+    size_t blob_floats = 0;
     float lr = 0.01f, eps = 1e-7f, acc0 = 0.f;
-    float *col = nullptr, *part = nullptr, *red0 = nullptr, *red1 = nullptr, *stat0 = nullptr, *stat1 = nullptr;
-    float *pred = nullptr, *loss_rows = nullptr, *dlogits = nullptr;
-    size_t col_cap = 0, part_cap = 0;
-    std::vector<float *> allocs;
-    // split-fp16 convolutions: per-layer weight jobs (device copy), max |w| / exponent slots, per-window operand maxima
+    std::vector<float *> allocs;                  // created once, owned until destroy: arenas, packed weights, BN statistics, job tables
+    // parameters live in three arenas of one layout (weights, gradients, Adagrad accumulators): one update launch
+    float *w_arena = nullptr, *g_arena = nullptr, *a_arena = nullptr;
+    size_t arena_cap = 0, arena_used = 0;
+    // split-fp16 convolutions: per-layer weight jobs (device copy), max |w| / exponent slots
     std::vector<amt_convh_pack_job> jobs;
     amt_convh_pack_job *jobs_dev = nullptr;
     float *wmax = nullptr;
     int *sw = nullptr;
-    float *amax = nullptr;                        // [2 jobs][capB] scratch + [2 tensors][capB] producer-measured maxima
-    size_t amax_floats = 0;
     int max_job_elems = 0;
-    // parameters live in three arenas of one layout (weights, gradients, Adagrad accumulators): one update launch
-    float *w_arena = nullptr, *g_arena = nullptr, *a_arena = nullptr;
-    size_t arena_cap = 0, arena_used = 0;
-    float *red2 = nullptr;                        // column sums of dz per workgroup (bias gradient of the convolution in front)
-    size_t red_cap = 0;
-    size_t fast_min_m = 2048;                     // AMT_TRAIN_FAST_MIN_M at create: fewest output positions (B H W) for the fast forms
-    bool wgrad_direct_on = true;                  // AMT_TRAIN_WGRAD=0 at create: weight gradients through im2col + GEMM
+    // per batch size (ensure_batch) -- besides every tensor's v and g: im2col / scratch image, column partials
+    // (red2: the column sums of dz per workgroup, the bias gradient of the convolution in front), the head's outputs,
+    // and amax = [2 jobs][capB] scratch rows + [2 tensors][capB] producer-measured per-window maxima
+    DevBuf col, red0, red1, red2, amax, pred, loss_rows, dlogits;
+    DevBuf part;                                  // split-K / weight-gradient partials, grown where they are needed
     int colsum_of = -1;                           // tensor whose gradient's column partials red2 holds (-1: none)
     int colsum_nwg = 0;
 };
@@ -784,32 +818,214 @@ namespace {
 int talloc(amt_trainer *t, size_t n, float **out, bool zero = false) {
     float *p = nullptr;
     if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(float)) != hipSuccess) return AMT_E_NOMEM;
-    if (zero && hipMemset(p, 0, std::max<size_t>(n, 1) * sizeof(float)) != hipSuccess) return AMT_E_HIP;
     t->allocs.push_back(p);
+    if (zero) AMT_HIP_CHECK(hipMemset(p, 0, std::max<size_t>(n, 1) * sizeof(float)));
     *out = p;
     return AMT_OK;
 }
 
-int add_param(amt_trainer *t, const float *&cur, size_t n, bool trainable) {
-    Param p;
-    p.n = n; p.trainable = trainable;
-    const size_t off = t->arena_used;
-    if (off + n > t->arena_cap) return -1;
-    t->arena_used = (off + n + 63) & ~(size_t)63;                 // 256-byte aligned slices
-    p.w = t->w_arena + off;
-    if (hipMemcpy(p.w, cur, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return -1;
-    cur += n;
-    if (trainable) { p.g = t->g_arena + off; p.acc = t->a_arena + off; }
-    t->params.push_back(p);
-    return (int)t->params.size() - 1;
-}
-
-int new_tensor(amt_trainer *t, int H, int W, int C, bool flat = false) {
-    Tensor x; x.H = H; x.W = W; x.C = C; x.flat = flat;
+// ---- the tape, from the topology (amt_rdcnn_topology.h) ----------------------------------------------------------------
+int new_tensor(amt_trainer *t, int H, int W, int C) {
+    Tensor x; x.H = H; x.W = W; x.C = C;
     t->tensors.push_back(x);
     return (int)t->tensors.size() - 1;
 }
+// n floats at blob offset off become the next parameter: a 256-byte aligned slice of the arenas
+int add_param(amt_trainer *t, const float *wh, size_t off, size_t n, bool trainable, int *idx) {
+    Param p;
+    p.n = n; p.off = off; p.trainable = trainable;
+    const size_t at = t->arena_used;
+    if (at + n > t->arena_cap) return AMT_E_NOMEM;
+    t->arena_used = (at + n + 63) & ~(size_t)63;
+    p.w = t->w_arena + at;
+    AMT_HIP_CHECK(hipMemcpy(p.w, wh + off, n * sizeof(float), hipMemcpyHostToDevice));
+    if (trainable) { p.g = t->g_arena + at; p.acc = t->a_arena + at; }
+    t->params.push_back(p);
+    *idx = (int)t->params.size() - 1;
+    return AMT_OK;
+}
+// a convolution over H x W positions, or a Dense layer as the 1 x 1 convolution over one position: kernel, bias, output tensor
+int add_conv(amt_trainer *t, const float *wh, int in, int H, int W, int Cin, int Cout, int kh, int kw, size_t kernel_off,
+             size_t bias_off, int *out) {
+    Op o; o.kind = OP_CONV; o.in0 = in; o.H = H; o.W = W; o.Cin = Cin; o.Cout = Cout; o.kh = kh; o.kw = kw;
+    o.is_input = std::find(t->inputs.begin(), t->inputs.end(), in) != t->inputs.end();
+    TR_TRY(add_param(t, wh, kernel_off, (size_t)kh * kw * Cin * Cout, true, &o.p0));
+    TR_TRY(add_param(t, wh, bias_off, Cout, true, &o.p1));
+    *out = o.out = new_tensor(t, H, W, Cout);
+    t->ops.push_back(o);
+    return AMT_OK;
+}
+int add_bn(amt_trainer *t, const float *wh, size_t off, int in, int *out) {
+    const int H = t->tensors[in].H, W = t->tensors[in].W, C = t->tensors[in].C;
+    Op o; o.kind = OP_BN; o.in0 = in; o.Cout = C;
+    int *const idx[4] = {&o.p0, &o.p1, &o.p2, &o.p3};          // gamma, beta: trainable; moving mean, variance: not
+    for (int k = 0; k < 4; ++k) TR_TRY(add_param(t, wh, off + (size_t)k * C, C, k < 2, idx[k]));
+    TR_TRY(talloc(t, C, &o.bmu));
+    TR_TRY(talloc(t, C, &o.binv));
+    TR_TRY(talloc(t, C, &o.bvar));
+    *out = o.out = new_tensor(t, H, W, C);
+    t->ops.push_back(o);
+    return AMT_OK;
+}
+int add_sigmoid(amt_trainer *t, int in) {
+    const Tensor x = t->tensors[in];
+    Op o; o.kind = OP_SIGMOID; o.in0 = in; o.out = new_tensor(t, x.H, x.W, x.C);
+    t->ops.push_back(o);
+    return o.out;
+}
+int add_pool(amt_trainer *t, int in, int ph, int pw, int is_max) {
+    const Tensor x = t->tensors[in];
+    Op o; o.kind = OP_POOL; o.in0 = in; o.is_max = is_max; o.kh = ph; o.kw = pw; o.H = x.H; o.W = x.W; o.Cin = x.C;
+    o.out = new_tensor(t, x.H / ph, x.W / pw, x.C);
+    t->ops.push_back(o);
+    return o.out;
+}
 
+int build_tape(amt_trainer *t, const RdTopology &tp, const float *wh) {
+    const amt_rdcnn_desc &d = t->d;
+    std::vector<int> tails;
+    for (int tw = 0; tw < d.n_towers; ++tw) {
+        int cur = new_tensor(t, d.in_h[tw], d.in_w[tw], 1);
+        t->inputs.push_back(cur);
+        int src = cur;                                        // where the next shortcut starts
+        for (int i = 0; i < d.conv_layers; ++i) {
+            const RdLayer &l = tp.layers[(size_t)tw * d.conv_layers + i];
+            TR_TRY(add_conv(t, wh, cur, l.H, l.W, l.cin, l.cout, l.kh, l.kw, l.kernel, l.bias, &cur));
+            TR_TRY(add_bn(t, wh, l.bn, cur, &cur));
+            cur = add_sigmoid(t, cur);
+            if (l.residual) {
+                int a = src;
+                if (l.sc_proj) TR_TRY(add_conv(t, wh, a, l.sH, l.sW, l.sC, l.cout, 1, 1, l.sc_kernel, l.sc_bias, &a));
+                if (l.sc_pool) a = add_pool(t, a, l.sc_ph, l.sc_pw, 0);
+                if (l.sc_bn) TR_TRY(add_bn(t, wh, l.sc_bnorm, a, &a));
+                Op ad; ad.kind = OP_ADD; ad.in0 = a; ad.in1 = cur; ad.out = new_tensor(t, l.H, l.W, l.cout);
+                t->ops.push_back(ad);
+                TR_TRY(add_bn(t, wh, l.res_bn, ad.out, &cur));
+                src = cur;
+            }
+            if (l.pool_after) cur = add_pool(t, cur, l.ph, l.pw, 1);
+        }
+        tails.push_back(cur);
+    }
+    t->flat = tp.flat;
+    t->t_flat = new_tensor(t, 1, 1, tp.flat);
+    for (int tw = 0; tw < d.n_towers; ++tw) {
+        Op f; f.kind = OP_FLATTEN; f.in0 = tails[tw]; f.out = t->t_flat; f.flat_off = tp.flat_off[tw];
+        t->ops.push_back(f);
+    }
+    int h = -1;
+    TR_TRY(add_conv(t, wh, t->t_flat, 1, 1, tp.flat, d.dense_units, 1, 1, tp.d1_kernel, tp.d1_bias, &h));
+    h = add_sigmoid(t, h);
+    TR_TRY(add_conv(t, wh, h, 1, 1, d.dense_units, d.output_classes, 1, 1, tp.d2_kernel, tp.d2_bias, &t->t_logits));
+    return AMT_OK;
+}
+
+// BatchNormalizations on the fused passes, with the sigmoid behind them folded in
+void choose_fused_bn(amt_trainer *t) {
+    for (size_t i = 0; i < t->ops.size(); ++i) {
+        Op &o = t->ops[i];
+        if (!t->opt.fused_bn || o.kind != OP_BN) continue;
+        const int C = o.Cout;
+        if (C < 4 || C > 1024 || (C & (C - 1)) != 0) continue;
+        o.bn_fused = true;
+        if (i + 1 < t->ops.size() && t->ops[i + 1].kind == OP_SIGMOID && t->ops[i + 1].in0 == o.out) {
+            o.sig_out = t->ops[i + 1].out;
+            t->ops[i + 1].skip = true;
+        }
+    }
+}
+// convolutions the split-fp16 kernels cover: plans, packed-weight storage and the weight-preparation jobs
+int choose_fast_convs(amt_trainer *t) {
+    int njobs = 0;
+    for (Op &o : t->ops) {
+        if (!t->opt.fast || o.kind != OP_CONV || (o.kh == 1 && o.kw == 1)) continue;
+        if (amt_convh_plan_init(&o.fplan, o.kh, o.kw, o.Cin, o.Cout, o.H, o.W) != AMT_OK) continue;
+        o.job = njobs++;
+        o.fast_bwd = !o.is_input && amt_convh_plan_init(&o.bplan, o.kh, o.kw, o.Cout, o.Cin, o.H, o.W) == AMT_OK;
+    }
+    if (!njobs) return AMT_OK;
+    float *tmp = nullptr;
+    TR_TRY(talloc(t, njobs, &t->wmax, true));
+    TR_TRY(talloc(t, njobs, &tmp, true));
+    t->sw = reinterpret_cast<int *>(tmp);
+    t->jobs.resize(njobs);
+    for (Op &o : t->ops) {
+        if (o.job < 0) continue;
+        float *a = nullptr, *b = nullptr;
+        TR_TRY(talloc(t, (amt_convh_packed_bytes(&o.fplan) + 3) / 4, &a));
+        if (o.fast_bwd) TR_TRY(talloc(t, (amt_convh_packed_bytes(&o.bplan) + 3) / 4, &b));
+        o.wp_f = a; o.wp_b = b;
+        amt_convh_pack_job &j = t->jobs[o.job];
+        j.w = t->params[o.p0].w; j.packed_fwd = a; j.packed_bwd = b;
+        j.wmax = t->wmax + o.job; j.sw = t->sw + o.job;
+        j.ntap = o.kh * o.kw; j.Cin = o.Cin; j.Cout = o.Cout;
+        t->max_job_elems = std::max(t->max_job_elems, j.ntap * j.Cin * j.Cout);
+    }
+    float *jd = nullptr;
+    const size_t jb = (size_t)njobs * sizeof(amt_convh_pack_job);
+    TR_TRY(talloc(t, (jb + 3) / 4, &jd));
+    AMT_HIP_CHECK(hipMemcpy(jd, t->jobs.data(), jb, hipMemcpyHostToDevice));
+    t->jobs_dev = reinterpret_cast<amt_convh_pack_job *>(jd);
+    return AMT_OK;
+}
+
+int trainer_init(amt_trainer *t, const RdTopology &tp, const float *wh) {
+    const amt_rdcnn_desc &d = t->d;
+    // upper bound of the slices' padding: 8 parameters per convolution (kernel, bias, BN x 2 incl. shortcut) + the head
+    const size_t nparams = (size_t)d.n_towers * (size_t)d.conv_layers * 16 + 64;
+    t->arena_cap = tp.total + 64 * nparams;
+    TR_TRY(talloc(t, t->arena_cap, &t->w_arena, true));
+    TR_TRY(talloc(t, t->arena_cap, &t->g_arena, true));
+    TR_TRY(talloc(t, t->arena_cap, &t->a_arena, true));
+    if (t->acc0 > 0.f) {
+        std::vector<float> a0(t->arena_cap, t->acc0);
+        AMT_HIP_CHECK(hipMemcpy(t->a_arena, a0.data(), a0.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    TR_TRY(build_tape(t, tp, wh));
+    choose_fused_bn(t);
+    return choose_fast_convs(t);
+}
+
+size_t bnf_rows_wg(int C) { return (size_t)(1024 / C) * BNF_RPT; }
+int bnf_nwg(size_t M, int C) { return (int)((M + bnf_rows_wg(C) - 1) / bnf_rows_wg(C)); }
+
+// storage for B windows: every per-batch buffer grows (and frees what it held) when a larger batch arrives
+int ensure_batch(amt_trainer *t, int B) {
+    if (B <= t->capB) return AMT_OK;
+    t->capB = 0;                                  // a regrowth that fails half-way leaves no batch size valid
+    size_t col_need = 0, red_need = 0;
+    int maxC = 1;
+    for (Tensor &x : t->tensors) {
+        TR_TRY(x.v.reserve(x.numel(B)));
+        TR_TRY(x.g.reserve(x.numel(B)));
+        col_need = std::max(col_need, x.numel(B));
+    }
+    for (const Op &o : t->ops) {
+        if (o.kind == OP_CONV) col_need = std::max(col_need, (size_t)B * o.H * o.W * o.kh * o.kw * o.Cin);
+        if (o.kind == OP_CONV || o.kind == OP_BN) maxC = std::max(maxC, o.Cout);     // column sums over Cout
+        if (o.kind == OP_BN) {
+            if (o.bn_fused) red_need = std::max(red_need, (size_t)bnf_nwg(t->tensors[o.in0].numel(B) / o.Cout, o.Cout) * o.Cout);
+        }
+    }
+    red_need = std::max(red_need, (size_t)CR_SPLIT * maxC);
+    TR_TRY(t->col.reserve(col_need));
+    TR_TRY(t->red0.reserve(red_need));
+    TR_TRY(t->red1.reserve(red_need));
+    TR_TRY(t->red2.reserve(red_need));
+    // per-window maxima: two scratch rows per split-fp16 layer (operands no producer measured) + two per tensor.  The
+    // tensors' rows are the only pointers kept INTO a per-batch buffer: derived here, after every growth
+    TR_TRY(t->amax.reserve((2 * t->jobs.size() + 2 * t->tensors.size()) * (size_t)B));
+    float *base = t->amax + 2 * t->jobs.size() * (size_t)B;
+    for (Tensor &x : t->tensors) { x.am_slot = base; x.gam_slot = base + B; base += 2 * (size_t)B; }
+    const int K = t->d.output_classes;
+    TR_TRY(t->pred.reserve((size_t)B * K));
+    TR_TRY(t->loss_rows.reserve(B));
+    TR_TRY(t->dlogits.reserve((size_t)B * K));
+    t->capB = B;
+    return AMT_OK;
+}
+
+// ---- shared launches ----------------------------------------------------------------------------------------------------
 // GEMM dispatch with split over the contraction when the output grid is small
 int gemm(amt_trainer *t, bool TA, bool TB, const float *A, int lda, const float *B, int ldb, float *C, int ldc,
          int M, int N, int K, const float *bias, hipStream_t st) {
@@ -824,22 +1040,14 @@ int gemm(amt_trainer *t, bool TA, bool TB, const float *A, int lda, const float 
     Z = (K + kslice - 1) / kslice;
     float *part = nullptr;
     if (Z > 1) {
-        const size_t need = (size_t)Z * M * N;
-        if (need > t->part_cap) {
-            if (talloc(t, need, &t->part) != AMT_OK) return AMT_E_NOMEM;
-            t->part_cap = need;
-        }
+        TR_TRY(t->part.reserve((size_t)Z * M * N));
         part = t->part;
     }
-    dim3 grid(gx, gy, Z);
-#define TG_LAUNCH(ta, tb)                                                                                       \
-    do {                                                                                                        \
-        if (wn == 1) tgemm_kernel<ta, tb, 1><<<grid, 256, 0, st>>>(A, lda, B, ldb, C, ldc, M, N, K, kslice, bias, part); \
-        else tgemm_kernel<ta, tb, 2><<<grid, 256, 0, st>>>(A, lda, B, ldb, C, ldc, M, N, K, kslice, bias, part);  \
-    } while (0)
     if (TA && TB) return AMT_E_UNSUPPORTED;
-    if (TA) TG_LAUNCH(true, false); else if (TB) TG_LAUNCH(false, true); else TG_LAUNCH(false, false);
-#undef TG_LAUNCH
+    auto kern = TA ? (wn == 1 ? tgemm_kernel<true, false, 1> : tgemm_kernel<true, false, 2>)
+              : TB ? (wn == 1 ? tgemm_kernel<false, true, 1> : tgemm_kernel<false, true, 2>)
+                   : (wn == 1 ? tgemm_kernel<false, false, 1> : tgemm_kernel<false, false, 2>);
+    kern<<<dim3(gx, gy, Z), 256, 0, st>>>(A, lda, B, ldb, C, ldc, M, N, K, kslice, bias, part);
     if (Z > 1) splitk_reduce_kernel<<<grid1((size_t)M * N), 256, 0, st>>>(part, Z, C, ldc, M, N, bias);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
@@ -867,11 +1075,8 @@ int wgrad_direct(amt_trainer *t, const Op &o, const float *x, const float *dz, f
     a.ntiles = B * o.H * a.nseg;
     const int ngroups = o.kh * (o.Cin / 32) * (o.Cout / 32);
     const int P = std::max(1, std::min(a.ntiles, 512 / ngroups));
-    const size_t nW = (size_t)o.kh * o.kw * o.Cin * o.Cout, need = (size_t)P * nW;
-    if (need > t->part_cap) {
-        if (talloc(t, need, &t->part) != AMT_OK) return AMT_E_NOMEM;
-        t->part_cap = need;
-    }
+    const size_t nW = (size_t)o.kh * o.kw * o.Cin * o.Cout;
+    TR_TRY(t->part.reserve((size_t)P * nW));
     a.part = t->part;
     const size_t lds = (size_t)(2 * a.seg + 15) * 32 * sizeof(float);
     wgrad_kernel<16><<<dim3(P, ngroups), 256, lds, st>>>(a);
@@ -880,278 +1085,58 @@ int wgrad_direct(amt_trainer *t, const Op &o, const float *x, const float *dz, f
     return AMT_OK;
 }
 
-}  // namespace
+// layers too small to fill the chip stay on the GEMM path (a handful of workgroups walking the whole contraction one
+// after the other is slower than the split-K GEMM)
+bool fast_now(const amt_trainer *t, const Op &o, int B) { return o.job >= 0 && (size_t)B * o.H * o.W >= t->opt.fast_min_m; }
 
-extern "C" {
-
-int amt_trainer_destroy(amt_trainer *t) {
-    if (!t) return AMT_OK;
-    for (float *p : t->allocs) (void)hipFree(p);
-    delete t;
-    return AMT_OK;
+// the convolution's input as the GEMM's row operand: the activation itself (1 x 1) or its im2col image in col
+const float *conv_rows(amt_trainer *t, const Op &o, const float *x, int B, hipStream_t st) {
+    if (o.kh == 1 && o.kw == 1) return x;
+    const size_t M = (size_t)B * o.H * o.W;
+    im2col_kernel<<<(unsigned)std::min<size_t>(M, 1u << 20), 256, 0, st>>>(x, (size_t)o.H * o.W * o.Cin, B, o.H, o.W, o.Cin, o.kh, o.kw, t->col);
+    return t->col;
 }
-
-int amt_trainer_create(amt_trainer **out, const amt_rdcnn_desc *desc, const float *wh, size_t n_floats, float lr,
-                       float epsilon, float initial_accumulator) {
-    if (!out || !desc || !wh) return AMT_E_INVALID;
-    if ((size_t)amt_rdcnn_param_count(desc) != n_floats || n_floats == 0) return AMT_E_SHAPE;
-    const amt_rdcnn_desc &d = *desc;
-    amt_trainer *t = new amt_trainer();
-    t->d = d;
-    if (lr > 0.f) t->lr = lr;
-    if (epsilon > 0.f) t->eps = epsilon;
-    t->acc0 = initial_accumulator > 0.f ? initial_accumulator : 0.f;
-    {
-        // upper bound of the slices' padding: 8 parameters per convolution (kernel, bias, BN x 2 incl. shortcut) + the head
-        const size_t nparams = (size_t)d.n_towers * (size_t)d.conv_layers * 16 + 64;
-        t->arena_cap = n_floats + 64 * nparams;
-        if (talloc(t, t->arena_cap, &t->w_arena, true) != AMT_OK || talloc(t, t->arena_cap, &t->g_arena, true) != AMT_OK ||
-            talloc(t, t->arena_cap, &t->a_arena, true) != AMT_OK) {
-            amt_trainer_destroy(t); return AMT_E_NOMEM;
-        }
-        if (t->acc0 > 0.f) {
-            std::vector<float> a0(t->arena_cap, t->acc0);
-            if (hipMemcpy(t->a_arena, a0.data(), a0.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-                amt_trainer_destroy(t); return AMT_E_HIP;
-            }
-        }
-    }
-    const float *cur = wh;
-#define TR_P(n, tr) add_param(t, cur, (size_t)(n), tr)
-#define TR_FAIL() do { amt_trainer_destroy(t); return AMT_E_NOMEM; } while (0)
-    auto bn_op = [&](int in, int C) -> int {
-        Op o; o.kind = OP_BN; o.in0 = in; o.Cout = C;
-        o.p0 = TR_P(C, true); o.p1 = TR_P(C, true); o.p2 = TR_P(C, false); o.p3 = TR_P(C, false);
-        if (o.p0 < 0 || o.p1 < 0 || o.p2 < 0 || o.p3 < 0) return -1;
-        const Tensor &x = t->tensors[in];
-        o.out = new_tensor(t, x.H, x.W, C);
-        if (talloc(t, C, &o.bmu) != AMT_OK || talloc(t, C, &o.binv) != AMT_OK || talloc(t, C, &o.bvar) != AMT_OK) return -1;
-        t->ops.push_back(o);
-        return o.out;
-    };
-    std::vector<std::pair<int, int>> tails;               // (tensor, flat offset)
-    int flat = 0;
-    for (int tw = 0; tw < d.n_towers; ++tw) {
-        int H = d.in_h[tw], W = d.in_w[tw], C = 1, fo = 32;
-        int cur_t = new_tensor(t, H, W, 1);
-        t->inputs.push_back(cur_t);
-        int p0 = cur_t;
-        for (int i = 1; i <= d.conv_layers; ++i) {
-            Op c; c.kind = OP_CONV; c.in0 = cur_t; c.H = H; c.W = W; c.Cin = C; c.Cout = fo; c.kh = d.kh[tw]; c.kw = d.kw[tw];
-            c.p0 = TR_P((size_t)c.kh * c.kw * C * fo, true); c.p1 = TR_P(fo, true);
-            if (c.p0 < 0 || c.p1 < 0) TR_FAIL();
-            c.out = new_tensor(t, H, W, fo);
-            t->ops.push_back(c);
-            int z = bn_op(c.out, fo);
-            if (z < 0) TR_FAIL();
-            Op s; s.kind = OP_SIGMOID; s.in0 = z; s.out = new_tensor(t, H, W, fo);
-            t->ops.push_back(s);
-            cur_t = s.out; C = fo;
-            if (d.residual_frequency > 0 && i % d.residual_frequency == 0) {
-                int a = p0;
-                const Tensor src = t->tensors[p0];
-                if (!(src.H == H && src.W == W && src.C == C)) {
-                    if (src.C != C) {
-                        Op pc; pc.kind = OP_CONV; pc.in0 = a; pc.H = src.H; pc.W = src.W; pc.Cin = src.C; pc.Cout = C; pc.kh = 1; pc.kw = 1;
-                        pc.p0 = TR_P((size_t)src.C * C, true); pc.p1 = TR_P(C, true);
-                        if (pc.p0 < 0 || pc.p1 < 0) TR_FAIL();
-                        pc.out = new_tensor(t, src.H, src.W, C);
-                        t->ops.push_back(pc);
-                        a = pc.out;
-                    }
-                    if (src.H != H || src.W != W) {
-                        Op ap; ap.kind = OP_POOL; ap.in0 = a; ap.is_max = 0; ap.kh = src.H / H; ap.kw = src.W / W;
-                        ap.H = src.H; ap.W = src.W; ap.Cin = C;
-                        if (src.H / ap.kh != H || src.W / ap.kw != W) { amt_trainer_destroy(t); return AMT_E_UNSUPPORTED; }
-                        ap.out = new_tensor(t, H, W, C);
-                        t->ops.push_back(ap);
-                        a = ap.out;
-                    }
-                    a = bn_op(a, C);
-                    if (a < 0) TR_FAIL();
-                }
-                Op ad; ad.kind = OP_ADD; ad.in0 = a; ad.in1 = cur_t; ad.out = new_tensor(t, H, W, C);
-                t->ops.push_back(ad);
-                cur_t = bn_op(ad.out, C);
-                if (cur_t < 0) TR_FAIL();
-                p0 = cur_t;
-            }
-            if (d.pool_layer_frequency > 0 && i % d.pool_layer_frequency == 0) {
-                Op mp; mp.kind = OP_POOL; mp.in0 = cur_t; mp.is_max = 1; mp.kh = d.pool_h[tw]; mp.kw = d.pool_w[tw];
-                mp.H = H; mp.W = W; mp.Cin = C;
-                H /= mp.kh; W /= mp.kw;
-                if (H < 1 || W < 1) { amt_trainer_destroy(t); return AMT_E_UNSUPPORTED; }
-                mp.out = new_tensor(t, H, W, C);
-                t->ops.push_back(mp);
-                cur_t = mp.out;
-            }
-            if (d.feature_expand_frequency > 0 && i % d.feature_expand_frequency == 0) fo *= 2;
-        }
-        tails.push_back({cur_t, flat});
-        flat += H * W * C;
-    }
-    t->flat = flat;
-    t->t_flat = new_tensor(t, 1, 1, flat, true);
-    for (auto &tl : tails) {
-        Op f; f.kind = OP_FLATTEN; f.in0 = tl.first; f.out = t->t_flat; f.flat_off = tl.second;
-        t->ops.push_back(f);
-    }
-    {
-        Op d1; d1.kind = OP_DENSE; d1.in0 = t->t_flat; d1.Cin = flat; d1.Cout = d.dense_units;
-        d1.p0 = TR_P((size_t)flat * d.dense_units, true); d1.p1 = TR_P(d.dense_units, true);
-        if (d1.p0 < 0 || d1.p1 < 0) TR_FAIL();
-        d1.out = new_tensor(t, 1, 1, d.dense_units, true);
-        t->ops.push_back(d1);
-        Op s; s.kind = OP_SIGMOID; s.in0 = d1.out; s.out = new_tensor(t, 1, 1, d.dense_units, true);
-        t->ops.push_back(s);
-        Op d2; d2.kind = OP_DENSE; d2.in0 = s.out; d2.Cin = d.dense_units; d2.Cout = d.output_classes;
-        d2.p0 = TR_P((size_t)d.dense_units * d.output_classes, true); d2.p1 = TR_P(d.output_classes, true);
-        if (d2.p0 < 0 || d2.p1 < 0) TR_FAIL();
-        d2.out = new_tensor(t, 1, 1, d.output_classes, true);
-        t->ops.push_back(d2);
-        t->t_logits = d2.out;
-    }
-#undef TR_P
-#undef TR_FAIL
-    if ((size_t)(cur - wh) != n_floats) { amt_trainer_destroy(t); return AMT_E_SHAPE; }
-    {
-        const char *e = getenv("AMT_TRAIN_WGRAD");
-        t->wgrad_direct_on = !(e && atoi(e) == 0);
-        const char *m = getenv("AMT_TRAIN_FAST_MIN_M");
-        if (m && atol(m) >= 0) t->fast_min_m = (size_t)atol(m);
-    }
-    // BatchNormalizations on the fused passes, with the sigmoid behind them folded in (AMT_TRAIN_FUSED_BN=0: the generic
-    // column-reduction kernels)
-    {
-        const char *e = getenv("AMT_TRAIN_FUSED_BN");
-        const bool want = !(e && atoi(e) == 0);
-        for (size_t i = 0; i < t->ops.size(); ++i) {
-            Op &o = t->ops[i];
-            if (!want || o.kind != OP_BN) continue;
-            const int C = o.Cout;
-            if (C < 4 || C > 1024 || (C & (C - 1)) != 0) continue;
-            o.bn_fused = true;
-            if (i + 1 < t->ops.size() && t->ops[i + 1].kind == OP_SIGMOID && t->ops[i + 1].in0 == o.out) {
-                o.sig_out = t->ops[i + 1].out;
-                t->ops[i + 1].skip = true;
-            }
-        }
-    }
-    // convolutions the split-fp16 kernels cover (AMT_TRAIN_FAST=0: keep every layer on the f32 GEMM path)
-    {
-        const char *e = getenv("AMT_TRAIN_FAST");
-        const bool want = !(e && atoi(e) == 0);
-        int njobs = 0;
-        for (Op &o : t->ops) {
-            if (!want || o.kind != OP_CONV || (o.kh == 1 && o.kw == 1)) continue;
-            if (amt_convh_plan_init(&o.fplan, o.kh, o.kw, o.Cin, o.Cout, o.H, o.W) != AMT_OK) continue;
-            o.job = njobs++;
-            const bool is_input = std::find(t->inputs.begin(), t->inputs.end(), o.in0) != t->inputs.end();
-            o.fast_bwd = !is_input && amt_convh_plan_init(&o.bplan, o.kh, o.kw, o.Cout, o.Cin, o.H, o.W) == AMT_OK;
-        }
-        if (njobs) {
-            float *tmp = nullptr;
-            if (talloc(t, njobs, &t->wmax, true) != AMT_OK || talloc(t, njobs, &tmp, true) != AMT_OK) {
-                amt_trainer_destroy(t); return AMT_E_NOMEM;
-            }
-            t->sw = reinterpret_cast<int *>(tmp);
-            t->jobs.resize(njobs);
-            for (Op &o : t->ops) {
-                if (o.job < 0) continue;
-                float *a = nullptr, *b = nullptr;
-                if (talloc(t, (amt_convh_packed_bytes(&o.fplan) + 3) / 4, &a) != AMT_OK ||
-                    (o.fast_bwd && talloc(t, (amt_convh_packed_bytes(&o.bplan) + 3) / 4, &b) != AMT_OK)) {
-                    amt_trainer_destroy(t); return AMT_E_NOMEM;
-                }
-                o.wp_f = a; o.wp_b = b;
-                amt_convh_pack_job &j = t->jobs[o.job];
-                j.w = t->params[o.p0].w; j.packed_fwd = a; j.packed_bwd = b;
-                j.wmax = t->wmax + o.job; j.sw = t->sw + o.job;
-                j.ntap = o.kh * o.kw; j.Cin = o.Cin; j.Cout = o.Cout;
-                t->max_job_elems = std::max(t->max_job_elems, j.ntap * j.Cin * j.Cout);
-            }
-            float *jd = nullptr;
-            const size_t jb = (size_t)njobs * sizeof(amt_convh_pack_job);
-            if (talloc(t, (jb + 3) / 4, &jd) != AMT_OK ||
-                hipMemcpy(jd, t->jobs.data(), jb, hipMemcpyHostToDevice) != hipSuccess) {
-                amt_trainer_destroy(t); return AMT_E_NOMEM;
-            }
-            t->jobs_dev = reinterpret_cast<amt_convh_pack_job *>(jd);
-        }
-    }
-    int maxC = 1;
-    for (const Tensor &x : t->tensors) maxC = std::max(maxC, x.C);
-    if (talloc(t, maxC, &t->stat0) != AMT_OK || talloc(t, maxC, &t->stat1) != AMT_OK) {
-        amt_trainer_destroy(t); return AMT_E_NOMEM;
-    }
-    *out = t;
-    return AMT_OK;
-}
-
-static size_t bnf_rows_wg(int C) { return (size_t)(1024 / C) * BNF_RPT; }
-static int bnf_nwg(size_t M, int C) { return (int)((M + bnf_rows_wg(C) - 1) / bnf_rows_wg(C)); }
-
-static int ensure_batch(amt_trainer *t, int B) {
-    if (B <= t->capB) return AMT_OK;
-    // (re)allocate activations and gradients for B windows; earlier, smaller buffers stay owned until destroy
-    size_t col_need = 0;
-    for (Tensor &x : t->tensors) {
-        const size_t n = (size_t)B * x.H * x.W * x.C;
-        if (talloc(t, n, &x.v) != AMT_OK || talloc(t, n, &x.g) != AMT_OK) return AMT_E_NOMEM;
-    }
-    int maxC = 1;
-    size_t red_need = 0;
-    for (const Op &o : t->ops) {
-        if (o.kind == OP_CONV) col_need = std::max(col_need, (size_t)B * o.H * o.W * o.kh * o.kw * o.Cin);
-        if (o.kind == OP_BN) {
-            const Tensor &in = t->tensors[o.in0];
-            maxC = std::max(maxC, o.Cout);
-            if (o.bn_fused) red_need = std::max(red_need, (size_t)bnf_nwg((size_t)B * in.H * in.W, o.Cout) * o.Cout);
-        }
-        if (o.kind == OP_DENSE) { maxC = std::max(maxC, o.Cout); col_need = std::max(col_need, (size_t)B * o.Cin); }
-    }
-    for (const Tensor &x : t->tensors) col_need = std::max(col_need, (size_t)B * x.H * x.W * x.C);
-    red_need = std::max(red_need, (size_t)CR_SPLIT * maxC);
-    if (talloc(t, col_need, &t->col) != AMT_OK) return AMT_E_NOMEM;
-    t->col_cap = col_need;
-    if (talloc(t, red_need, &t->red0) != AMT_OK || talloc(t, red_need, &t->red1) != AMT_OK ||
-        talloc(t, red_need, &t->red2) != AMT_OK)
-        return AMT_E_NOMEM;
-    t->red_cap = red_need;
-    // per-window maxima: two scratch rows per split-fp16 layer (operands no producer measured) + two per tensor
-    t->amax_floats = (2 * t->jobs.size() + 2 * t->tensors.size()) * (size_t)B;
-    if (talloc(t, t->amax_floats, &t->amax) != AMT_OK) return AMT_E_NOMEM;
-    {
-        float *base = t->amax + 2 * t->jobs.size() * (size_t)B;
-        for (Tensor &x : t->tensors) { x.am_slot = base; x.gam_slot = base + B; base += 2 * (size_t)B; }
-    }
-    const int K = t->d.output_classes;
-    if (talloc(t, (size_t)B * K, &t->pred) != AMT_OK || talloc(t, B, &t->loss_rows) != AMT_OK ||
-        talloc(t, (size_t)B * K, &t->dlogits) != AMT_OK)
-        return AMT_E_NOMEM;
-    t->capB = B;
-    return AMT_OK;
+// per-window max |x| of a split-fp16 operand: what its producer measured, or one pass into scratch row `row` of amax
+int operand_amax(amt_trainer *t, const float *measured, const float *x, size_t n, int B, int row, hipStream_t st, const float **am) {
+    *am = measured;
+    if (measured) return AMT_OK;
+    float *scratch = t->amax + (size_t)row * B;
+    *am = scratch;
+    return amt_convh_absmax(x, n, B, scratch, st);
 }
 
 // ---- gradient hand-over ------------------------------------------------------------------------------------------------
 // A kernel that can write "value (+ what is there)" asks claim() for the destination's own buffer and the addend (null on
 // the first arrival); afterwards the tensor's gradient lives in its own buffer.
-static float *claim(amt_trainer *t, int id, const float **acc) {
+float *claim(amt_trainer *t, int id, const float **acc) {
     Tensor &x = t->tensors[id];
     *acc = x.g_set ? x.gptr : nullptr;
     x.gptr = x.g; x.g_set = true; x.gam = nullptr;
     return x.g;
 }
+// A kernel that can only write: launch(dst) runs it into the destination's own buffer on the first arrival, into col
+// followed by an add on a later one
+template <class F>
+int write_or_add(amt_trainer *t, int id, size_t n, hipStream_t st, F launch) {
+    const float *acc = nullptr;
+    float *dst = claim(t, id, &acc);
+    if (!acc) { launch(dst); return AMT_OK; }
+    if (n > t->col.cap) return AMT_E_NOMEM;
+    launch(t->col);
+    add_kernel<<<grid1(n), 256, 0, st>>>(acc, t->col, n, dst);
+    return AMT_OK;
+}
 // the gradient of tensor `id` is (also) the n floats at src: a view on the first arrival, a sum into the own buffer after
-static int give_view(amt_trainer *t, int id, const float *src, size_t n, hipStream_t st) {
+int give_view(amt_trainer *t, int id, const float *src, size_t n, hipStream_t st) {
     Tensor &x = t->tensors[id];
     if (!x.g_set) { x.gptr = const_cast<float *>(src); x.g_set = true; x.gam = nullptr; return AMT_OK; }
     add_kernel<<<grid1(n), 256, 0, st>>>(x.gptr, src, n, x.g);
     x.gptr = x.g; x.gam = nullptr;
     return AMT_OK;
 }
-// src is a scratch buffer that will be reused: copy (first arrival) or add into the own buffer
-static int give_copy(amt_trainer *t, int id, const float *src, size_t n, hipStream_t st) {
+// src is a scratch buffer that will be reused (copy on the first arrival, add into the own buffer after), or the own
+// buffer itself, already written (first arrival only)
+int give_copy(amt_trainer *t, int id, const float *src, size_t n, hipStream_t st) {
     Tensor &x = t->tensors[id];
     if (!x.g_set) {
         if (x.g != src) AMT_HIP_CHECK(hipMemcpyAsync(x.g, src, n * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -1162,324 +1147,286 @@ static int give_copy(amt_trainer *t, int id, const float *src, size_t n, hipStre
     return AMT_OK;
 }
 
+// ---- the ops: one forward and one backward per kind; gout = the gradient arriving at the op's output -------------------
+int fwd_conv(amt_trainer *t, Op &o, const Step &s) {
+    Tensor &in = t->tensors[o.in0], &out = t->tensors[o.out];
+    const float *bias = t->params[o.p1].w;
+    if (fast_now(t, o, s.B)) {
+        const float *am = nullptr;
+        TR_TRY(operand_amax(t, in.am, in.v, in.numel(1), s.B, 2 * o.job, s.st, &am));
+        return amt_convh_run(&o.fplan, in.v, out.v, nullptr, s.B, o.wp_f, t->sw + o.job, bias, am, (o.kh - 1) / 2, (o.kw - 1) / 2, s.st);
+    }
+    const int M = s.B * o.H * o.W, Kc = o.kh * o.kw * o.Cin;
+    return gemm(t, false, false, conv_rows(t, o, in.v, s.B, s.st), Kc, t->params[o.p0].w, o.Cout, out.v, o.Cout, M, o.Cout, Kc, bias, s.st);
+}
+int bwd_conv(amt_trainer *t, Op &o, const Step &s, const float *gout) {
+    Tensor &in = t->tensors[o.in0], &out = t->tensors[o.out];
+    const size_t M = (size_t)s.B * o.H * o.W, nin = in.numel(s.B);
+    const int Kc = o.kh * o.kw * o.Cin;
+    float *dW = t->params[o.p0].g, *db = t->params[o.p1].g;
+    if (t->opt.wgrad_direct && wgrad_direct_ok(o) && M >= t->opt.fast_min_m) TR_TRY(wgrad_direct(t, o, in.v, gout, dW, s.B, s.st));
+    else TR_TRY(gemm(t, true, false, conv_rows(t, o, in.v, s.B, s.st), Kc, gout, o.Cout, dW, o.Cout, Kc, o.Cout, (int)M, nullptr, s.st));
+    // bias gradient: the column sums of dz -- per-workgroup partials are there when the BatchNormalization behind this
+    // convolution just wrote dz
+    if (t->colsum_of == o.out) {
+        colreduce_final_kernel<<<(o.Cout + 31) / 32, 256, 0, s.st>>>(t->red2, t->red2, o.Cout, 1.0f / (float)M, 3, t->colsum_nwg, db, nullptr);
+        t->colsum_of = -1;
+    } else {
+        TR_TRY(colreduce(t, gout, nullptr, nullptr, nullptr, M, o.Cout, 3, db, nullptr, s.st));
+    }
+    if (o.is_input) return AMT_OK;                              // no gradient wrt the network input
+    if (o.fast_bwd && fast_now(t, o, s.B)) {
+        // dX = correlation of dOut with the flipped, transposed kernel (mirror-image padding), written into the input's
+        // gradient buffer, plus what the shortcut branch already handed to that tensor
+        const float *am = nullptr, *acc = nullptr;
+        TR_TRY(operand_amax(t, out.gam, gout, out.numel(1), s.B, 2 * o.job + 1, s.st, &am));
+        float *dst = claim(t, o.in0, &acc);
+        return amt_convh_run(&o.bplan, gout, dst, acc, s.B, o.wp_b, t->sw + o.job, nullptr, am, o.kh - 1 - (o.kh - 1) / 2,
+                             o.kw - 1 - (o.kw - 1) / 2, s.st);
+    }
+    // dcol = dOut W^T (into col); a 1 x 1 kernel's (a Dense layer's) dcol is dX itself, any other is gathered back to the image
+    TR_TRY(gemm(t, false, true, gout, o.Cout, t->params[o.p0].w, o.Cout, t->col, Kc, (int)M, Kc, o.Cout, nullptr, s.st));
+    if (o.kh == 1 && o.kw == 1) return give_copy(t, o.in0, t->col, nin, s.st);
+    // gathered into the input's own gradient buffer on the first arrival; on a later one into dOut's own buffer, dead
+    // once both GEMMs above have read it, and added from there
+    float *img = in.g;
+    if (in.g_set) {
+        if (gout != out.g || out.numel(s.B) < nin) return AMT_E_NOMEM;
+        img = out.g;
+    }
+    col2im_kernel<<<(unsigned)std::min<size_t>(M, 1u << 20), 256, 0, s.st>>>(t->col, s.B, o.H, o.W, o.Cin, o.kh, o.kw, img);
+    return give_copy(t, o.in0, img, nin, s.st);
+}
+
+// statistics the BatchNormalization normalises with, into o.bmu / o.binv: of the batch when training (o.bvar too; the
+// moving statistics absorb them), the moving ones otherwise -- for the fused and the generic apply alike
+int bn_statistics(amt_trainer *t, Op &o, const float *x, size_t M, const Step &s) {
+    float *mov_mean = t->params[o.p2].w, *mov_var = t->params[o.p3].w;
+    if (!s.training) {
+        AMT_HIP_CHECK(hipMemcpyAsync(o.bmu, mov_mean, o.Cout * sizeof(float), hipMemcpyDeviceToDevice, s.st));
+        inv_from_var_kernel<<<(o.Cout + 63) / 64, 64, 0, s.st>>>(mov_var, o.Cout, o.binv);
+        return AMT_OK;
+    }
+    const float bessel = M > 1 ? (float)((double)M / ((double)M - 1.0)) : 1.0f;
+    if (o.bn_fused) {
+        const int nwg = bnf_nwg(M, o.Cout);
+        bnf_stats_kernel<<<nwg, 256, 0, s.st>>>(x, M, o.Cout, t->red0, t->red1);
+        bnf_stats_final_kernel<<<(o.Cout + 31) / 32, 256, 0, s.st>>>(t->red0, t->red1, M, o.Cout, (int)bnf_rows_wg(o.Cout), nwg, o.bmu,
+                                                                     o.bvar, o.binv, mov_mean, mov_var, 1, bessel);
+        return AMT_OK;
+    }
+    TR_TRY(colreduce(t, x, nullptr, nullptr, nullptr, M, o.Cout, 0, o.bmu, nullptr, s.st));
+    TR_TRY(colreduce(t, x, nullptr, o.bmu, nullptr, M, o.Cout, 1, o.bvar, o.binv, s.st));
+    moving_update_kernel<<<(o.Cout + 63) / 64, 64, 0, s.st>>>(mov_mean, mov_var, o.bmu, o.bvar, o.Cout, bessel);
+    return AMT_OK;
+}
+int fwd_bn(amt_trainer *t, Op &o, const Step &s) {
+    Tensor &in = t->tensors[o.in0];
+    const size_t nin = in.numel(s.B), M = nin / o.Cout;
+    const float *gamma = t->params[o.p0].w, *beta = t->params[o.p1].w;
+    TR_TRY(bn_statistics(t, o, in.v, M, s));
+    if (o.bn_fused) {
+        Tensor &dst = t->tensors[o.sig_out >= 0 ? o.sig_out : o.out];
+        bnf_act_kernel<<<bnf_nwg(M, o.Cout), 256, 0, s.st>>>(in.v, o.bmu, o.binv, gamma, beta, M, o.Cout, in.H * in.W,
+                                                             o.sig_out >= 0 ? 1 : 0, dst.v, dst.am_slot);
+        dst.am = dst.am_slot;
+    } else {
+        bn_apply_kernel<<<grid1(nin), 256, 0, s.st>>>(in.v, o.bmu, o.binv, gamma, beta, nin, o.Cout, t->tensors[o.out].v);
+    }
+    return AMT_OK;
+}
+int bwd_bn(amt_trainer *t, Op &o, const Step &s, const float *gout) {
+    Tensor &in = t->tensors[o.in0];
+    const size_t nin = in.numel(s.B), M = nin / o.Cout;
+    const float *gamma = t->params[o.p0].w;
+    float *dgamma = t->params[o.p0].g, *dbeta = t->params[o.p1].g;
+    if (o.bn_fused) {
+        // dgamma = sum dy zhat, dbeta = sum dy, with dy = dA a (1 - a) when the sigmoid is folded in
+        const int nwg = bnf_nwg(M, o.Cout);
+        const float *a = o.sig_out >= 0 ? t->tensors[o.sig_out].v.p : nullptr;
+        bnf_bwd_reduce_kernel<<<nwg, 256, 0, s.st>>>(gout, a, in.v, o.bmu, o.binv, M, o.Cout, t->red0, t->red1);
+        colreduce_final_kernel<<<(o.Cout + 31) / 32, 256, 0, s.st>>>(t->red0, t->red1, o.Cout, 1.0f / (float)M, 2, nwg, dbeta, dgamma);
+        const float *acc = nullptr;
+        float *dst = claim(t, o.in0, &acc);
+        bnf_bwd_apply_kernel<<<nwg, 256, 0, s.st>>>(gout, a, in.v, o.bmu, o.binv, gamma, dbeta, dgamma, 1.0f / (float)M, M, o.Cout,
+                                                    in.H * in.W, acc, dst, t->red2, in.gam_slot);
+        // red2 now holds THIS launch's column partials: valid as the bias gradient of the convolution in front only when
+        // dz was written, not accumulated; any partials another convolution was still waiting for are gone either way
+        if (!acc) { in.gam = in.gam_slot; t->colsum_of = o.in0; t->colsum_nwg = nwg; }
+        else t->colsum_of = -1;
+        return AMT_OK;
+    }
+    // generic path: dy -> scratch, two column sums, dz
+    if (nin > t->col.cap) return AMT_E_NOMEM;
+    AMT_HIP_CHECK(hipMemcpyAsync(t->col, gout, nin * sizeof(float), hipMemcpyDeviceToDevice, s.st));
+    TR_TRY(colreduce(t, t->col, in.v, o.bmu, o.binv, M, o.Cout, 2, dbeta, dgamma, s.st));
+    bn_backward_kernel<<<grid1(nin), 256, 0, s.st>>>(t->col, in.v, o.bmu, o.binv, gamma, dbeta, dgamma, 1.0f / (float)M, nin, o.Cout, 1, t->col);
+    return give_copy(t, o.in0, t->col, nin, s.st);
+}
+
+int fwd_sigmoid(amt_trainer *t, Op &o, const Step &s) {
+    Tensor &in = t->tensors[o.in0];
+    sigmoid_fwd_kernel<<<grid1(in.numel(s.B)), 256, 0, s.st>>>(in.v, in.numel(s.B), t->tensors[o.out].v);
+    return AMT_OK;
+}
+int bwd_sigmoid(amt_trainer *t, Op &o, const Step &s, const float *gout) {
+    const size_t n = t->tensors[o.in0].numel(s.B);
+    const float *a = t->tensors[o.out].v;
+    return write_or_add(t, o.in0, n, s.st, [&](float *dst) { sigmoid_bwd_kernel<<<grid1(n), 256, 0, s.st>>>(gout, a, n, dst); });
+}
+
+int fwd_add(amt_trainer *t, Op &o, const Step &s) {
+    Tensor &in = t->tensors[o.in0];
+    add_kernel<<<grid1(in.numel(s.B)), 256, 0, s.st>>>(in.v, t->tensors[o.in1].v, in.numel(s.B), t->tensors[o.out].v);
+    return AMT_OK;
+}
+int bwd_add(amt_trainer *t, Op &o, const Step &s, const float *gout) {
+    const size_t n = t->tensors[o.in0].numel(s.B);
+    TR_TRY(give_view(t, o.in0, gout, n, s.st));
+    return give_view(t, o.in1, gout, n, s.st);
+}
+
+int fwd_pool(amt_trainer *t, Op &o, const Step &s) {
+    Tensor &in = t->tensors[o.in0], &out = t->tensors[o.out];
+    pool_fwd_kernel<<<grid1(out.numel(s.B)), 256, 0, s.st>>>(in.v, s.B, o.H, o.W, o.Cin, o.kh, o.kw, o.is_max, out.v, out.numel(1));
+    out.am = in.am;                             // a max / average of values bounded by the window's maximum stays bounded by it
+    return AMT_OK;
+}
+int bwd_pool(amt_trainer *t, Op &o, const Step &s, const float *gout) {
+    Tensor &in = t->tensors[o.in0], &out = t->tensors[o.out];
+    const size_t n = in.numel(s.B);
+    return write_or_add(t, o.in0, n, s.st, [&](float *dst) {
+        pool_bwd_kernel<<<grid1(n), 256, 0, s.st>>>(gout, out.numel(1), in.v, s.B, o.H, o.W, o.Cin, o.kh, o.kw, o.is_max, dst);
+    });
+}
+
+int fwd_flatten(amt_trainer *t, Op &o, const Step &s) {
+    Tensor &in = t->tensors[o.in0];
+    copy_rows_kernel<<<grid1(in.numel(s.B)), 256, 0, s.st>>>(in.v, in.numel(1), t->tensors[o.out].v + o.flat_off, (size_t)t->flat, s.B, in.numel(1));
+    return AMT_OK;
+}
+int bwd_flatten(amt_trainer *t, Op &o, const Step &s, const float *gout) {
+    // rows of the dense input's gradient -> this tower's last activation (written straight into its grad)
+    Tensor &in = t->tensors[o.in0];
+    copy_rows_kernel<<<grid1(in.numel(s.B)), 256, 0, s.st>>>(gout + o.flat_off, (size_t)t->flat, in.g, in.numel(1), s.B, in.numel(1));
+    in.gptr = in.g; in.g_set = true;
+    return AMT_OK;
+}
+
+struct OpFns {
+    int (*fwd)(amt_trainer *, Op &, const Step &);
+    int (*bwd)(amt_trainer *, Op &, const Step &, const float *gout);
+};
+const OpFns OP_TABLE[OP_KINDS] = {   // indexed by OpKind
+    {fwd_conv, bwd_conv}, {fwd_bn, bwd_bn}, {fwd_sigmoid, bwd_sigmoid}, {fwd_add, bwd_add},
+    {fwd_pool, bwd_pool}, {fwd_flatten, bwd_flatten}};
+
+// AMT_TRAIN_TRACE: synchronise and report after every op (a diagnostic for locating a failing launch)
+void trace_op(const amt_trainer *t, const char *phase, size_t op_no, const Op &o, hipStream_t st) {
+    if (!t->opt.trace) return;
+    const hipError_t e = hipStreamSynchronize(st);
+    fprintf(stderr, "[amt_train] %s op %d kind %d H %d W %d Cin %d Cout %d k %dx%d : %s\n", phase, (int)op_no, (int)o.kind, o.H, o.W,
+            o.Cin, o.Cout, o.kh, o.kw, hipGetErrorString(e));
+    fflush(stderr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int amt_trainer_destroy(amt_trainer *t) {
+    if (!t) return AMT_OK;
+    for (float *p : t->allocs) (void)hipFree(p);
+    for (Tensor &x : t->tensors) { x.v.release(); x.g.release(); }
+    for (DevBuf *b : {&t->col, &t->red0, &t->red1, &t->red2, &t->amax, &t->pred, &t->loss_rows, &t->dlogits, &t->part}) b->release();
+    delete t;
+    return AMT_OK;
+}
+
+int amt_trainer_create(amt_trainer **out, const amt_rdcnn_desc *desc, const float *wh, size_t n_floats, float lr,
+                       float epsilon, float initial_accumulator) {
+    if (!out || !desc || !wh) return AMT_E_INVALID;
+    RdTopology tp;
+    if (amt_rdcnn_topology(*desc, &tp) != AMT_OK || tp.total != n_floats || n_floats == 0) return AMT_E_SHAPE;
+    if (!tp.shortcut_ok) return AMT_E_UNSUPPORTED;
+    amt_trainer *t = new amt_trainer();
+    t->d = *desc;
+    t->blob_floats = tp.total;
+    if (lr > 0.f) t->lr = lr;
+    if (epsilon > 0.f) t->eps = epsilon;
+    t->acc0 = initial_accumulator > 0.f ? initial_accumulator : 0.f;
+    const int rc = trainer_init(t, tp, wh);       // the status of what failed: AMT_E_NOMEM an allocation, AMT_E_HIP a copy
+    if (rc != AMT_OK) { amt_trainer_destroy(t); return rc; }
+    *out = t;
+    return AMT_OK;
+}
+
 int amt_trainer_step(amt_trainer *t, const float *const *x, const float *y, int B, int update, float *loss_host,
                      float *pred_out, void *stream) {
     if (!t || !x || !y || B <= 0) return AMT_E_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    int rc = ensure_batch(t, B);
-    if (rc != AMT_OK) return rc;
-    const int training = update ? 1 : 0;
+    for (size_t i = 0; i < t->inputs.size(); ++i) if (!x[i]) return AMT_E_INVALID;
+    const Step s{B, update != 0, (hipStream_t)stream};
     const int K = t->d.output_classes;
+    TR_TRY(ensure_batch(t, B));
     for (size_t i = 0; i < t->inputs.size(); ++i) {
-        if (!x[i]) return AMT_E_INVALID;
         Tensor &in = t->tensors[t->inputs[i]];
-        AMT_HIP_CHECK(hipMemcpyAsync(in.v, x[i], (size_t)B * in.H * in.W * sizeof(float), hipMemcpyDeviceToDevice, st));
+        AMT_HIP_CHECK(hipMemcpyAsync(in.v, x[i], in.numel(B) * sizeof(float), hipMemcpyDeviceToDevice, s.st));
     }
-    AMT_HIP_CHECK(hipMemsetAsync(t->amax, 0, t->amax_floats * sizeof(float), st));
+    // per-step state: the measured maxima, where each gradient lives, whose column partials red2 holds
+    AMT_HIP_CHECK(hipMemsetAsync(t->amax, 0, t->amax.cap * sizeof(float), s.st));
     for (Tensor &x_ : t->tensors) { x_.am = nullptr; x_.gam = nullptr; x_.g_set = false; x_.gptr = nullptr; }
     t->colsum_of = -1;
     if (!t->jobs.empty()) {
         // the weights moved in the last update: measure their range and lay them out for the split-fp16 kernels again
         // (two launches for every layer)
         const int nj = (int)t->jobs.size();
-        AMT_HIP_CHECK(hipMemsetAsync(t->wmax, 0, nj * sizeof(float), st));
-        rc = amt_convh_pack_all(t->jobs_dev, nj, t->max_job_elems, st);
-        if (rc != AMT_OK) return rc;
+        AMT_HIP_CHECK(hipMemsetAsync(t->wmax, 0, nj * sizeof(float), s.st));
+        TR_TRY(amt_convh_pack_all(t->jobs_dev, nj, t->max_job_elems, s.st));
     }
-    // layers too small to fill the chip stay on the GEMM path (a handful of workgroups walking the whole contraction
-    // one after the other is slower than the split-K GEMM)
-    auto fast_now = [&](const Op &o) { return o.job >= 0 && (size_t)B * o.H * o.W >= t->fast_min_m; };
-    // AMT_TRAIN_TRACE=1: synchronise and report after every op (locating a faulting kernel)
-    static const bool trace = getenv("AMT_TRAIN_TRACE") != nullptr;
-    int op_no = 0;
-    auto mark = [&](const char *phase, const Op &o) {
-        if (!trace) return;
-        const hipError_t e = hipStreamSynchronize(st);
-        fprintf(stderr, "[amt_train] %s op %d kind %d H %d W %d Cin %d Cout %d k %dx%d : %s\n", phase, op_no, (int)o.kind, o.H, o.W,
-                o.Cin, o.Cout, o.kh, o.kw, hipGetErrorString(e));
-        fflush(stderr);
-    };
     // ---------------- forward ----------------------------------------------------------------
-    for (Op &o : t->ops) {
-        Tensor &in = t->tensors[o.in0];
-        Tensor &out = t->tensors[o.out];
-        const size_t nin = (size_t)B * in.H * in.W * in.C, nout = (size_t)B * out.H * out.W * out.C;
-        switch (o.kind) {
-        case OP_CONV: {
-            const size_t M = (size_t)B * o.H * o.W;
-            const int Kc = o.kh * o.kw * o.Cin;
-            if (fast_now(o)) {
-                const float *am = in.am;
-                if (!am) {
-                    float *scratch = t->amax + (size_t)(2 * o.job) * B;
-                    rc = amt_convh_absmax(in.v, nin / B, B, scratch, st);
-                    if (rc != AMT_OK) return rc;
-                    am = scratch;
-                }
-                rc = amt_convh_run(&o.fplan, in.v, out.v, nullptr, B, o.wp_f, t->sw + o.job, t->params[o.p1].w, am,
-                                   (o.kh - 1) / 2, (o.kw - 1) / 2, st);
-                if (rc != AMT_OK) return rc;
-                break;
-            }
-            const float *A = in.v;
-            if (!(o.kh == 1 && o.kw == 1)) {
-                im2col_kernel<<<(unsigned)std::min<size_t>(M, 1u << 20), 256, 0, st>>>(in.v, (size_t)o.H * o.W * o.Cin, B, o.H, o.W, o.Cin, o.kh, o.kw, t->col);
-                A = t->col;
-            }
-            rc = gemm(t, false, false, A, Kc, t->params[o.p0].w, o.Cout, out.v, o.Cout, (int)M, o.Cout, Kc, t->params[o.p1].w, st);
-            if (rc != AMT_OK) return rc;
-            break;
-        }
-        case OP_BN: {
-            const size_t M = nin / o.Cout;
-            if (o.bn_fused) {
-                const int nwg = bnf_nwg(M, o.Cout);
-                if (training) {
-                    bnf_stats_kernel<<<nwg, 256, 0, st>>>(in.v, M, o.Cout, t->red0, t->red1);
-                    bnf_stats_final_kernel<<<(o.Cout + 31) / 32, 256, 0, st>>>(
-                        t->red0, t->red1, M, o.Cout, (int)bnf_rows_wg(o.Cout), nwg, o.bmu, o.bvar, o.binv, t->params[o.p2].w,
-                        t->params[o.p3].w, 1, M > 1 ? (float)((double)M / ((double)M - 1.0)) : 1.0f);
-                } else {
-                    AMT_HIP_CHECK(hipMemcpyAsync(o.bmu, t->params[o.p2].w, o.Cout * sizeof(float), hipMemcpyDeviceToDevice, st));
-                    inv_from_var_kernel<<<(o.Cout + 63) / 64, 64, 0, st>>>(t->params[o.p3].w, o.Cout, o.binv);
-                }
-                Tensor &dst = t->tensors[o.sig_out >= 0 ? o.sig_out : o.out];
-                bnf_act_kernel<<<nwg, 256, 0, st>>>(in.v, o.bmu, o.binv, t->params[o.p0].w, t->params[o.p1].w, M, o.Cout,
-                                                    in.H * in.W, o.sig_out >= 0 ? 1 : 0, dst.v, dst.am_slot);
-                dst.am = dst.am_slot;
-                break;
-            }
-            if (training) {
-                rc = colreduce(t, in.v, nullptr, nullptr, nullptr, M, o.Cout, 0, o.bmu, nullptr, st);
-                if (rc == AMT_OK) rc = colreduce(t, in.v, nullptr, o.bmu, nullptr, M, o.Cout, 1, o.bvar, o.binv, st);
-                if (rc != AMT_OK) return rc;
-                moving_update_kernel<<<(o.Cout + 63) / 64, 64, 0, st>>>(t->params[o.p2].w, t->params[o.p3].w, o.bmu, o.bvar, o.Cout,
-                                                                       M > 1 ? (float)((double)M / ((double)M - 1.0)) : 1.0f);
-            } else {
-                AMT_HIP_CHECK(hipMemcpyAsync(o.bmu, t->params[o.p2].w, o.Cout * sizeof(float), hipMemcpyDeviceToDevice, st));
-                inv_from_var_kernel<<<(o.Cout + 63) / 64, 64, 0, st>>>(t->params[o.p3].w, o.Cout, o.binv);
-            }
-            bn_apply_kernel<<<grid1(nin), 256, 0, st>>>(in.v, o.bmu, o.binv, t->params[o.p0].w, t->params[o.p1].w, nin, o.Cout, out.v);
-            break;
-        }
-        case OP_SIGMOID:
-            if (o.skip) break;
-            sigmoid_fwd_kernel<<<grid1(nin), 256, 0, st>>>(in.v, nin, out.v);
-            break;
-        case OP_ADD:
-            add_kernel<<<grid1(nin), 256, 0, st>>>(in.v, t->tensors[o.in1].v, nin, out.v);
-            break;
-        case OP_POOL:
-            pool_fwd_kernel<<<grid1(nout), 256, 0, st>>>(in.v, B, o.H, o.W, o.Cin, o.kh, o.kw, o.is_max, out.v,
-                                                          (size_t)out.H * out.W * out.C);
-            out.am = in.am;                         // a max / average of values bounded by the window's maximum stays bounded by it
-            break;
-        case OP_FLATTEN:
-            copy_rows_kernel<<<grid1(nin), 256, 0, st>>>(in.v, (size_t)in.H * in.W * in.C, out.v + o.flat_off, (size_t)t->flat,
-                                                          B, (size_t)in.H * in.W * in.C);
-            break;
-        case OP_DENSE:
-            rc = gemm(t, false, false, in.v, o.Cin, t->params[o.p0].w, o.Cout, out.v, o.Cout, B, o.Cout, o.Cin, t->params[o.p1].w, st);
-            if (rc != AMT_OK) return rc;
-            break;
-        }
-        mark("fwd", o);
-        ++op_no;
+    for (size_t i = 0; i < t->ops.size(); ++i) {
+        Op &o = t->ops[i];
+        if (o.skip) continue;                                    // a sigmoid folded into the BatchNormalization in front
+        TR_TRY(OP_TABLE[o.kind].fwd(t, o, s));
+        trace_op(t, "fwd", i, o, s.st);
     }
     AMT_LAUNCH_CHECK();
     // ---------------- loss --------------------------------------------------------------------
-    loss_kernel<<<(B + 63) / 64, 64, 0, st>>>(t->tensors[t->t_logits].v, y, B, K, t->pred, t->dlogits, t->loss_rows);
-    if (pred_out) AMT_HIP_CHECK(hipMemcpyAsync(pred_out, t->pred, (size_t)B * K * sizeof(float), hipMemcpyDeviceToDevice, st));
+    loss_kernel<<<(B + 63) / 64, 64, 0, s.st>>>(t->tensors[t->t_logits].v, y, B, K, t->pred, t->dlogits, t->loss_rows);
+    if (pred_out) AMT_HIP_CHECK(hipMemcpyAsync(pred_out, t->pred, (size_t)B * K * sizeof(float), hipMemcpyDeviceToDevice, s.st));
     if (loss_host) {
         std::vector<float> rows(B);
-        AMT_HIP_CHECK(hipMemcpyAsync(rows.data(), t->loss_rows, B * sizeof(float), hipMemcpyDeviceToHost, st));
-        AMT_HIP_CHECK(hipStreamSynchronize(st));
-        double s = 0;
-        for (float v : rows) s += v;
-        *loss_host = (float)(s / B);
+        AMT_HIP_CHECK(hipMemcpyAsync(rows.data(), t->loss_rows, B * sizeof(float), hipMemcpyDeviceToHost, s.st));
+        AMT_HIP_CHECK(hipStreamSynchronize(s.st));
+        double sum = 0;
+        for (float v : rows) sum += v;
+        *loss_host = (float)(sum / B);
     }
     if (!update) return AMT_OK;
     // ---------------- backward ----------------------------------------------------------------
-    rc = give_view(t, t->t_logits, t->dlogits, (size_t)B * K, st);
-    if (rc != AMT_OK) return rc;
-    for (int oi = (int)t->ops.size() - 1; oi >= 0; --oi) {
-        Op &o = t->ops[oi];
-        Tensor &in = t->tensors[o.in0];
-        Tensor &out = t->tensors[o.out];
-        const size_t nin = (size_t)B * in.H * in.W * in.C;
-        if (o.kind == OP_SIGMOID && o.skip) continue;                 // folded into the BatchNormalization in front
-        const int gsrc = (o.kind == OP_BN && o.sig_out >= 0) ? o.sig_out : o.out;   // tensor whose gradient arrives here
-        if (o.kind != OP_FLATTEN && !t->tensors[gsrc].g_set) continue;               // no gradient reaches this op
-        const float *gout = t->tensors[gsrc].gptr;
-        op_no = oi;
-        mark("bwd-enter", o);
-        switch (o.kind) {
-        case OP_DENSE: {
-            // dW = in^T dOut, db = colsum dOut, dIn = dOut W^T
-            rc = gemm(t, true, false, in.v, o.Cin, gout, o.Cout, t->params[o.p0].g, o.Cout, o.Cin, o.Cout, B, nullptr, st);
-            if (rc == AMT_OK) rc = colreduce(t, gout, nullptr, nullptr, nullptr, (size_t)B, o.Cout, 3, t->params[o.p1].g, nullptr, st);
-            if (rc != AMT_OK) return rc;
-            if ((size_t)B * o.Cin > t->col_cap) return AMT_E_NOMEM;
-            rc = gemm(t, false, true, gout, o.Cout, t->params[o.p0].w, o.Cout, t->col, o.Cin, B, o.Cin, o.Cout, nullptr, st);
-            if (rc == AMT_OK) rc = give_copy(t, o.in0, t->col, (size_t)B * o.Cin, st);
-            if (rc != AMT_OK) return rc;
-            break;
-        }
-        case OP_FLATTEN: {
-            Tensor &fl = t->tensors[o.out];
-            if (!fl.g_set) break;
-            // rows of the dense input's gradient -> this tower's last activation (written straight into its grad)
-            copy_rows_kernel<<<grid1(nin), 256, 0, st>>>(fl.gptr + o.flat_off, (size_t)t->flat, in.g, (size_t)in.H * in.W * in.C, B,
-                                                          (size_t)in.H * in.W * in.C);
-            in.gptr = in.g; in.g_set = true;
-            break;
-        }
-        case OP_SIGMOID: {
-            const float *acc = nullptr;
-            float *dst = claim(t, o.in0, &acc);
-            if (acc) {
-                if (nin > t->col_cap) return AMT_E_NOMEM;
-                sigmoid_bwd_kernel<<<grid1(nin), 256, 0, st>>>(gout, out.v, nin, t->col);
-                add_kernel<<<grid1(nin), 256, 0, st>>>(acc, t->col, nin, dst);
-            } else {
-                sigmoid_bwd_kernel<<<grid1(nin), 256, 0, st>>>(gout, out.v, nin, dst);
-            }
-            break;
-        }
-        case OP_ADD: {
-            rc = give_view(t, o.in0, gout, nin, st);
-            if (rc == AMT_OK) rc = give_view(t, o.in1, gout, nin, st);
-            if (rc != AMT_OK) return rc;
-            break;
-        }
-        case OP_POOL: {
-            const float *acc = nullptr;
-            float *dst = claim(t, o.in0, &acc);
-            if (acc) {
-                if (nin > t->col_cap) return AMT_E_NOMEM;
-                pool_bwd_kernel<<<grid1(nin), 256, 0, st>>>(gout, (size_t)out.H * out.W * out.C, in.v, B, o.H, o.W, o.Cin, o.kh, o.kw,
-                                                             o.is_max, t->col);
-                add_kernel<<<grid1(nin), 256, 0, st>>>(acc, t->col, nin, dst);
-            } else {
-                pool_bwd_kernel<<<grid1(nin), 256, 0, st>>>(gout, (size_t)out.H * out.W * out.C, in.v, B, o.H, o.W, o.Cin, o.kh, o.kw,
-                                                             o.is_max, dst);
-            }
-            break;
-        }
-        case OP_BN: {
-            const size_t M = nin / o.Cout;
-            if (o.bn_fused) {
-                // dgamma = sum dy zhat, dbeta = sum dy, with dy = dA a (1 - a) when the sigmoid is folded in
-                const int nwg = bnf_nwg(M, o.Cout);
-                const float *a = o.sig_out >= 0 ? t->tensors[o.sig_out].v : nullptr;
-                bnf_bwd_reduce_kernel<<<nwg, 256, 0, st>>>(gout, a, in.v, o.bmu, o.binv, M, o.Cout, t->red0, t->red1);
-                colreduce_final_kernel<<<(o.Cout + 31) / 32, 256, 0, st>>>(t->red0, t->red1, o.Cout, 1.0f / (float)M, 2, nwg,
-                                                                             t->params[o.p1].g, t->params[o.p0].g);
-                const float *acc = nullptr;
-                float *dst = claim(t, o.in0, &acc);
-                bnf_bwd_apply_kernel<<<nwg, 256, 0, st>>>(gout, a, in.v, o.bmu, o.binv, t->params[o.p0].w, t->params[o.p1].g,
-                                                          t->params[o.p0].g, 1.0f / (float)M, M, o.Cout, in.H * in.W, acc, dst,
-                                                          t->red2, in.gam_slot);
-                // red2 now holds THIS launch's column partials: valid as the bias gradient of the convolution in front only when
-                // dz was written, not accumulated; any partials another convolution was still waiting for are gone either way
-                if (!acc) { in.gam = in.gam_slot; t->colsum_of = o.in0; t->colsum_nwg = nwg; }
-                else t->colsum_of = -1;
-                break;
-            }
-            // generic path: dy -> scratch, two column sums, dz
-            if (nin > t->col_cap) return AMT_E_NOMEM;
-            AMT_HIP_CHECK(hipMemcpyAsync(t->col, gout, nin * sizeof(float), hipMemcpyDeviceToDevice, st));
-            rc = colreduce(t, t->col, in.v, o.bmu, o.binv, M, o.Cout, 2, t->params[o.p1].g, t->params[o.p0].g, st);
-            if (rc != AMT_OK) return rc;
-            bn_backward_kernel<<<grid1(nin), 256, 0, st>>>(t->col, in.v, o.bmu, o.binv, t->params[o.p0].w, t->params[o.p1].g,
-                                                            t->params[o.p0].g, 1.0f / (float)M, nin, o.Cout, 1, t->col);
-            rc = give_copy(t, o.in0, t->col, nin, st);
-            if (rc != AMT_OK) return rc;
-            break;
-        }
-        case OP_CONV: {
-            const size_t M = (size_t)B * o.H * o.W;
-            const int Kc = o.kh * o.kw * o.Cin;
-            const bool one = o.kh == 1 && o.kw == 1;
-            if (t->wgrad_direct_on && wgrad_direct_ok(o) && M >= t->fast_min_m) {
-                rc = wgrad_direct(t, o, in.v, gout, t->params[o.p0].g, B, st);
-            } else {
-                const float *A = in.v;
-                if (!one) {
-                    im2col_kernel<<<(unsigned)std::min<size_t>(M, 1u << 20), 256, 0, st>>>(in.v, (size_t)o.H * o.W * o.Cin, B, o.H, o.W, o.Cin, o.kh, o.kw, t->col);
-                    A = t->col;
-                }
-                rc = gemm(t, true, false, A, Kc, gout, o.Cout, t->params[o.p0].g, o.Cout, Kc, o.Cout, (int)M, nullptr, st);
-            }
-            if (rc != AMT_OK) return rc;
-            // bias gradient: the column sums of dz -- per-workgroup partials are there when the BatchNormalization behind
-            // this convolution just wrote dz
-            if (t->colsum_of == o.out) {
-                colreduce_final_kernel<<<(o.Cout + 31) / 32, 256, 0, st>>>(t->red2, t->red2, o.Cout, 1.0f / (float)M, 3, t->colsum_nwg,
-                                                                             t->params[o.p1].g, nullptr);
-                t->colsum_of = -1;
-            } else {
-                rc = colreduce(t, gout, nullptr, nullptr, nullptr, M, o.Cout, 3, t->params[o.p1].g, nullptr, st);
-                if (rc != AMT_OK) return rc;
-            }
-            const bool is_input = std::find(t->inputs.begin(), t->inputs.end(), o.in0) != t->inputs.end();
-            if (is_input) break;                                        // no gradient wrt the network input
-            if (o.fast_bwd && fast_now(o)) {
-                // dX = correlation of dOut with the flipped, transposed kernel (mirror-image padding), written into the
-                // input's gradient buffer, plus what the shortcut branch already handed to that tensor
-                const float *am = out.gam;
-                if (!am) {
-                    float *scratch = t->amax + (size_t)(2 * o.job + 1) * B;
-                    rc = amt_convh_absmax(gout, (size_t)o.H * o.W * o.Cout, B, scratch, st);
-                    if (rc != AMT_OK) return rc;
-                    am = scratch;
-                }
-                const float *acc = nullptr;
-                float *dst = claim(t, o.in0, &acc);
-                rc = amt_convh_run(&o.bplan, gout, dst, acc, B, o.wp_b, t->sw + o.job, nullptr, am,
-                                   o.kh - 1 - (o.kh - 1) / 2, o.kw - 1 - (o.kw - 1) / 2, st);
-                if (rc != AMT_OK) return rc;
-                break;
-            }
-            // dcol = dOut W^T (into col), then gathered back to the image
-            rc = gemm(t, false, true, gout, o.Cout, t->params[o.p0].w, o.Cout, t->col, Kc, (int)M, Kc, o.Cout, nullptr, st);
-            if (rc != AMT_OK) return rc;
-            if (one) rc = give_copy(t, o.in0, t->col, nin, st);
-            else {
-                Tensor &inT = t->tensors[o.in0];
-                if (!inT.g_set) {
-                    col2im_kernel<<<(unsigned)std::min<size_t>(M, 1u << 20), 256, 0, st>>>(t->col, B, o.H, o.W, o.Cin, o.kh, o.kw, inT.g);
-                    inT.gptr = inT.g; inT.g_set = true; inT.gam = nullptr;
-                } else {
-                    // dOut's own buffer is dead once both GEMMs above have read it: gather there, then add
-                    if (gout != out.g || (size_t)B * out.H * out.W * out.C < nin) return AMT_E_NOMEM;
-                    col2im_kernel<<<(unsigned)std::min<size_t>(M, 1u << 20), 256, 0, st>>>(t->col, B, o.H, o.W, o.Cin, o.kh, o.kw, out.g);
-                    rc = give_copy(t, o.in0, out.g, nin, st);
-                }
-            }
-            if (rc != AMT_OK) return rc;
-            break;
-        }
-        }
+    TR_TRY(give_view(t, t->t_logits, t->dlogits, (size_t)B * K, s.st));
+    for (size_t i = t->ops.size(); i-- > 0;) {
+        Op &o = t->ops[i];
+        if (o.skip) continue;
+        const Tensor &from = t->tensors[o.kind == OP_BN && o.sig_out >= 0 ? o.sig_out : o.out];   // whose gradient arrives here
+        if (!from.g_set) continue;                               // no gradient reaches this op
+        trace_op(t, "bwd-enter", i, o, s.st);
+        TR_TRY(OP_TABLE[o.kind].bwd(t, o, s, from.gptr));
     }
     AMT_LAUNCH_CHECK();
     // ---------------- update -------------------------------------------------------------------
-    adagrad_kernel<<<grid1(t->arena_used), 256, 0, st>>>(t->w_arena, t->g_arena, t->a_arena, t->arena_used, t->lr, t->eps);
+    adagrad_kernel<<<grid1(t->arena_used), 256, 0, s.st>>>(t->w_arena, t->g_arena, t->a_arena, t->arena_used, t->lr, t->eps);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }
 
 static int copy_out(amt_trainer *t, float *host, size_t n, bool grads) {
     if (!t || !host) return AMT_E_INVALID;
-    size_t total = 0;
-    for (const Param &p : t->params) total += p.n;
-    if (total != n) return AMT_E_SHAPE;
+    if (t->blob_floats != n) return AMT_E_SHAPE;
     AMT_HIP_CHECK(hipDeviceSynchronize());
-    float *cur = host;
     for (const Param &p : t->params) {
-        if (grads && !p.trainable) memset(cur, 0, p.n * sizeof(float));
-        else AMT_HIP_CHECK(hipMemcpy(cur, grads ? p.g : p.w, p.n * sizeof(float), hipMemcpyDeviceToHost));
-        cur += p.n;
+        if (grads && !p.trainable) memset(host + p.off, 0, p.n * sizeof(float));
+        else AMT_HIP_CHECK(hipMemcpy(host + p.off, grads ? p.g : p.w, p.n * sizeof(float), hipMemcpyDeviceToHost));
     }
     return AMT_OK;
 }

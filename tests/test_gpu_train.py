@@ -118,6 +118,40 @@ def test_train_batch_size_changes_between_steps(env, monkeypatch):
         _, acc = _compare_step(env, net, xs, y, w_dev, acc, 'batch %d' % B)
 
 
+def test_regrowth_changes_nothing_but_capacity(env, monkeypatch):
+    """The trainer's per-batch buffers free what they hold and grow when a larger batch arrives.  Net A trains on 3 windows,
+    then on 7: its buffers grow between the steps.  Net B (same seed) first runs test() on 7 windows -- which sizes the
+    buffers and moves no state -- then trains on the same two batches in buffers that never grow.  Loss, predictions,
+    every gradient and the synced weights are equal bit for bit after each step: a pointer into a buffer that was not
+    derived again after the growth (the per-window maxima rows), or a freed partial-sum / im2col buffer still in use,
+    shows up as a difference (fast forms on, so those buffers are all in play)."""
+    monkeypatch.setenv('AMT_TRAIN_FAST_MIN_M', '0')
+    a = env['rdcnn'].res_net(weight_seed=77, calibrated=False, **CASES[1])
+    b = env['rdcnn'].res_net(weight_seed=77, calibrated=False, **CASES[1])
+    batches = [_batch(a.cfg, B, 950 + i) for i, B in enumerate((3, 7))]
+    one = (lambda xs: xs if len(xs) > 1 else xs[0])
+    w0 = {k: v.copy() for k, v in b.weights.items()}
+    b.test(one(batches[1][0]), batches[1][1])
+    b._trained = True                      # pull the device's weights back although no train() has run
+    b._sync_from_trainer()
+    assert all(b.weights[k].tobytes() == w0[k].tobytes() for k in w0)            # test() moved nothing
+    for i, (xs, y) in enumerate(batches):
+        out = []
+        for net in (a, b):
+            pred = net.train(one(xs), y)
+            grads = net.gradients()
+            net._sync_from_trainer()
+            out.append((np.float32(net.metrics_train[-1][0]), pred, grads, {k: v.copy() for k, v in net.weights.items()}))
+        (la, pa, ga, wa), (lb, pb, gb, wb) = out
+        assert la.tobytes() == lb.tobytes(), (i, la, lb)
+        assert np.array_equal(pa, pb) and pa.dtype == pb.dtype, i
+        assert set(ga) == set(gb) and set(wa) == set(wb)
+        for k in ga:
+            assert ga[k].tobytes() == gb[k].tobytes(), (i, 'gradient', k)
+        for k in wa:
+            assert wa[k].tobytes() == wb[k].tobytes(), (i, 'weight', k)
+
+
 def test_velocity_head_first_step_and_learning(env):
     """The reference's smallest head (11 conv layers, 36 x 8 input) on a batch of 8 (main.py -batch_size): the first
     train_on_batch matches the oracle; and forty steps on a fixed batch drive the loss of two shallow nets (one

@@ -75,6 +75,64 @@ def test_param_counts_match_survey():
         heads.InstrumentClassifier(p, 'Invalid')
 
 
+def test_param_count_matches_python_layout_over_topology_grid():
+    """amt_rdcnn_param_count (the C++ topology walk every create reads) == the size of the product's own Python layout,
+    sum(prod(shape)) over res_net(...).layout, over a grid of descriptions: one and two towers (the second tower takes
+    the next input shape, kernel and another pool size), every kernel size of the heads, three inputs, residual
+    frequency 0..3, pool frequency 0..2, feature expansion 0..2, 1..6 layers.  A max pool that collapses an activation
+    (H or W below 1) gives a count of 0.  The grid holds shortcuts with a pool but no channel change, with a channel
+    change but no pool, and with neither."""
+    import itertools
+    from amt_saga import _lib, rdcnn
+    lib = _lib.load()
+
+    class LayoutOnly(rdcnn.res_net):
+        """res_net(...) up to its layout: no weights are drawn (the widest grid entries hold 10^8 floats)."""
+        def init_weights(self, *a, **k):
+            return {}
+
+        def set_weights(self, w):
+            pass
+
+    kernels, inputs, pools = [(4, 16), (4, 2), (2, 2)], [(20, 32), (8, 8), (5, 8)], [(2, 2), (1, 2), (2, 1)]
+    seen = {'pool only': 0, 'channels only': 0, 'neither': 0, 'both': 0, 'collapse': 0}
+    n_cases = 0
+    for towers, ki, ii, r, pf, ff, layers in itertools.product((1, 2), range(3), range(3), range(4), range(3), range(3),
+                                                               range(1, 7)):
+        tw = [((ii + t) % 3, (ki + t) % 3) for t in range(towers)]
+        net = LayoutOnly(input_shapes=[inputs[i] + (1,) for i, _ in tw], kernel_sizes=[kernels[k] for _, k in tw],
+                         pool_sizes=[pools[k] for _, k in tw], output_classes=3 if towers == 1 else 1, output_range=[0, 10],
+                         convolutional_layer_count=layers, feature_expand_frequency=ff, pool_layer_frequency=pf,
+                         residual_layer_frequencies=r)
+        n_py = sum(int(np.prod(shape)) for _, shape in net.layout)
+        n_c = lib.amt_rdcnn_param_count(ctypes.byref(net._desc()))
+        # what the description means, restated here only as far as the required cases need it
+        collapse = False
+        for i_in, k in tw:
+            (H, W), (ph, pw), C, fo = inputs[i_in], pools[k], 1, 32
+            src = (H, W, 1)
+            for i in range(1, layers + 1):
+                C = fo
+                if r and i % r == 0:
+                    kind = ('both' if src[2] != C else 'pool only') if src[:2] != (H, W) else \
+                        ('channels only' if src[2] != C else 'neither')
+                    seen[kind] += 1
+                    src = (H, W, C)
+                if pf and i % pf == 0:
+                    H, W = H // ph, W // pw
+                    collapse = collapse or H < 1 or W < 1
+                if ff and i % ff == 0:
+                    fo *= 2
+        n_cases += 1
+        if collapse:
+            seen['collapse'] += 1
+            assert n_c == 0, (net.cfg, n_c)
+        else:
+            assert n_c == n_py and n_c > 0, (net.cfg, n_c, n_py)
+    assert n_cases == 2 * 3 * 3 * 4 * 3 * 3 * 6
+    assert all(v > 0 for v in seen.values()), seen
+
+
 def test_product_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():
