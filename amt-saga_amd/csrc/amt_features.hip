@@ -80,10 +80,11 @@ __global__ __launch_bounds__(256) void compress_bands_kernel(
 #pragma unroll
     for (int q = 0; q < MAXQ; ++q) v[q] = (frame_ok && lane + 64 * q < F) ? v[q] : 0.f;
     if (frame_max && frame_ok) {
-        // the frame is in registers anyway: its maximum, for amt_subtract_span (identity frame map: every frame once)
-        float m = v[0];
+        // the frame is in registers anyway: its maximum, for amt_subtract_span (identity frame map: every frame once).
+        // The lanes past F hold the sums' 0: they stand aside here, or a frame below zero throughout would report 0.
+        float m = -INFINITY;
 #pragma unroll
-        for (int q = 1; q < MAXQ; ++q) m = fmaxf(m, v[q]);
+        for (int q = 0; q < MAXQ; ++q) m = fmaxf(m, lane + 64 * q < F ? v[q] : -INFINITY);
         m = wave_max(m);
         if (lane == 0) frame_max[(size_t)b * T + t] = m;
     }

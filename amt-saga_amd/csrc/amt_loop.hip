@@ -16,7 +16,8 @@ __global__ void round_clamp_kernel(const float *__restrict__ x, int n, int strid
     out[i] = r;
 }
 
-// argmax over K classes, first maximum (numpy argmax)
+// argmax over K classes, first maximum (numpy argmax on rows without NaN).  A NaN is never selected: a leading one
+// gives way to the first number behind it (-inf included); a row of NaNs alone gives 0.
 __global__ void argmax_rows_kernel(const float *__restrict__ p, int n, int K,
                                    int32_t *__restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -25,7 +26,7 @@ __global__ void argmax_rows_kernel(const float *__restrict__ p, int n, int K,
     int best = 0;
     float bv = r[0];
     for (int k = 1; k < K; ++k)
-        if (r[k] > bv) { bv = r[k]; best = k; }
+        if (r[k] > bv || (bv != bv && r[k] == r[k])) { bv = r[k]; best = k; }
     out[i] = best;
 }
 

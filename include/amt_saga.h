@@ -148,7 +148,8 @@ int amt_compress_bands(const float *mag, int B, int T, int F, int ldf, size_t sp
                        const int32_t *src_frame, float *out, int target_frames,
                        void *stream);
 /* The same, also leaving frame_max [B][T] = max over the F bins of every frame (the kernel has the frame in registers):
- * what amt_subtract_span needs.  Identity frame map only (src_frame NULL, target_frames == T). */
+ * what amt_subtract_span needs.  Identity frame map only (src_frame NULL, target_frames == T).  Any sign: the pad bins
+ * beyond F take no part.  Spectra hold no NaN; if one does, fmaxf passes over it (a frame of NaNs alone gives -inf). */
 int amt_compress_bands_fmax(const float *mag, int B, int T, int F, int ldf, size_t spec_stride,
                             const int32_t *edges, int bands, const float *ref,
                             const int32_t *src_frame, float *out, int target_frames,
@@ -246,7 +247,9 @@ int amt_cqt_window_max(const float *wave, int B, int L, size_t wave_stride, int 
 /* out[i] = clamp(rint(x[i*stride]), lo, hi)  (half-to-even; NaN -> lo) */
 int amt_round_clamp(const float *x, int n, int stride, int lo, int hi, int32_t *out,
                     void *stream);
-/* out[i] = first argmax of p[i][0..K)  (np.argmax) */
+/* out[i] = first argmax of p[i][0..K)  (np.argmax on a row without NaN).  A NaN is never selected: the
+ * result is the first largest of the row's other elements (-inf included); a row of NaNs alone gives 0.
+ * That is a decision, not numpy's rule (np.argmax returns the first NaN). */
 int amt_argmax_rows(const float *p, int n, int K, int32_t *out, void *stream);
 /* out[b][j] = source frame of column j of _resize(X[:, start[b]:end[b]], frames)
  * (util_audio.py:384-409 with numpy slice clamping to [0,T]); -1 = zero column */

@@ -34,6 +34,171 @@ def test_glue_kernels(env):
         assert np.array_equal(tab[i], slice_C_frames(T, int(s[i]), int(e[i]), 8)), i
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# the integer glue through the C ABI against the restatements of tests/features_reference.py
+# (test_features_reference_cpu.py pins those); every comparison is exact
+# ---------------------------------------------------------------------------------------------------------------------
+def _glue(env):
+    import features_reference as fr      # tests/features_reference.py
+    from amt_saga import _lib
+    torch = env['torch']
+    up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    ptr = lambda t: None if t is None else t.data_ptr()
+
+    def ints(n):                                  # sentinel-filled int32 output with room behind it
+        return torch.full((n + 3,), -7, dtype=torch.int32, device='cuda')
+
+    def fetch(buf, n):
+        torch.cuda.synchronize()
+        o = buf.cpu().numpy()
+        assert np.all(o[n:] == -7), 'written past the documented extent'
+        return o[:n]
+    return fr, _lib, env['lib'], up, ptr, ints, fetch
+
+
+def test_resize_table_every_interval(env):
+    """Every (s, t) in [-2, T + 2]^2 at T = 12 in one launch per frames = 3, 4, 8, 32: 17 x 17 = 289 windows, at 32 frames
+    9248 entries in 37 workgroups, the last one partial.  That is the whole len 0 / < 3 / < frames / >= frames partition
+    of _resize.  frames < 3 is refused."""
+    fr, L, lib, up, ptr, ints, fetch = _glue(env)
+    T = fr.RESIZE_T
+    s, t = [a.ravel().astype(np.int32) for a in np.meshgrid(np.arange(-2, T + 3), np.arange(-2, T + 3), indexing='ij')]
+    n = len(s)
+    assert n >= 256
+    d_s, d_t = up(s), up(t)
+    for frames in fr.RESIZE_FRAMES:
+        out = ints(n * frames)
+        assert lib.amt_resize_table(ptr(d_s), ptr(d_t), n, T, frames, ptr(out), None) == L.AMT_OK
+        got = fetch(out, n * frames).reshape(n, frames)
+        want = fr.resize_table(s, t, T, frames)
+        bad = np.flatnonzero((got != want).any(axis=1))
+        assert len(bad) == 0, (frames, int(s[bad[0]]), int(t[bad[0]]), got[bad[0]].tolist(), want[bad[0]].tolist())
+    out = ints(n * 2)
+    for frames in (2, 0, -1):
+        assert lib.amt_resize_table(ptr(d_s), ptr(d_t), n, T, frames, ptr(out), None) == L.AMT_E_INVALID
+    fetch(out, 0)
+
+
+def test_round_clamp_edges(env):
+    """n = 600 (three workgroups): halves of both parities and signs, lo and hi themselves, lo - 0.5 and hi + 0.5,
+    +-inf, NaN, +-3e9, -0.0, among values spread over and beyond [lo, hi]; stride 1 and stride 3 over an [n, 3] tensor
+    whose other columns would give other answers; lo == hi; lo > hi refused."""
+    fr, L, lib, up, ptr, ints, fetch = _glue(env)
+    n = 600
+    rng = np.random.default_rng(12)
+    for lo, hi in ((0, 50), (-7, 6), (21, 21)):
+        x = rng.uniform(lo - 5, hi + 5, n).astype(np.float32)
+        x[:200] = np.round(x[:200]) + rng.choice([-0.5, 0.5], 200)      # halves, both parities and signs
+        special = [0.5, 1.5, 2.5, 3.5, -0.5, -1.5, -2.5, -3.5, lo, hi, lo - 0.5, hi + 0.5, lo + 0.5, hi - 0.5, np.inf,
+                   -np.inf, np.nan, 3e9, -3e9, -0.0, 2.4999, 2.5001]
+        x[300:300 + len(special)] = special
+        x[-1], x[255], x[256] = np.nan, hi + 0.5, lo - 0.5              # the last thread, both sides of a workgroup edge
+        want = fr.round_clamp(x, lo, hi)
+        out, d_x = ints(n), up(x)
+        assert lib.amt_round_clamp(ptr(d_x), n, 1, lo, hi, ptr(out), None) == L.AMT_OK
+        got = fetch(out, n)
+        assert np.array_equal(got, want), (lo, hi, x[got != want].tolist(), got[got != want].tolist())
+        x3 = np.stack([x[::-1], x, np.full(n, np.nan, np.float32)], axis=1)
+        d_x3 = up(x3)
+        for col in range(2):
+            out = ints(n)
+            assert lib.amt_round_clamp(ptr(d_x3) + 4 * col, n, 3, lo, hi, ptr(out), None) == L.AMT_OK
+            assert np.array_equal(fetch(out, n), fr.round_clamp(x3[:, col], lo, hi)), (lo, hi, col)
+    out = ints(n)
+    assert lib.amt_round_clamp(ptr(d_x), n, 1, 5, 4, ptr(out), None) == L.AMT_E_INVALID
+    assert lib.amt_round_clamp(ptr(d_x), n, 0, 0, 4, ptr(out), None) == L.AMT_E_INVALID
+    fetch(out, 0)
+
+
+def test_argmax_rows_ties_inf_nan(env):
+    """K = 1, 2, 88, 129 at n = 300 (two workgroups): ties at the first / a middle / the last class, rows of equal
+    values, rows holding -inf and +inf, a row of NaNs (-> 0) and rows with one NaN at the first, a middle and the last
+    class.  A NaN is never selected (the header's rule, not numpy's)."""
+    fr, L, lib, up, ptr, ints, fetch = _glue(env)
+    n = 300
+    for K in (1, 2, 88, 129):
+        rng = np.random.default_rng(K)
+        p = rng.standard_normal((n, K)).astype(np.float32)
+        mid = K // 2
+        top = np.float32(9.0)
+        p[0, [0, K - 1]] = top                                          # tie first / last
+        p[1, [mid, K - 1]] = top                                        # tie middle / last
+        p[2, [0, mid]] = top
+        p[3] = 0.25                                                     # all equal
+        p[4] = -np.inf                                                  # all -inf
+        p[5] = -np.inf
+        p[5, K - 1] = -1e30                                             # one number behind -inf
+        p[6, mid] = np.inf
+        p[7] = np.nan                                                   # a row of NaNs
+        p[8, 0] = np.nan                                                # one NaN: first, middle, last
+        p[9, mid] = np.nan
+        p[10, K - 1] = np.nan
+        p[11] = np.nan
+        p[11, K - 1] = -np.inf                                          # NaNs, then -inf: the -inf is the choice
+        p[12, 0], p[12, K - 1] = np.nan, top
+        p[256:268] = p[:12]                                             # the same in the second workgroup
+        p[299] = p[8]
+        want = fr.argmax_rows(p)
+        clean = ~np.isnan(p).any(axis=1)
+        assert np.array_equal(want[clean], p[clean].argmax(axis=1))
+        out, d_p = ints(n), up(p)
+        assert lib.amt_argmax_rows(ptr(d_p), n, K, ptr(out), None) == L.AMT_OK
+        got = fetch(out, n)
+        bad = np.flatnonzero(got != want)
+        assert len(bad) == 0, (K, bad.tolist(), got[bad].tolist(), want[bad].tolist())
+        chosen = p[np.arange(n), got]
+        assert not np.isnan(chosen[~np.isnan(p).all(axis=1)]).any()
+
+
+def test_note_select_clamps(env):
+    """n = 300: programs -1, 0 .. n_prog + 3 with and without a prog_group table and with program NULL; pitches below
+    pitch_lo and at / above pitch_lo + n_pitch; end < onset; end - onset + tail above bank_frames."""
+    fr, L, lib, up, ptr, ints, fetch = _glue(env)
+    n, n_prog, pitch_lo, n_pitch, tail, bank = 300, 5, 21, 88, 43, 173
+    rng = np.random.default_rng(3)
+    program = rng.integers(-1, n_prog + 4, n).astype(np.int32)
+    pitch = rng.integers(pitch_lo - 4, pitch_lo + n_pitch + 4, n).astype(np.int32)
+    onset = rng.integers(0, 200, n).astype(np.int32)
+    end = (onset + rng.integers(-50, 200, n)).astype(np.int32)
+    program[:3], program[-3:] = (-1, 0, n_prog + 3), (n_prog + 3, -1, n_prog)
+    pitch[:4] = (pitch_lo - 1, pitch_lo, pitch_lo + n_pitch - 1, pitch_lo + n_pitch)
+    pitch[-2:] = (pitch_lo + n_pitch + 3, pitch_lo - 4)
+    onset[4:8], end[4:8] = (10, 10, 0, 100), (9, 10, bank - tail, 100 + bank - tail + 1)
+    group = np.array([2, 0, 1, 1, 3], np.int32)
+    assert (end < onset).any() and (end - onset + tail > bank).any()
+    for prog, grp in ((program, group), (program, None), (None, group), (None, None)):
+        gi, gf = ints(n), ints(n)
+        d = [up(a) for a in (prog, pitch, onset, end, grp)]
+        st = lib.amt_note_select(ptr(d[0]), ptr(d[1]), ptr(d[2]), ptr(d[3]), ptr(d[4]), n_prog, n,
+                                 pitch_lo, n_pitch, tail, bank, ptr(gi), ptr(gf), None)
+        assert st == L.AMT_OK
+        wi, wf = fr.note_select(prog, pitch, onset, end, grp, n_prog, pitch_lo, n_pitch, tail, bank)
+        assert np.array_equal(fetch(gi, n), wi) and np.array_equal(fetch(gf, n), wf), (prog is None, grp is None)
+        assert wi.min() >= 0 and wi.max() < (4 if grp is not None else 1) * n_pitch and wf.min() >= tail and wf.max() == bank
+
+
+def test_pack_events_and_affine(env):
+    """pack_events at n = 300 with window0 and iter non-zero: all five columns, then each of them NULL in turn (-1);
+    affine_i32 with a negative multiplier."""
+    fr, L, lib, up, ptr, ints, fetch = _glue(env)
+    n = 300
+    rng = np.random.default_rng(4)
+    cols = [rng.integers(0, 500, n).astype(np.int32) for _ in range(5)]
+    d_cols = [up(c) for c in cols]
+    for drop in (None, 0, 1, 2, 3, 4):
+        out = ints(n * 7)
+        args = [None if c == drop else ptr(d_cols[c]) for c in range(5)]
+        assert lib.amt_pack_events(n, 1000, 3, *args, ptr(out), None) == L.AMT_OK
+        want = fr.pack_events(n, 1000, 3, *[None if c == drop else cols[c] for c in range(5)])
+        assert np.array_equal(fetch(out, n * 7).reshape(n, 7), want), drop
+    x = rng.integers(-1000, 1000, n).astype(np.int32)
+    d_x = up(x)
+    for mul, add in ((-4, 7), (3, -100), (0, 5)):
+        out = ints(n)
+        assert lib.amt_affine_i32(ptr(d_x), n, mul, add, ptr(out), None) == L.AMT_OK
+        assert np.array_equal(fetch(out, n), fr.affine_i32(x, mul, add)), (mul, add)
+
+
 # Near-tie policy and the per-window comparison: oracle/compare.py (shared with test_gpu_synth and smoke()).
 import os
 from oracle.compare import bands_for, compare_windows
