@@ -36,6 +36,12 @@
 // weight group; small images (H x W <= 64) use the masked form (no halo).  Tile geometry and the
 // masked idea follow conv_bf16x6_kernel (amt_conv_bf16x6.h).  An earlier two-M-tiles-per-wave kernel on
 // v_mfma_f32_32x32x16_f16 and the experiments around it are recorded in profiles/r01/ablation_f16x3.txt.
+//
+// conv_f16x3w_kernel (end of this file) is a second small-image form for the 4 x 16 kernels: window-major
+// M-subtiles (16 windows at ONE output position), so that the tap pairs which fall into the 'same' padding are
+// known per subtile and are skipped instead of multiplied by zeros.  The 4 x 16 layers on H x W <= 64 images use
+// it in modes 2 and 3; AMT_CONV_WMAJOR=0 in the environment, read when a net is created, keeps them on the masked
+// form (same bits, tests/test_gpu_small_conv.py).
 #pragma once
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -471,6 +477,321 @@ __global__ __launch_bounds__(1024 / MS, MS == 2 ? 4 : 2) void conv_f16x3s_kernel
         }
         __syncthreads();
         if (tid < p.NWIN && win0 + tid < p.B) atomicMax(reinterpret_cast<int *>(hs.amax_out) + win0 + tid, win_max[tid]);
+    }
+    if (tsp && tid == 0) tsp[3] = wall_clock64();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Window-major small-image form: KH x KW = 4 x 16 on whole H x W <= 64 images, inference only.
+//
+// The masked form above takes 16 consecutive POSITIONS as an M-subtile, so every tap is in bounds for some lane of
+// every subtile and all NTAPS / 2 tap pairs are multiplied -- on a 5 x 8 image 55 % of them entirely by the zeros
+// of the 'same' padding (PAD_T = 1, PAD_L = 7: 16 of 20 (row, tap row) pairs are valid and a column touches 4 or 5
+// of the 8 tap pairs of a kernel row).  Here an M-subtile is 16 WINDOWS at one output position (r, c).  Whether
+// a tap pair (dy, dx .. dx + 1) is valid, half valid or all padding is then the same for the 16 rows: a
+// wave-uniform bit.  An all-padding pair issues neither A reads nor MFMAs for that subtile, and no B reads if no
+// subtile of the wave needs it; a half-valid pair points the lanes of the missing tap (tsel) at the all-zero
+// position, as the masked form does per lane.  The skipped MFMAs would have added exact zeros, and what remains runs
+// in the masked form's order (16-channel chunk outer, tap pairs ascending, lo / hi / lo per block, same K layout of
+// a block), so the outputs are bit-identical to the masked form's.
+//
+// Workgroup: 512 threads = 8 waves, 16 windows x every position x 32 output channels; 1-D grid of
+// ceil(B / 16) x nslice workgroups with the N-slice in the low bits of the workgroup id, so that the workgroups an
+// XCD receives (id % 8) stream one slice's weights through its L2, not all of them.  LDS: two 32-KB weight groups +
+// one chunk of the 16 images ([position][window][80 B]: 51 KB for 5 x 8) = 115 KB, one workgroup per CU, 256
+// VGPRs per lane; 1024 windows x 4 slices are 256 workgroups = one round of the chip.
+// The position pitch 16 x 80 B = 5 x 256 B keeps the masked form's conflict-free ds_read_b128 pattern: the tsel
+// lanes land on the bank slots of their own row, and a lane group covers 16 different rows.
+//
+// Balance.  Weight groups are handed over with a barrier, so a group costs what its slowest wave costs.  A weight
+// group here is one whole KERNEL ROW (dy, all 8 tap pairs, 32 KB) instead of half a row, and wave w owns the positions
+// q = w, w + 8, w + 16 ... (MS of them; for W = 8: column w, every row).  Per group every wave then has the same
+// number of live rows (5 x 8: 4, 5, 4, 3 for dy = 0 .. 3) and 4 or 5 tap pairs per live row (columns 7, 5, 3, 1: 4;
+// columns 6, 4, 2, 0: 5), so the four groups of a chunk cost at most 20, 25, 20, 15 subtile-steps against a mean of
+// 18, 22.5, 18, 13.5: 90 % balanced.  (With half-row groups a column costs 4 + 0 .. 1 + 4 pairs and nothing is saved.)
+// Other image shapes get the same assignment; their balance is whatever q % 8 gives.
+// The next chunk's images are requested under the last weight group of a chunk and split into LDS after it.
+// ---------------------------------------------------------------------------------------------
+#define HXW_WIN 16                           // windows per workgroup = rows of an M-subtile
+#define HXW_PPITCH (HXW_WIN * HX_PSTRIDE)    // bytes per staged position
+#define HXW_NWAVE 8
+template <int KW>
+__host__ __device__ constexpr int hxw_group_bytes() { return (KW / 2) * 4096; }
+// dynamic LDS bytes of conv_f16x3w_kernel for an image of npos positions
+template <int KW>
+__host__ __device__ constexpr size_t hxw_lds_bytes(int npos) {
+    const size_t tile = (size_t)npos * HXW_PPITCH + HX_PSTRIDE, patch = (size_t)HXW_NWAVE * 16 * HX_TPITCH * 4;
+    return 2 * (size_t)hxw_group_bytes<KW>() + 3 * HXW_WIN * 4 + 512 + (tile > patch ? tile : patch);
+}
+// MS = positions per wave (H * W <= 8 MS)
+template <int KH, int KW, int CIN, int MS>
+__global__ __launch_bounds__(64 * HXW_NWAVE, 2) void conv_f16x3w_kernel(ConvParams p, const uint4 *__restrict__ w16s, HxScale hs,
+                                                                         int nslice) {
+    constexpr int NT = 64 * HXW_NWAVE;
+    constexpr int NIT = (MS + 1) / 2;                               // staged 32-byte items per thread: 16 x 8 MS x 2 / 512
+    constexpr int NCHUNK = CIN / BX_CC;
+    constexpr int PAD_T = (KH - 1) / 2, PAD_L = (KW - 1) / 2;
+    constexpr int NTP = KW / 2;                                     // tap pairs of a kernel row = 4-KB slabs of a weight group
+    constexpr int GV4 = hxw_group_bytes<KW>() / 16;
+    constexpr int NG = KH, NGT = NCHUNK * NG;
+    constexpr int WPT = GV4 / NT;
+    constexpr int BATCH = MS <= 5 ? MS : 2;                         // subtiles whose A fragments are in flight together
+    constexpr bool PREFETCH = MS <= 5;                              // the next chunk's tile is requested a weight group ahead (MS = 8: no registers for it)
+    static_assert(KW % 2 == 0 && NTP <= 8 && GV4 % NT == 0 && MS % BATCH == 0, "whole groups");
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    uint4 *wbuf = reinterpret_cast<uint4 *>(smem);                  // [2][GV4]
+    float *win_is = reinterpret_cast<float *>(wbuf + 2 * GV4);      // [16] 2^sa of the workgroup's windows
+    float *win_os = win_is + HXW_WIN;                               // [16] 2^-(sa + sw)
+    int *win_max = reinterpret_cast<int *>(win_os + HXW_WIN);       // [16] max |output| (float bits)
+    float *bnp = reinterpret_cast<float *>(win_max + HXW_WIN);      // [4][32] s1, t1, s2, t2 of this 32-channel slice
+    char *in_lds = reinterpret_cast<char *>(bnp + 128);             // [npos][16 windows][80 B] + one all-zero position
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    unsigned long long *tsp = hs.ts ? hs.ts + (size_t)blockIdx.x * 4 : nullptr;
+    if (tsp && tid == 0) tsp[0] = wall_clock64();
+    const int slice = blockIdx.x % nslice, win0 = (blockIdx.x / nslice) * HXW_WIN;
+    const int cout_off = slice * 32;
+    const uint4 *w16 = w16s + (size_t)slice * ((size_t)NCHUNK * NG * GV4);
+    const int npos = p.H * p.W;
+
+    float my_amax = 0.f;
+    if (tid < HXW_WIN && win0 + tid < p.B) my_amax = hs.amax_in[win0 + tid];
+    float my_bn = 0.f;
+    if (tid < 128) {
+        const float *src = tid < 32 ? p.s1 : tid < 64 ? p.t1 : tid < 96 ? p.s2 : p.t2;
+        my_bn = src ? src[cout_off + (tid & 31)] : ((tid < 32 || (tid >= 64 && tid < 96)) ? 1.f : 0.f);   // absent: scale 1, shift 0
+    }
+    // wave-uniform validity of this wave's subtiles: rowm bit dy = tap row dy reads an image row; m0 / m1 bit tp = the first /
+    // second tap of pair tp reads an image column
+    unsigned rowm[MS], pm[MS], mlane[MS];                  // pm = m0 | m1; mlane = this lane's tap of the pairs
+    const int tsel = (lane >> 4) & 1;
+#pragma unroll
+    for (int ms = 0; ms < MS; ++ms) {
+        const int q = wid + HXW_NWAVE * ms;
+        const int r = q / p.W, c = q - r * p.W;
+        unsigned rm = 0, m0 = 0, m1 = 0;
+#pragma unroll
+        for (int dy = 0; dy < KH; ++dy) rm |= (unsigned)((unsigned)(r + dy - PAD_T) < (unsigned)p.H) << dy;
+#pragma unroll
+        for (int tp = 0; tp < NTP; ++tp) {
+            m0 |= (unsigned)((unsigned)(c + 2 * tp - PAD_L) < (unsigned)p.W) << tp;
+            m1 |= (unsigned)((unsigned)(c + 2 * tp + 1 - PAD_L) < (unsigned)p.W) << tp;
+        }
+        rowm[ms] = q < npos ? rm : 0u;
+        pm[ms] = m0 | m1;
+        mlane[ms] = tsel ? m1 : m0;
+    }
+    // A lane l = window l % 16, k-group l / 16: (tap t + g % 2, channels 8 (g / 2) ..), as in conv_f16x3s_kernel
+    const int abase = (wid * HXW_WIN + (lane & 15)) * HX_PSTRIDE + (lane >> 5) * 16 + tsel * HXW_PPITCH;
+    const int zero_off = npos * HXW_PPITCH + (lane >> 5) * 16;
+    if (tid < HX_PSTRIDE / 4) reinterpret_cast<unsigned *>(in_lds + npos * HXW_PPITCH)[tid] = 0u;
+    f32x4 hi[MS][2], lo[MS][2];
+#pragma unroll
+    for (int ms = 0; ms < MS; ++ms)
+#pragma unroll
+        for (int ns = 0; ns < 2; ++ns)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { hi[ms][ns][e] = 0.f; lo[ms][ns][e] = 0.f; }
+
+    u32x4 wp[WPT];
+    auto issue = [&](int gg) {
+        const uint4 *src = w16 + (size_t)gg * GV4 + tid;
+#pragma unroll
+        for (int i = 0; i < WPT; ++i)
+            asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(wp[i]) : "v"(src + i * NT) : "memory");
+    };
+    // staged 32-byte items of this thread (the same for every chunk): item = (position, window, channel half), the
+    // window fastest, so that a wave writes consecutive 80-byte pitches
+    const int items = npos * HXW_WIN * 2;
+    int sdst[NIT];                                         // LDS offset | window << 24, -1: no item
+    const float *ssrc[NIT];                                // chunk-0 source, null: absent window (zeros)
+    auto slot_live = [&](int u) { return u * NT + wid * 64 < items; };               // wave-uniform
+#pragma unroll
+    for (int u = 0; u < NIT; ++u) {
+        const int it = u * NT + tid;
+        sdst[u] = -1; ssrc[u] = nullptr;
+        if (it < items) {
+            const int cg = it & 1, w_ = (it >> 1) & (HXW_WIN - 1), q = it >> 5, gw = win0 + w_;
+            sdst[u] = ((q * HXW_WIN + w_) * HX_PSTRIDE + cg * 16) | (w_ << 24);
+            if (gw < p.B) ssrc[u] = p.in + (size_t)gw * p.in_win_stride + (size_t)q * CIN + cg * 8;
+        }
+    }
+    u32x4 sv[NIT][2];                                      // staged values in flight (inline-asm loads)
+    auto stage_issue = [&](int ch) {
+#pragma unroll
+        for (int u = 0; u < NIT; ++u) {
+            if (!slot_live(u)) continue;
+            const float *src = ssrc[u] ? ssrc[u] + ch * BX_CC : p.in;
+            asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(sv[u][0]) : "v"(src) : "memory");
+            asm volatile("global_load_dwordx4 %0, %1, off offset:16" : "=v"(sv[u][1]) : "v"(src) : "memory");
+        }
+    };
+    auto split_store = [&](const float (&v)[8], int dsto, float in_scale) {
+        unsigned short h[2][8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) amt_split_f16<false>(v[e] * in_scale, h[0][e], h[1][e]);
+        char *dst = in_lds + dsto;
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) {
+            uint4 pk;
+            pk.x = h[pl][0] | ((unsigned)h[pl][1] << 16);
+            pk.y = h[pl][2] | ((unsigned)h[pl][3] << 16);
+            pk.z = h[pl][4] | ((unsigned)h[pl][5] << 16);
+            pk.w = h[pl][6] | ((unsigned)h[pl][7] << 16);
+            *reinterpret_cast<uint4 *>(dst + pl * 32) = pk;
+        }
+    };
+    issue(0);
+    if constexpr (PREFETCH) stage_issue(0);
+    if (tid < HXW_WIN) {
+        const int sa = hx_scale_exp(my_amax);
+        win_is[tid] = __uint_as_float((unsigned)(127 + sa) << 23);                 // 2^sa
+        win_os[tid] = __uint_as_float((unsigned)(127 - (sa + hs.sw)) << 23);       // 2^-(sa + sw)
+        win_max[tid] = 0;
+    }
+    if (tid < 128) bnp[tid] = my_bn;
+    for (int ch = 0; ch < NCHUNK; ++ch) {
+        __syncthreads();                                   // the previous chunk's tile has been read
+        // chunk 0: wait here; later chunks: the values landed with the wait that closed the previous chunk's last group
+        if constexpr (!PREFETCH) stage_issue(ch);
+        if (ch == 0 || !PREFETCH) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int u = 0; u < NIT; ++u) asm volatile("" : "+v"(sv[u][0]), "+v"(sv[u][1]));   // tie the values to the wait
+#pragma unroll
+        for (int u = 0; u < NIT; ++u) {
+            if (sdst[u] < 0 || !slot_live(u)) continue;
+            float v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = ssrc[u] ? __uint_as_float(sv[u][e >> 2][e & 3]) : 0.f;
+            split_store(v, sdst[u] & 0xFFFFFF, win_is[sdst[u] >> 24]);
+        }
+        if (ch == 0) {                                    // weight group 0 -> LDS, group 1 -> prefetch registers
+#pragma unroll
+            for (int i = 0; i < WPT; ++i) reinterpret_cast<u32x4 *>(wbuf)[tid + i * NT] = wp[i];
+            if (NGT > 1) issue(1);
+        }
+        __syncthreads();                                   // tile staged, weight group parked
+        if (tsp && tid == 0 && ch == 0) tsp[1] = wall_clock64();
+        union U { uint4 u; f16x8 v; };
+#pragma unroll 1
+        for (int g = 0; g < NG; ++g) {                     // g = tap row dy
+            const int gg = ch * NG + g;
+            const uint4 *wb = wbuf + (gg & 1) * GV4 + lane;          // [tap pair][plane][N-subtile][64 lanes]
+            const int goff = abase + ((g - PAD_T) * p.W - PAD_L) * HXW_PPITCH;
+            unsigned lv[MS], any = 0;                                // pairs of this row each subtile needs (wave-uniform)
+#pragma unroll
+            for (int ms = 0; ms < MS; ++ms) { lv[ms] = (rowm[ms] >> g) & 1u ? pm[ms] : 0u; any |= lv[ms]; }
+            if (PREFETCH && g == NG - 1 && ch + 1 < NCHUNK) stage_issue(ch + 1);   // next chunk's tile: flies under this row's matrix work
+            U a[BATCH][2];                                           // A fragments [subtile][plane]
+            U b[2][2];                                               // [N-subtile][plane]
+#pragma unroll
+            for (int tp = 0; tp < NTP; ++tp) {
+                if (!((any >> tp) & 1u)) continue;
+#pragma unroll
+                for (int ns = 0; ns < 2; ++ns)
+#pragma unroll
+                    for (int pl = 0; pl < 2; ++pl) b[ns][pl].u = wb[((tp * 2 + pl) * 2 + ns) * 64];
+#pragma unroll
+                for (int m0 = 0; m0 < MS; m0 += BATCH) {
+#pragma unroll
+                    for (int mb = 0; mb < BATCH; ++mb) {
+                        const int ms = m0 + mb;
+                        if (!((lv[ms] >> tp) & 1u)) continue;
+                        const int off = ((mlane[ms] >> tp) & 1u) ? goff + (ms * HXW_NWAVE + 2 * tp) * HXW_PPITCH : zero_off;
+                        a[mb][0].u = *reinterpret_cast<const uint4 *>(in_lds + off);
+                        a[mb][1].u = *reinterpret_cast<const uint4 *>(in_lds + off + 32);
+                    }
+#pragma unroll
+                    for (int mb = 0; mb < BATCH; ++mb) {
+                        const int ms = m0 + mb;
+                        if (!((lv[ms] >> tp) & 1u)) continue;
+#pragma unroll
+                        for (int ns = 0; ns < 2; ++ns) {
+                            lo[ms][ns] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[mb][1].v, b[ns][0].v, lo[ms][ns], 0, 0, 0);
+                            hi[ms][ns] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[mb][0].v, b[ns][0].v, hi[ms][ns], 0, 0, 0);
+                            lo[ms][ns] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[mb][0].v, b[ns][1].v, lo[ms][ns], 0, 0, 0);
+                        }
+                    }
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (gg + 1 < NGT) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // group gg+1 (and a requested tile) has landed in registers
+                u32x4 *dst = reinterpret_cast<u32x4 *>(wbuf + ((gg + 1) & 1) * GV4);
+#pragma unroll
+                for (int i = 0; i < WPT; ++i) dst[tid + i * NT] = wp[i];
+                if (gg + 2 < NGT) issue(gg + 2);
+            }
+            if (g + 1 < NG) __syncthreads();
+        }
+    }
+    // ---- epilogue: as conv_f16x3s_kernel's, one subtile (16 windows of one position) at a time ---------------------
+    if (tsp && tid == 0) tsp[2] = wall_clock64();
+    __syncthreads();                                       // the last tile has been read: its LDS becomes the waves' patches
+    float *tb = reinterpret_cast<float *>(in_lds) + wid * (16 * HX_TPITCH);
+    const int c4 = (lane & 7) * 4;
+    const float4 s2v = *reinterpret_cast<const float4 *>(bnp + 64 + c4), t2v = *reinterpret_cast<const float4 *>(bnp + 96 + c4);
+    // D of a 16x16 MFMA: lane l holds rows (windows) 4*(l/16) + e, column l%16
+    float osc[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) osc[e] = win_os[4 * (lane >> 4) + e];
+    float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f), s4 = w4, t4 = w4;
+    if (p.sc1) {
+        w4 = *reinterpret_cast<const float4 *>(p.sc1_w + cout_off + c4);
+        s4 = *reinterpret_cast<const float4 *>(p.sc1_s + cout_off + c4);
+        t4 = *reinterpret_cast<const float4 *>(p.sc1_t + cout_off + c4);
+    }
+    float rmax[2] = {0.f, 0.f};                            // this lane's two rows: windows lane / 8 and lane / 8 + 8
+#pragma unroll
+    for (int ms = 0; ms < MS; ++ms) {
+        const int q = wid + HXW_NWAVE * ms;
+        if (q >= npos) continue;
+#pragma unroll
+        for (int ns = 0; ns < 2; ++ns) {
+            const float s1 = bnp[ns * 16 + (lane & 15)], t1 = bnp[32 + ns * 16 + (lane & 15)];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int row = 4 * (lane >> 4) + e;
+                const float z = (hi[ms][ns][e] + lo[ms][ns][e] * (1.0f / HX_LSCALE)) * osc[e];
+                tb[row * HX_TPITCH + ns * 16 + (lane & 15)] = sigmoidf_(z * s1 + t1);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int row = (lane >> 3) + 8 * i, gw = win0 + row;
+            float4 v = *reinterpret_cast<const float4 *>(tb + row * HX_TPITCH + c4);
+            if (gw >= p.B) continue;                       // absent window: nothing is stored
+            if (p.sc) {
+                const float4 scv = *reinterpret_cast<const float4 *>(p.sc + (size_t)gw * p.sc_win_stride + (size_t)q * p.cout_total + cout_off + c4);
+                v.x = (v.x + scv.x) * s2v.x + t2v.x;
+                v.y = (v.y + scv.y) * s2v.y + t2v.y;
+                v.z = (v.z + scv.z) * s2v.z + t2v.z;
+                v.w = (v.w + scv.w) * s2v.w + t2v.w;
+            } else if (p.sc1) {
+                // rank-1 shortcut: BN(conv1x1(x)) of the one-channel input, formed here as proj_kernel forms it
+                const float x = p.sc1[(size_t)gw * p.sc1_win_stride + q];
+                v.x = (v.x + (fmaf(x, w4.x, 0.f) * s4.x + t4.x)) * s2v.x + t2v.x;
+                v.y = (v.y + (fmaf(x, w4.y, 0.f) * s4.y + t4.y)) * s2v.y + t2v.y;
+                v.z = (v.z + (fmaf(x, w4.z, 0.f) * s4.z + t4.z)) * s2v.z + t2v.z;
+                v.w = (v.w + (fmaf(x, w4.w, 0.f) * s4.w + t4.w)) * s2v.w + t2v.w;
+            }
+            rmax[i] = fmaxf(rmax[i], fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+            *reinterpret_cast<float4 *>(p.out + (size_t)gw * p.out_win_stride + (size_t)q * p.cout_total + cout_off + c4) = v;
+        }
+    }
+    // max |output| per window for the next layer's operand scaling
+    if (hs.amax_out) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            float m = rmax[i];                              // eight lanes share a row
+            m = fmaxf(m, __shfl_xor(m, 1, 64));
+            m = fmaxf(m, __shfl_xor(m, 2, 64));
+            m = fmaxf(m, __shfl_xor(m, 4, 64));
+            if ((lane & 7) == 0) atomicMax(win_max + (lane >> 3) + 8 * i, __float_as_int(m));
+        }
+        __syncthreads();
+        if (tid < HXW_WIN && win0 + tid < p.B) atomicMax(reinterpret_cast<int *>(hs.amax_out) + win0 + tid, win_max[tid]);
     }
     if (tsp && tid == 0) tsp[3] = wall_clock64();
 }

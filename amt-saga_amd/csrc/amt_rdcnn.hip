@@ -34,6 +34,8 @@ struct ConvPlan {
     size_t lds = 0;
     int nslice = 1, cw = 0;    // output channels are computed in nslice slices (blockIdx.y) of cw channels
     bool masked = false;       // small-image form: whole images per workgroup, no halo
+    int wm_ms = 0;             // split-fp16 only, > 0: the window-major small-image form (conv_f16x3w_kernel) runs instead of
+    size_t wm_lds = 0;         //   the masked one, with wm_ms positions per wave and wm_lds bytes of LDS
     double eff = 0;            // useful fraction of the tile's positions
     void *w = nullptr;         // device weights (null: the variant is not built for this layer)
 };
@@ -228,6 +230,55 @@ static void choose_tile_h(ConvOp &c) {
     });
 }
 
+// AMT_CONV_TS diagnostic: phase split of a workgroup's life, four 100-MHz timestamps per workgroup of a split-fp16 launch
+static bool conv_ts_wanted() {
+    static const bool want = getenv("AMT_CONV_TS") != nullptr;
+    return want;
+}
+static int conv_ts_buffer(size_t nwg, unsigned long long **out) {
+    static unsigned long long *ts_dev = nullptr;
+    static size_t ts_cap = 0;
+    if (nwg > ts_cap) {
+        if (ts_dev) (void)hipFree(ts_dev);
+        ts_dev = nullptr; ts_cap = 0;
+        AMT_HIP_CHECK(hipMalloc(&ts_dev, nwg * 4 * sizeof(unsigned long long)));
+        ts_cap = nwg;
+    }
+    *out = ts_dev;
+    return AMT_OK;
+}
+// form: "masked0", "masked1" or "wmajor"; slots = workgroups the chip holds at once
+static int conv_ts_report(const ConvOp &c, const char *form, const unsigned long long *ts_dev, size_t nwg, int slots, hipStream_t st) {
+    AMT_HIP_CHECK(hipStreamSynchronize(st));
+    std::vector<unsigned long long> h(nwg * 4);
+    AMT_HIP_CHECK(hipMemcpy(h.data(), ts_dev, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    double a = 0, b = 0, e = 0;
+    unsigned long long t0 = ~0ull, t1 = 0;
+    for (size_t i = 0; i < nwg; ++i) {
+        a += (double)(h[4 * i + 1] - h[4 * i]); b += (double)(h[4 * i + 2] - h[4 * i + 1]);
+        e += (double)(h[4 * i + 3] - h[4 * i + 2]);
+        t0 = std::min(t0, h[4 * i]); t1 = std::max(t1, h[4 * i + 3]);
+    }
+    fprintf(stderr, "conv_ts k%dx%d cin%d %dx%d %s wgs %zu: start->first MFMA %.2f us, MFMA loop %.2f us, epilogue %.2f us; "
+                    "kernel %.1f us = %.2f workgroup lives per slot of %d\n",
+            c.kh, c.kw, c.cin, c.H, c.W, form, nwg, a / nwg / 100.0, b / nwg / 100.0, e / nwg / 100.0,
+            (double)(t1 - t0) / 100.0, (double)(t1 - t0) * slots / ((a + b + e)), slots);
+    return AMT_OK;
+}
+// The inference net's 4 x 16 layers on small images (the masked plan of choose_tile_h) take the window-major form
+// instead (amt_conv_f16x3.h): 3, 5 or 8 positions per wave.  AMT_CONV_WMAJOR=0, read here = when a net is created,
+// keeps them on the masked form (A/B measurements, tests/test_gpu_small_conv.py).
+static void choose_tile_w(ConvOp &c) {
+    ConvPlan &p = c.f16;
+    p.wm_ms = 0;
+    const char *e = getenv("AMT_CONV_WMAJOR");
+    if (e && e[0] == '0') return;
+    if (!p.masked || c.kh != 4 || c.kw != 16 || !(c.cin == 32 || c.cin == 64 || c.cin == 128)) return;
+    const int npos = c.H * c.W, ms = (npos + HXW_NWAVE - 1) / HXW_NWAVE;
+    p.wm_ms = ms <= 3 ? 3 : ms <= 5 ? 5 : 8;
+    p.wm_lds = hxw_lds_bytes<16>(npos);
+}
+
 template <int KH, int KW, int CIN, bool MASKED>
 static int launch_convs_t(const ConvOp &c, ConvParams p, const float *amax_in, float *amax_out, hipStream_t st) {
     auto kern = conv_f16x3s_kernel<KH, KW, CIN, MASKED>;
@@ -239,37 +290,42 @@ static int launch_convs_t(const ConvOp &c, ConvParams p, const float *amax_in, f
     }
     const unsigned grid = apply_plan(p, c.f16);
     HxScale hs{amax_in, amax_out, c.sw, nullptr};
-    static const bool want_ts = getenv("AMT_CONV_TS") != nullptr;      // diagnostic: phase split of a workgroup's life
-    static unsigned long long *ts_dev = nullptr;
-    static size_t ts_cap = 0;
     const size_t nwg = (size_t)grid * c.f16.nslice;
-    if (want_ts) {
-        if (nwg > ts_cap) {
-            if (ts_dev) (void)hipFree(ts_dev);
-            AMT_HIP_CHECK(hipMalloc(&ts_dev, nwg * 4 * sizeof(unsigned long long)));
-            ts_cap = nwg;
-        }
-        hs.ts = ts_dev;
-    }
+    if (conv_ts_wanted()) { const int rc = conv_ts_buffer(nwg, &hs.ts); if (rc != AMT_OK) return rc; }
     kern<<<dim3(grid, c.f16.nslice), 512, c.f16.lds, st>>>(p, static_cast<const uint4 *>(c.f16.w), hs);
     AMT_LAUNCH_CHECK();
-    if (want_ts) {
-        AMT_HIP_CHECK(hipStreamSynchronize(st));
-        std::vector<unsigned long long> h(nwg * 4);
-        AMT_HIP_CHECK(hipMemcpy(h.data(), ts_dev, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        double a = 0, b = 0, e = 0;
-        unsigned long long t0 = ~0ull, t1 = 0;
-        for (size_t i = 0; i < nwg; ++i) {
-            a += (double)(h[4 * i + 1] - h[4 * i]); b += (double)(h[4 * i + 2] - h[4 * i + 1]);
-            e += (double)(h[4 * i + 3] - h[4 * i + 2]);
-            t0 = std::min(t0, h[4 * i]); t1 = std::max(t1, h[4 * i + 3]);
-        }
-        fprintf(stderr, "conv_ts k%dx%d cin%d %dx%d masked%d wgs %zu: start->first MFMA %.2f us, MFMA loop %.2f us, epilogue %.2f us; "
-                        "kernel %.1f us = %.2f workgroup lives per slot of 512\n",
-                KH, KW, CIN, p.H, p.W, (int)MASKED, nwg, a / nwg / 100.0, b / nwg / 100.0, e / nwg / 100.0,
-                (double)(t1 - t0) / 100.0, (double)(t1 - t0) * 512.0 / ((a + b + e)));
-    }
+    if (hs.ts) return conv_ts_report(c, MASKED ? "masked1" : "masked0", hs.ts, nwg, 512, st);
     return AMT_OK;
+}
+// window-major small-image form: 16 windows x all positions x 32 output channels per workgroup, the N-slice in the low
+// bits of the 1-D workgroup id; one workgroup per CU
+template <int KH, int KW, int CIN, int MS>
+static int launch_convw_t(const ConvOp &c, ConvParams p, const float *amax_in, float *amax_out, hipStream_t st) {
+    auto kern = conv_f16x3w_kernel<KH, KW, CIN, MS>;
+    static bool attr_set = false;
+    if (!attr_set) {
+        AMT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
+        attr_set = true;
+    }
+    p.TH = p.H; p.TW = p.W; p.NWIN = HXW_WIN; p.tiles_h = p.tiles_w = 1;
+    const size_t nwg = (size_t)((p.B + HXW_WIN - 1) / HXW_WIN) * c.f16.nslice;
+    HxScale hs{amax_in, amax_out, c.sw, nullptr};
+    if (conv_ts_wanted()) { const int rc = conv_ts_buffer(nwg, &hs.ts); if (rc != AMT_OK) return rc; }
+    kern<<<dim3((unsigned)nwg), 64 * HXW_NWAVE, c.f16.wm_lds, st>>>(p, static_cast<const uint4 *>(c.f16.w), hs, c.f16.nslice);
+    AMT_LAUNCH_CHECK();
+    if (hs.ts) return conv_ts_report(c, "wmajor", hs.ts, nwg, 256, st);
+    return AMT_OK;
+}
+static int launch_convw(const ConvOp &c, const ConvParams &p, const float *amax_in, float *amax_out, hipStream_t st) {
+    if (!c.f16.w || c.f16.cw != 32 || c.kh != 4 || c.kw != 16 || c.H * c.W > 8 * c.f16.wm_ms) return AMT_E_UNSUPPORTED;
+#define HXW_CASE(CI, MS)                                                                   \
+    if (c.cin == CI && c.f16.wm_ms == MS) return launch_convw_t<4, 16, CI, MS>(c, p, amax_in, amax_out, st);
+    HXW_CASE(32, 3) HXW_CASE(32, 5) HXW_CASE(32, 8)
+    HXW_CASE(64, 3) HXW_CASE(64, 5) HXW_CASE(64, 8)
+    HXW_CASE(128, 3) HXW_CASE(128, 5) HXW_CASE(128, 8)
+#undef HXW_CASE
+    return AMT_E_UNSUPPORTED;
 }
 template <int KH, int KW>
 static int launch_convh_k(const ConvOp &c, const ConvParams &p, const float *amax_in, float *amax_out, hipStream_t st) {
@@ -284,6 +340,7 @@ static int launch_convh_k(const ConvOp &c, const ConvParams &p, const float *ama
     return AMT_E_UNSUPPORTED;
 }
 static int launch_convh(const ConvOp &c, const ConvParams &p, const float *amax_in, float *amax_out, hipStream_t st) {
+    if (c.f16.wm_ms > 0) return launch_convw(c, p, amax_in, amax_out, st);
     if (c.kh == 4 && c.kw == 16) return launch_convh_k<4, 16>(c, p, amax_in, amax_out, st);
     if (c.kh == 4 && c.kw == 2) return launch_convh_k<4, 2>(c, p, amax_in, amax_out, st);
     if (c.kh == 2 && c.kw == 2) return launch_convh_k<2, 2>(c, p, amax_in, amax_out, st);
@@ -387,7 +444,7 @@ static ConvImpl conv_impl(const ConvOp &c, int mode) {
 static bool impl_is_fft(ConvImpl impl) { return impl == IMPL_FFT_ROW || impl == IMPL_FFT_PACKED; }
 // the epilogue can form a 1 x 1 projection of the one-channel network input itself (ConvParams::sc1, FcEpilogue::sc1)
 static bool impl_forms_rank1_shortcut(ConvImpl impl, const ConvOp &c) {
-    return impl == IMPL_FFT_ROW || (impl == IMPL_F16X3 && !c.f16.masked);
+    return impl == IMPL_FFT_ROW || (impl == IMPL_F16X3 && (!c.f16.masked || c.f16.wm_ms > 0));
 }
 // the kernel leaves max |output| per window for the split-fp16 scaling of its consumer
 static bool impl_writes_amax(ConvImpl impl) {
@@ -494,6 +551,7 @@ static int build_conv_variants(amt_rdcnn *n, ConvOp &c, const float *kern) {
 
     c.f16.cw = 32; c.f16.nslice = fo / 32;                // 32-wide N-slices
     choose_tile_h(c);
+    choose_tile_w(c);
     float wmax = 0.f;
     bool finite = true;
     for (size_t q = 0; q < (size_t)ntap * C * fo; ++q) {
