@@ -85,6 +85,11 @@ PROTOTYPES = {
                                C.c_int, C.c_size_t, vp]),
     'amt_stft_mag_ragged': (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_longlong, vp, vp, vp, vp,
                                       C.c_longlong, C.c_int, vp]),
+    'amt_resampler_create': (C.c_int, [C.POINTER(vp), C.c_int, C.c_int]),
+    'amt_resampler_destroy': (C.c_int, [vp]),
+    'amt_resample_length': (C.c_longlong, [vp, C.c_longlong]),
+    'amt_resample_ragged': (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_longlong, vp, vp, C.c_longlong,
+                                      vp]),
     'amt_istft': (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp,
                             C.c_size_t, vp]),
     'amt_window_max': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp]),

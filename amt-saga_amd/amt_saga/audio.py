@@ -892,3 +892,124 @@ class audio_complete:
             raise NotImplementedError('only FLAC output is provided')
         from . import flac as _flac
         _flac.save_float(np.asarray(self.wf), filename, sr=self.sr, bps=24)
+
+
+# ======================================================================================
+# Sample-rate conversion (the `sr=` of librosa.load, util_audio.py:962-964)
+# ======================================================================================
+def _check_rates(sr_in, sr_out):
+    if int(sr_in) != sr_in or int(sr_out) != sr_out or int(sr_in) <= 0 or int(sr_out) <= 0:
+        raise ValueError('resample: sample rates must be positive integers. Got: %r -> %r' % (sr_in, sr_out))
+    return int(sr_in), int(sr_out)
+
+
+def _check_signal(s):
+    """(samples, channels) of a waveform [n] or [n, channels], from its shape alone."""
+    shape = tuple(s.shape) if hasattr(s, 'shape') else np.asarray(s).shape
+    if len(shape) not in (1, 2):
+        raise ValueError('Invalid Input shape. Expected: a waveform [n] or [n, channels] . Got: %s' % (shape,))
+    n, channels = shape[0], (shape[1] if len(shape) == 2 else 1)
+    if n == 0:
+        raise ValueError('Invalid Input shape. Expected: at least one sample . Got: an empty signal')
+    if not 1 <= channels <= Resampler.MAX_CHANNELS:
+        raise ValueError('Invalid Input shape. Expected: 1 to %d channels . Got: %d' % (Resampler.MAX_CHANNELS, channels))
+    return int(n), int(channels)
+
+
+class Resampler:
+    """Signals at sr_in -> signals at sr_out on the device (amt_resample_ragged): rational polyphase resampling with a
+    Kaiser-windowed sinc (32 zero crossings per side, beta 10, rolloff 0.88), zero phase -- output n sits at time
+    n / sr_out.  L / M = sr_out / sr_in reduced; `taps` = the most input samples one output uses, 2 Z R / L + 1 with
+    R = max(L, M).  Channels ([n, channels], interleaved) are averaged by the kernel, as librosa.load's mono=True does.
+    Every argument error is a ValueError raised before the library or the GPU is touched; the coefficient table is
+    built (amt_resampler_create) at the first call."""
+    Z, R_MAX, MAX_CHANNELS, MAX_SIGNALS = 32, 2048, 8, 65535
+
+    def __init__(self, sr_in, sr_out):
+        self.sr_in, self.sr_out = _check_rates(sr_in, sr_out)
+        if self.sr_in == self.sr_out:
+            raise ValueError('Resampler: equal rates (%d): pass the signal through (audio.resample does)' % self.sr_in)
+        g = math.gcd(self.sr_in, self.sr_out)
+        self.L, self.M = self.sr_out // g, self.sr_in // g
+        R = max(self.L, self.M)
+        if R > self.R_MAX:
+            raise ValueError('Resampler: %d -> %d reduces to %d / %d; the larger side may be at most %d'
+                             % (self.sr_in, self.sr_out, self.L, self.M, self.R_MAX))
+        self.taps = 2 * self.Z * R // self.L + 1
+        self._handles = {}                                          # device index -> amt_resampler *
+
+    def out_len(self, n_in):
+        """ceil(n_in L / M) (amt_resample_length)."""
+        return -((-int(n_in) * self.L) // self.M)
+
+    def _handle(self):
+        dev = torch.cuda.current_device()
+        if dev not in self._handles:
+            h = C.c_void_p()
+            _lib.check(_lib.load().amt_resampler_create(C.byref(h), self.sr_in, self.sr_out))
+            self._handles[dev] = h
+        return self._handles[dev]
+
+    def __del__(self):
+        try:
+            lib = _lib.load()
+            for h in self._handles.values():
+                lib.amt_resampler_destroy(h)
+        except Exception:                                           # interpreter shutdown: the library may be gone
+            pass
+        self._handles = {}
+
+    def __call__(self, signals, out=None):
+        """signals: a waveform [n], an [n, channels] array, or a list of those (one channel count per call); numpy or
+        torch, host or device.  Returns one float32 1-d device tensor per input (a list for a list), views of ONE
+        packed buffer -- `out` when given (a contiguous float32 device tensor of at least the summed lengths)."""
+        single = not isinstance(signals, (list, tuple))
+        items = [signals] if single else list(signals)
+        if not items:
+            raise ValueError('Invalid Input shape. Expected: at least one signal . Got: an empty list')
+        if len(items) > self.MAX_SIGNALS:
+            raise ValueError('Invalid Input shape. Expected: at most %d signals a call . Got: %d'
+                             % (self.MAX_SIGNALS, len(items)))
+        shapes = [_check_signal(s) for s in items]
+        channels = shapes[0][1]
+        if any(c != channels for _, c in shapes):
+            raise ValueError('Invalid Input shape. Expected: one channel count per call . Got: %s'
+                             % sorted({c for _, c in shapes}))
+        in_len = np.asarray([n for n, _ in shapes], np.int64)
+        out_len = np.asarray([self.out_len(n) for n in in_len], np.int64)
+        in_base = np.concatenate([[0], np.cumsum(in_len * channels)[:-1]]).astype(np.int64)
+        out_base = np.concatenate([[0], np.cumsum(out_len)[:-1]]).astype(np.int64)
+        total = int(out_len.sum())
+        if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32
+                                    and out.dim() == 1 and out.is_contiguous() and out.numel() >= total):
+            raise ValueError('Invalid Input shape. Expected: out = a contiguous float32 device tensor of >= %d . Got: %s'
+                             % (total, tuple(out.shape) if hasattr(out, 'shape') else type(out).__name__))
+        lib = _lib.load()
+        flat = [to_dev(s).reshape(-1) for s in items]
+        buf = flat[0] if len(flat) == 1 else torch.cat(flat)
+        if out is None:
+            out = empty((total,))
+        meta = to_dev(np.stack([in_base, in_len, out_base]), torch.int64)
+        _lib.check(lib.amt_resample_ragged(self._handle(), ptr(buf), ptr(meta[0]), ptr(meta[1]), len(items), channels,
+                                           buf.numel(), int(out_len.max()), ptr(out), ptr(meta[2]), out.numel(),
+                                           stream_ptr()))
+        views = [out[b:b + n] for b, n in zip(out_base.tolist(), out_len.tolist())]
+        return views[0] if single else views
+
+
+_RESAMPLERS = {}
+
+
+def resample(wf, sr_in, sr_out):
+    """librosa.load's sr= and mono=True (util_audio.py:962-964) for a loaded waveform [n] or [n, channels]: the float32
+    1-d device tensor of it at sr_out (Resampler, cached per rate pair).  Equal rates: to_dev(wf) itself, channels
+    averaged if there are any -- no filter runs."""
+    sr_in, sr_out = _check_rates(sr_in, sr_out)
+    if sr_in == sr_out:
+        _check_signal(wf)
+        w = to_dev(wf)
+        return w.mean(dim=1) if w.dim() == 2 else w
+    rs = _RESAMPLERS.get((sr_in, sr_out))
+    if rs is None:
+        rs = _RESAMPLERS[(sr_in, sr_out)] = Resampler(sr_in, sr_out)
+    return rs(wf)

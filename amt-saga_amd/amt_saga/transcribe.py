@@ -13,6 +13,8 @@ provide for the inference direction:
 
     python -m amt_saga.transcribe in.flac out.mid [--weights DIR] [--iters 5]
     python -m amt_saga.transcribe --songs a.flac b.flac ... --out-dir DIR [--slots N]     (song queue, one .mid per input)
+    --sr RATE (both modes): the model runs at RATE and every file is resampled to it from its own rate on the device
+    (audio.resample, the `sr=` of librosa.load, util_audio.py:962-964); without it the model is built at the file's rate.
 
 Weights: a directory with {timing_start,timing_end,pitch,instrument,velocity}.npz in the
 naming of amt_saga/rdcnn.py; without it the heads carry their seeded synthetic weights (the
@@ -59,8 +61,10 @@ def _make_loop(p, iters, heads, groups, weights_dir, guess):
 
 def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument', 'velocity'),
                groups=(0, 1, 2), weights_dir=None, guess='bank', loop=None, batch=1024, traversal='windows',
-               silence=1e-3):
-    """wf: float32 mono waveform at params.sr.  Returns (notes, events) where notes is the
+               silence=1e-3, sr=None):
+    """wf: float32 mono waveform at params.sr -- or, with `sr` given, a waveform [n] or [n, channels] at `sr`, resampled
+    to params.sr (and downmixed) on the device first (audio.resample): everything below, the length the note times are
+    computed from included, then sees the resampled signal.  Returns (notes, events) where notes is the
     merged list of dicts (pitch, program, velocity, start, end) and events the raw int32
     [iters, n_windows, 7] records.
     traversal='windows' (default): independent 50 %-overlapped windows, `iters` notes each, duplicates merged.
@@ -72,16 +76,21 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
     p = params or Hyperparams(N=2048)
     if loop is None:
         loop = _make_loop(p, iters, heads, groups, weights_dir, guess)
+    if sr is not None:
+        from .audio import resample
+        wf = resample(wf, sr, p.sr)                                # 1-d float32, on the device; sr == p.sr: a downmix
+    on_dev = isinstance(wf, torch.Tensor) and wf.is_cuda
     if traversal == 'song':
-        wf32 = np.ascontiguousarray(wf, dtype=np.float32)
+        wf32 = wf if on_dev else np.ascontiguousarray(wf, dtype=np.float32)      # (run_songs takes either)
         events, _ = loop.run_songs([wf32], max_notes=iters, silence=silence)
         evs = events.cpu().numpy()
         return ev.song_events_to_notes(evs, 1 + len(wf32) // p.H, len(wf32), sr=p.sr), evs
     L = p.H * (p.timing_frames - 1)
-    wins, starts = cut_windows(np.asarray(wf, dtype=np.float32), L, L // 2)
+    wf_dev = wf if on_dev else torch.from_numpy(np.ascontiguousarray(wf, dtype=np.float32)).cuda()
+    wins, starts = cut_windows(wf.cpu().numpy() if on_dev else np.asarray(wf, dtype=np.float32), L, L // 2)
     # song-level normalisers, as training.py:269-282 computes them: once per song, the maxima of the WHOLE song's
     # STFT and CQTs (one pass of the block-sum kernel over the song as a single signal), shared by every window
-    song_refs = loop.song_levels(torch.from_numpy(np.ascontiguousarray(wf, dtype=np.float32)).cuda())
+    song_refs = loop.song_levels(wf_dev)
     # the loop proper: host batches streamed through run_stream (copy of batch i+1 under the compute of batch i)
     chunks = [wins[b0:b0 + batch] for b0 in range(0, len(wins), batch)]
 
@@ -98,7 +107,9 @@ def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', '
                           groups=(0, 1, 2), weights_dir=None, guess='bank', loop=None, slots=8, silence=1e-3, poll=16,
                           pool_frames=None):
     """The song queue behind transcribe_songs (TranscriptionLoop.iter_song_queue): yields (index, notes, events) as
-    each song finishes, in finishing order.  wfs: a sequence or an iterator of mono float32 waveforms at params.sr."""
+    each song finishes, in finishing order.  wfs: a sequence or an iterator of mono float32 waveforms at params.sr; an
+    item may also be a (waveform [n] or [n, channels], sr) pair, which is resampled to params.sr on the device as it is
+    pulled (audio.resample)."""
     p = params or Hyperparams(N=2048)
     if loop is None:
         loop = _make_loop(p, iters, heads, groups, weights_dir, guess)
@@ -106,7 +117,11 @@ def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', '
 
     def feed():
         for i, wf in enumerate(wfs):
-            w = np.ascontiguousarray(wf, dtype=np.float32).reshape(-1)
+            if isinstance(wf, tuple):
+                from .audio import resample
+                w = resample(wf[0], wf[1], p.sr)
+            else:
+                w = np.ascontiguousarray(wf, dtype=np.float32).reshape(-1)
             lens[i] = len(w)
             yield w
     for i, evs in loop.iter_song_queue(feed(), slots, max_notes=iters, silence=silence, poll=poll,
@@ -140,11 +155,28 @@ def main_songs(argv):
     ap.add_argument('--weights', default=None)
     ap.add_argument('--iters', type=int, default=5)
     ap.add_argument('--guess', default='bank', choices=('bank', 'render'))
+    ap.add_argument('--sr', type=int, default=None,
+                    help='rate the model runs at; every file is resampled to it from its own rate (mixed rates allowed)')
     a = ap.parse_args(argv)
     os.makedirs(a.out_dir, exist_ok=True)
     stems = [os.path.splitext(os.path.basename(f))[0] for f in a.songs]
     if len(set(stems)) != len(stems):
         raise SystemExit('--songs: two inputs would write the same .mid (equal file names)')
+    if a.sr is not None:
+        if a.sr <= 0:
+            raise SystemExit('--sr: the rate must be positive')
+        queue = iter_transcribe_songs((flac.load_float(f) for f in a.songs), Hyperparams(N=2048, sr=a.sr), iters=a.iters,
+                                      weights_dir=a.weights, guess=a.guess, slots=a.slots)
+    else:
+        queue = _same_rate_queue(a, flac)
+    for i, notes, _ in queue:
+        out = os.path.join(a.out_dir, stems[i] + '.mid')
+        ev.write_midi(notes, out)
+        print('%d notes -> %s' % (len(notes), out))
+
+
+def _same_rate_queue(a, flac):
+    """--songs without --sr: the model at the first file's rate, every other file refused unless it has that rate."""
     first = flac.load_float(a.songs[0])
     sr0 = first[1]
 
@@ -155,11 +187,8 @@ def main_songs(argv):
                 raise SystemExit('%s: sample rate %d differs from the first file\'s %d; one queue runs at one rate'
                                  % (f, sr, sr0))
             yield wf.mean(axis=1) if wf.ndim > 1 else wf
-    for i, notes, _ in iter_transcribe_songs(load(), Hyperparams(N=2048, sr=sr0), iters=a.iters, weights_dir=a.weights,
-                                             guess=a.guess, slots=a.slots):
-        out = os.path.join(a.out_dir, stems[i] + '.mid')
-        ev.write_midi(notes, out)
-        print('%d notes -> %s' % (len(notes), out))
+    return iter_transcribe_songs(load(), Hyperparams(N=2048, sr=sr0), iters=a.iters, weights_dir=a.weights,
+                                 guess=a.guess, slots=a.slots)
 
 
 def main(argv=None):
@@ -176,12 +205,20 @@ def main(argv=None):
     ap.add_argument('--guess', default='bank', choices=('bank', 'render'))
     ap.add_argument('--traversal', default='windows', choices=('windows', 'song'),
                     help="'song': one sliding window per song with the residual kept (run_songs)")
+    ap.add_argument('--sr', type=int, default=None,
+                    help='rate the model runs at; the file is resampled to it from its own rate')
     a = ap.parse_args(argv)
     wf, sr = flac.load_float(a.infile)
-    if wf.ndim > 1:
-        wf = wf.mean(axis=1)                     # [n, channels] -> mono
-    notes, _ = transcribe(wf, Hyperparams(N=2048, sr=sr), iters=a.iters, weights_dir=a.weights, guess=a.guess,
-                          traversal=a.traversal)
+    if a.sr is None:                             # the model at the file's rate
+        if wf.ndim > 1:
+            wf = wf.mean(axis=1)                 # [n, channels] -> mono
+        model_sr, file_sr = sr, None
+    elif a.sr <= 0:
+        raise SystemExit('--sr: the rate must be positive')
+    else:                                        # the file at the model's rate: resampled and downmixed on the device
+        model_sr, file_sr = a.sr, sr
+    notes, _ = transcribe(wf, Hyperparams(N=2048, sr=model_sr), iters=a.iters, weights_dir=a.weights, guess=a.guess,
+                          traversal=a.traversal, sr=file_sr)
     ev.write_midi(notes, a.outfile)
     print('%d notes -> %s' % (len(notes), a.outfile))
 

@@ -101,6 +101,37 @@ int amt_window_max(const float *spec, int B, int T, int ldf, size_t spec_stride,
                    float *out_max, void *stream);
 
 /* ------------------------------------------------------------------------ *
+ * Sample-rate conversion  (replaces the `sr=` argument and the mono=True downmix
+ * of librosa.load as called from audio_from_file, util_audio.py:962-964)
+ *
+ * Rational polyphase resampling with a Kaiser-windowed sinc, zero phase:
+ *   g = gcd(sr_in, sr_out), L = sr_out / g, M = sr_in / g, R = max(L, M), Z = 32, beta = 10, rolloff = 0.88
+ *   h[k] = L (rolloff / R) sinc(rolloff k / R) I0(beta sqrt(1 - (k / (Z R))^2)) / I0(beta),   integer |k| <= Z R
+ *   y[n] = sum over m with |n M - m L| <= Z R of x[m] h[n M - m L],   x[m] = 0 outside [0, n_in)
+ * Output n sits at time n / sr_out: no delay to compensate.
+ * ------------------------------------------------------------------------ */
+typedef struct amt_resampler amt_resampler;
+
+/* librosa.load(sr=...) (util_audio.py:962-964): the coefficient table of one rate pair, computed in double and
+ * uploaded as f32.  AMT_E_INVALID: a rate <= 0, equal rates (the filter would still low-pass: the caller passes the
+ * signal through instead), or R > 2048 (a table of more than 512 KB; 44100 against 48001). */
+int amt_resampler_create(amt_resampler **rs, int sr_in, int sr_out);
+int amt_resampler_destroy(amt_resampler *rs);
+/* samples librosa.load(sr=...) (util_audio.py:962-964) returns for n_in of them: ceil(n_in L / M) */
+long long amt_resample_length(const amt_resampler *rs, long long n_in);
+
+/* librosa.load(sr=..., mono=True) (util_audio.py:962-964) for n signals in ONE launch: signal i is
+ * in[in_base[i] .. + in_len[i] * channels), `channels` (1 .. 8) interleaved floats per sample, x[m] their mean; its
+ * amt_resample_length(in_len[i]) outputs go to out[out_base[i] ..).  in_base / in_len / out_base int64 [n]: device.
+ * in_floats / out_floats: sizes of the two buffers; max_out_len: the longest output (a host value: it sizes the
+ * grid).  A signal whose region leaves either buffer is left unwritten; nothing outside the output regions is
+ * written.  Every output is an f32 sum over its taps in ascending m: a signal's result depends on its samples alone
+ * and is bit-identical alone and inside a batch, at any base. */
+int amt_resample_ragged(const amt_resampler *rs, const float *in, const int64_t *in_base, const int64_t *in_len,
+                        int n, int channels, long long in_floats, long long max_out_len,
+                        float *out, const int64_t *out_base, long long out_floats, void *stream);
+
+/* ------------------------------------------------------------------------ *
  * Spectral subtraction  (replaces audio_complete.subtract, util_audio.py:221-259)
  * ------------------------------------------------------------------------ */
 typedef struct amt_subtract_args {
