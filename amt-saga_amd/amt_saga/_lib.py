@@ -92,6 +92,7 @@ PROTOTYPES = {
                                       vp]),
     'amt_istft': (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp,
                             C.c_size_t, vp]),
+    'amt_istft_ragged': (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, vp, vp, C.c_longlong, vp]),
     'amt_window_max': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp]),
     'amt_subtract': (C.c_int, [C.POINTER(SubtractArgs), vp]),
     'amt_subtract_span': (C.c_int, [C.POINTER(SubtractArgs), vp, C.c_int, vp]),
@@ -130,6 +131,7 @@ PROTOTYPES = {
     'amt_song_admit': (C.c_int, [C.POINTER(SongAdmitArgs), vp]),
     'amt_song_pack_events_slots': (C.c_int, [C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     'amt_song_slide': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    'amt_song_slide_keep': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     'amt_synth_windows': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, C.c_size_t, vp, vp]),
     'amt_sf2_synth_windows': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp,
                                         C.c_size_t, vp, vp]),

@@ -315,25 +315,28 @@ class TranscriptionLoop:
             self.iterate(b, it, events, window0)
         return events, b
 
-    def prepare_songs(self, songs, refs=None, spectra=None, song0=0):
+    def prepare_songs(self, songs, refs=None, spectra=None, song0=0, keep_residual=False):
         """Set-up of the song walk, once per batch of songs: a song_walk.SongState of one slot per song and ONE admission
         of song i into slot i (SongState.admit: the songs' STFT, training.py:265-269, the song-level constants, :269-282,
         the first windows, section(0, None, timing_frames), :284, the raw-sample table and the per-song integers).
         songs: sequence of 1-d float32 waveforms of more than n_fft / 2 samples.  refs: optional dict(ref_mag, ref_C_1,
         ref_C_inst, ref_C_foc) of [B] tensors instead of the constants computed here.  spectra: optional AudioBatch that
         already holds the songs' STFT (mag, ph, ref_max; songs of equal length, one per row) -- it is read, not changed.
-        song0: the index of the first song (state.slot_song).  Returns the state walk_songs() advances."""
+        song0: the index of the first song (state.slot_song).  keep_residual: every slide writes the outgoing half
+        window back into the pool (SongState), for walk_songs(residual=True) / state.residual_waves().  Returns the
+        state walk_songs() advances."""
         song_walk.check_walk(self)
-        return song_walk.prepare_songs(self, songs, refs=refs, spectra=spectra, song0=song0)
+        return song_walk.prepare_songs(self, songs, refs=refs, spectra=spectra, song0=song0, keep_residual=keep_residual)
 
-    def walk_songs(self, st, max_notes=8, silence=1e-3, poll=16, song0=0, max_steps=None):
+    def walk_songs(self, st, max_notes=8, silence=1e-3, poll=16, song0=0, max_steps=None, residual=False):
         """The steps of the song walk on a state from prepare_songs(); see run_songs().  max_steps: stop after that many
-        steps even if songs are unfinished (the state can be inspected, not resumed).  Returns events [steps, B, 9] int32
-        (device)."""
+        steps even if songs are unfinished (the state can be inspected, not resumed).  residual: see run_songs(); the
+        state must have been prepared with keep_residual.  Returns events [steps, B, 9] int32 (device)."""
         song_walk.check_walk(self, max_notes, silence)
-        return song_walk.walk_songs(st, max_notes, silence, poll=poll, song0=song0, max_steps=max_steps)
+        return song_walk.walk_songs(st, max_notes, silence, poll=poll, song0=song0, max_steps=max_steps,
+                                    residual=residual)
 
-    def run_songs(self, songs, max_notes=8, silence=1e-3, poll=16, song0=0, refs=None):
+    def run_songs(self, songs, max_notes=8, silence=1e-3, poll=16, song0=0, refs=None, residual=False):
         """The reference's own traversal (training.py:284, :296-328) with the predicted note where it has the gold
         note, for B songs at once: ONE live window of timing_frames frames per song, cut from the song's spectrogram
         (one STFT per song) and, whenever the predicted onset lies in its second half, slid by half a window with
@@ -354,12 +357,20 @@ class TranscriptionLoop:
 
         Returns (events [steps, B, 9] int32 device, SONG_EVENT_FIELDS; state): state.batch is the AudioBatch holding
         every song's last window (residual magnitudes, unit phases, maxima), state.offset / count / finished /
-        t_song the per-song integers, state.refs the song-level constants."""
-        song_walk.check_walk(self, max_notes, silence)
-        st = song_walk.prepare_songs(self, songs, refs=refs, song0=song0)
-        return song_walk.walk_songs(st, max_notes, silence, poll=poll, song0=song0), st
+        t_song the per-song integers, state.refs the song-level constants.
 
-    def iter_song_queue(self, songs, slots, max_notes=8, silence=1e-3, poll=16, pool_frames=None, on_finish=None):
+        residual=True: what the walk left of every song, to listen to (the reference dumps _full_window / _guessed /
+        _after_subtr .flac per subtraction, training.py:438-447).  Every slide then stores the half window it pushes
+        out back into the song's frames of the spectrogram pool (amt_song_slide_keep), and after the walk
+        state.residual is a list with one 1-d float32 device tensor of hop * (frames - 1) samples per song: the iSTFT
+        of the residual magnitudes times the song's own phases (util_audio.py:94-97), all songs in one launch
+        (amt_istft_ragged).  None stands for a song the walk did not finish.  Events are the same with and without."""
+        song_walk.check_walk(self, max_notes, silence)
+        st = song_walk.prepare_songs(self, songs, refs=refs, song0=song0, keep_residual=residual)
+        return song_walk.walk_songs(st, max_notes, silence, poll=poll, song0=song0, residual=residual), st
+
+    def iter_song_queue(self, songs, slots, max_notes=8, silence=1e-3, poll=16, pool_frames=None, on_finish=None,
+                        residual=False):
         """Continuous batching of the song walk: any number of songs of any lengths walked through `slots` live windows,
         a finished slot handed to the next song of the queue (the reference's unit of work is a dataset of songs, one
         song after the other per worker, training.py:623-634).  State, admission and step are run_songs' own
@@ -395,18 +406,23 @@ class TranscriptionLoop:
         Counters of the walk, updated at every poll point: state.stats, also left in self.queue_stats (the LAST queue
         started on this loop; a second queue replaces it) -- dict(steps, songs, admissions, waits = admissions that
         stopped at a song without a free region, bound = the step cap so far, slot_steps = step slots per kind
-        [detect, slide, forced slide, idle])."""
+        [detect, slide, forced slide, idle]).
+        residual=True: yields (song_index, events, residual) -- the song's residual waveform as run_songs(residual=True)
+        gives it for that song alone (1-d float32 device tensor).  At a poll point ONE residual_waves() call covers
+        every song found finished there; it is enqueued before their regions are released, on the walk's stream, so it
+        reads them ahead of the STFT of any later admission."""
         song_walk.check_walk(self, max_notes, silence, slots, pool_frames)
         return song_walk.iter_song_queue(self, songs, slots, max_notes, silence, poll=poll, pool_frames=pool_frames,
-                                         on_finish=on_finish)
+                                         on_finish=on_finish, residual=residual)
 
-    def run_song_queue(self, songs, slots, max_notes=8, silence=1e-3, poll=16, pool_frames=None, on_finish=None):
+    def run_song_queue(self, songs, slots, max_notes=8, silence=1e-3, poll=16, pool_frames=None, on_finish=None,
+                       residual=False):
         """iter_song_queue() run to its end.  Returns the list of the songs' records, events [k, 9] int32 host arrays,
-        in queue order."""
+        in queue order; with residual=True a list of (events, residual waveform) pairs."""
         out = {}
-        for idx, ev in self.iter_song_queue(songs, slots, max_notes=max_notes, silence=silence, poll=poll,
-                                            pool_frames=pool_frames, on_finish=on_finish):
-            out[idx] = ev
+        for item in self.iter_song_queue(songs, slots, max_notes=max_notes, silence=silence, poll=poll,
+                                         pool_frames=pool_frames, on_finish=on_finish, residual=residual):
+            out[item[0]] = tuple(item[1:]) if residual else item[1]
         return [out[i] for i in range(len(out))]
 
     def run_stream(self, host_batches, refs=None, window0=0):

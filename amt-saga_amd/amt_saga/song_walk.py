@@ -160,15 +160,19 @@ class SongState:
     samples, so the one free list `pool` governs both), the per-slot device integers, the song-level constants `refs`,
     the raw-sample table `seg` with the CQT heads' rows `wave` [slots, l_row], and the host's counters: steps, positions
     (of the longest song admitted), bound (the driver's step cap) and `stats` (see iter_song_queue).  Every slot starts
-    idle: finished, song -1, and normalisers of 1 for its discarded heads to divide by."""
+    idle: finished, song -1, and normalisers of 1 for its discarded heads to divide by.
+    keep_residual: every slide stores the half window it pushes out back into the song's pool frames
+    (amt_song_slide_keep), so that a FINISHED song's region of s_mag holds its residual spectrogram -- what every
+    subtraction left of it -- and residual_waves() can resynthesise it.  Off (the default), the pool is never written
+    after the admission's STFT."""
 
-    def __init__(self, lp, slots, pool_frames):
+    def __init__(self, lp, slots, pool_frames, keep_residual=False):
         if not lp._dev_ready:
             lp.setup_device()
         p, dev = lp.p, require_gpu()
         B, pool_frames = int(slots), int(pool_frames)
         tf, ldf = p.timing_frames, ldf_of(p.N)
-        self.lp, self.slots = lp, B
+        self.lp, self.slots, self.keep_residual = lp, B, bool(keep_residual)
         self.pool = FramePool(pool_frames)
         self.s_mag, self.s_ph = empty((pool_frames, ldf)), empty((pool_frames, ldf, 2))
         self.samples = empty((pool_frames * p.H,))
@@ -185,6 +189,8 @@ class SongState:
         self.l_row = (tf * p.H + 3) // 4 * 4
         self.wave = empty((B, self.l_row))
         self.song_of, self.region = [-1] * B, [None] * B           # host: the slot's song (-1: free) and pool region
+        self.frames = [0] * B                                      # host: frames of the slot's song
+        self.residual = None                                       # walk_songs(residual=True): one waveform per slot
         self.steps = self.positions = self.bound = 0
         self.stats = dict(steps=0, songs=0, admissions=0, waits=0, bound=0, slot_steps=[0, 0, 0, 0])
 
@@ -248,7 +254,7 @@ class SongState:
         mask = np.zeros(B, np.int32)
         for j, (slot, idx, _, f0) in enumerate(took):
             mask[slot] = 1 + j
-            self.song_of[slot], self.region[slot] = idx, int(f0)
+            self.song_of[slot], self.region[slot], self.frames[slot] = idx, int(f0), int(t_song[j])
         d_mask, d_seg = to_dev(mask, torch.int32), to_dev(seg_new, torch.int32)
         d_ts, d_song = to_dev(np.asarray(t_song, np.int32), torch.int32), \
             to_dev(np.asarray([idx for _, idx, _, _ in took], np.int32), torch.int32)
@@ -266,7 +272,39 @@ class SongState:
 
     def release(self, slot):
         self.pool.release(self.region[slot])
-        self.song_of[slot], self.region[slot] = -1, None
+        self.song_of[slot], self.region[slot], self.frames[slot] = -1, None, 0
+
+    def residual_waves(self, slots):
+        """What the walk left of the songs in `slots` (every one finished), as audio: the iSTFT of the residual
+        magnitudes their slides wrote back into the pool times the songs' own phases (util_audio.py:94-97; the
+        _after_subtr.flac of training.py:438-447 at song length), ONE amt_istft_ragged launch over their regions, on
+        the walk's stream.  Returns one 1-d float32 device tensor of hop * (t_song - 1) samples per slot, in the order
+        given.  ValueError: a state built without keep_residual, a free slot, or a song that is not finished (part of
+        it is still in the window -- e.g. after a max_steps cut -- so its residual is not defined)."""
+        if not self.keep_residual:
+            raise ValueError('residual_waves: the state was built without keep_residual')
+        slots = [int(b) for b in slots]
+        if not slots:
+            return []
+        fin = self.finished.cpu().numpy()
+        for b in slots:
+            if not 0 <= b < self.slots or self.region[b] is None:
+                raise ValueError('residual_waves: slot %d holds no song' % b)
+            if not fin[b]:
+                raise ValueError('residual_waves: the song in slot %d is not finished' % b)
+        lp, H = self.lp, self.lp.p.H
+        frames = [self.frames[b] for b in slots]
+        lens = [H * (t - 1) for t in frames]
+        base = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        out = empty((int(base[-1]),))
+        if base[-1] > 0:
+            d_fb = to_dev(np.asarray([self.region[b] for b in slots], np.int64), torch.int64)
+            d_tf = to_dev(np.asarray(frames, np.int32), torch.int32)
+            d_ob = to_dev(base[:-1].copy(), torch.int64)
+            _lib.check(lp.lib.amt_istft_ragged(self.batch.plan, ptr(self.s_mag), ptr(self.s_ph), ptr(d_fb), ptr(d_tf),
+                                               len(slots), max(frames), self.pool.frames, self.s_mag.shape[1], ptr(out),
+                                               ptr(d_ob), int(base[-1]), stream_ptr()))
+        return [out[int(a):int(a) + n] for a, n in zip(base[:-1], lens)]
 
     def step(self, max_notes, silence, row, song0=None):
         """One step of the walk for every slot: the loop's _step() (the head sequence of iterate()) with the walk's
@@ -302,26 +340,31 @@ class SongState:
             _lib.check(lib.amt_song_pack_events_slots(B, ptr(self.slot_song), self.steps, *note))
         else:
             _lib.check(lib.amt_song_pack_events(B, int(song0), self.steps, *note))
-        _lib.check(lib.amt_song_slide(ptr(b.mag), ptr(b.ph), B, tf, ldf, tf * ldf, ptr(self.s_mag), ptr(self.s_ph),
-                                      ptr(self.frame_base), ptr(self.t_song), ptr(self.slide), ptr(self.offset),
-                                      ptr(self.count), ptr(self.finished), sp))
+        slide = lib.amt_song_slide_keep if self.keep_residual else lib.amt_song_slide
+        _lib.check(slide(ptr(b.mag), ptr(b.ph), B, tf, ldf, tf * ldf, ptr(self.s_mag), ptr(self.s_ph),
+                         ptr(self.frame_base), ptr(self.t_song), ptr(self.slide), ptr(self.offset), ptr(self.count),
+                         ptr(self.finished), sp))
         b._fmax = None                                             # the slid windows' per-frame maxima are stale
         self.steps += 1
 
 
-def prepare_songs(lp, songs, refs=None, spectra=None, song0=0):
+def prepare_songs(lp, songs, refs=None, spectra=None, song0=0, keep_residual=False):
     """A fixed batch: as many slots as songs, a pool of exactly their frames, ONE admission of song i into slot i."""
     waves = [check_song(lp.p, s) for s in songs]
     if not waves:
         raise ValueError('run_songs: no songs given')
-    st = SongState(lp, len(waves), sum(1 + w.numel() // lp.p.H for w in waves))
+    st = SongState(lp, len(waves), sum(1 + w.numel() // lp.p.H for w in waves), keep_residual=keep_residual)
     st.admit([(i, int(song0) + i, w) for i, w in enumerate(waves)], refs=refs, spectra=spectra)
     return st
 
 
-def walk_songs(st, max_notes, silence, poll=16, song0=0, max_steps=None):
+def walk_songs(st, max_notes, silence, poll=16, song0=0, max_steps=None, residual=False):
     """Steps a fixed batch to its end (or max_steps) with nothing read back but finished.sum() every `poll` steps.
+    residual (a state with keep_residual): afterwards st.residual = one entry per slot, the finished songs' residual
+    waveforms from ONE residual_waves() call, None for a song the walk left unfinished.
     Returns events [steps, slots, 9] int32 (device), FINISHED records of idle slots included."""
+    if residual and not st.keep_residual:
+        raise ValueError('walk_songs: residual needs a state prepared with keep_residual')
     B = st.slots
     st.bound = st.positions * (int(max_notes) + 1)
     if max_steps is not None:
@@ -332,10 +375,16 @@ def walk_songs(st, max_notes, silence, poll=16, song0=0, max_steps=None):
         st.step(max_notes, silence, events[st.steps], song0)
         if st.steps % max(int(poll), 1) == 0 and int(st.finished.sum()) == B:
             break
+    if residual:
+        fin = st.finished.cpu().numpy()
+        done = [b for b in range(B) if fin[b] and st.region[b] is not None]
+        st.residual = [None] * B
+        for b, w in zip(done, st.residual_waves(done)):
+            st.residual[b] = w
     return events[:st.steps]
 
 
-def iter_song_queue(lp, songs, slots, max_notes, silence, poll=16, pool_frames=None, on_finish=None):
+def iter_song_queue(lp, songs, slots, max_notes, silence, poll=16, pool_frames=None, on_finish=None, residual=False):
     """Pulls and checks the first `slots` songs (no song at all is an error of the call, not of the first next()) and
     returns the generator of the queue's walk."""
     p, B, poll = lp.p, int(slots), max(int(poll), 1)
@@ -357,7 +406,7 @@ def iter_song_queue(lp, songs, slots, max_notes, silence, poll=16, pool_frames=N
         pool_frames = B * max(1 + w.numel() // p.H for _, w in ahead)
 
     def walk():
-        st = SongState(lp, B, pool_frames)
+        st = SongState(lp, B, pool_frames, keep_residual=residual)
         stats = lp.queue_stats = st.stats
         chunk = empty((poll, B, len(SONG_EVENT_FIELDS)), torch.int32)
         host_chunk = torch.empty(tuple(chunk.shape), dtype=torch.int32, pin_memory=True)
@@ -395,13 +444,16 @@ def iter_song_queue(lp, songs, slots, max_notes, silence, poll=16, pool_frames=N
                 records[idx].append(rows[rows[:, 2] != SONG_FINISHED].copy())
                 if host_fin[slot]:
                     done.append((slot, idx))
-            for slot, idx in done:
+            # the residual of every song found finished here, in ONE launch, enqueued BEFORE any region is released:
+            # on the walk's stream it runs ahead of the STFT a later admission writes into such a region
+            waves = st.residual_waves([slot for slot, _ in done]) if residual and done else []
+            for k, (slot, idx) in enumerate(done):
                 if on_finish is not None:
                     on_finish(idx, slot, st)
                 out = np.concatenate(records.pop(idx))
                 out[:, 1] = np.arange(len(out))
                 st.release(slot)
-                yield idx, out
+                yield (idx, out, waves[k]) if residual else (idx, out)
             admit()
             if st.steps > stats['bound']:
                 raise RuntimeError('run_song_queue: %d steps, past the bound of the admitted songs (%d)'

@@ -15,6 +15,8 @@ provide for the inference direction:
     python -m amt_saga.transcribe --songs a.flac b.flac ... --out-dir DIR [--slots N]     (song queue, one .mid per input)
     --sr RATE (both modes): the model runs at RATE and every file is resampled to it from its own rate on the device
     (audio.resample, the `sr=` of librosa.load, util_audio.py:962-964); without it the model is built at the file's rate.
+    --residual OUT.flac (with --traversal song) / --residual-dir DIR (with --songs): what the walk left of the song after
+    every subtraction, as 24-bit FLAC at the model's rate (the reference's _after_subtr.flac, training.py:438-447).
 
 Weights: a directory with {timing_start,timing_end,pitch,instrument,velocity}.npz in the
 naming of amt_saga/rdcnn.py; without it the heads carry their seeded synthetic weights (the
@@ -61,7 +63,7 @@ def _make_loop(p, iters, heads, groups, weights_dir, guess):
 
 def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument', 'velocity'),
                groups=(0, 1, 2), weights_dir=None, guess='bank', loop=None, batch=1024, traversal='windows',
-               silence=1e-3, sr=None):
+               silence=1e-3, sr=None, residual=False):
     """wf: float32 mono waveform at params.sr -- or, with `sr` given, a waveform [n] or [n, channels] at `sr`, resampled
     to params.sr (and downmixed) on the device first (audio.resample): everything below, the length the note times are
     computed from included, then sees the resampled signal.  Returns (notes, events) where notes is the
@@ -70,9 +72,14 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
     traversal='windows' (default): independent 50 %-overlapped windows, `iters` notes each, duplicates merged.
     traversal='song': the reference's own walk (training.py:296-328, TranscriptionLoop.run_songs) -- one window that
     lives on the song's spectrogram and slides by half, at most `iters` notes per position (max_notes), windows below
-    `silence` x the song's maximum skipped; events are then the [steps, 1, 9] song records and nothing needs merging."""
+    `silence` x the song's maximum skipped; events are then the [steps, 1, 9] song records and nothing needs merging.
+    residual=True (traversal='song' only; the independent windows have no song-level residual: ValueError): returns
+    (notes, events, residual) with the song's residual waveform at params.sr, a 1-d float32 device tensor of
+    hop * (frames - 1) samples (run_songs(residual=True)); None if the walk stopped before the song's end."""
     if traversal not in ('windows', 'song'):
         raise ValueError('Requested attribute does not exist')
+    if residual and traversal != 'song':
+        raise ValueError("transcribe: residual=True needs traversal='song'")
     p = params or Hyperparams(N=2048)
     if loop is None:
         loop = _make_loop(p, iters, heads, groups, weights_dir, guess)
@@ -82,9 +89,10 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
     on_dev = isinstance(wf, torch.Tensor) and wf.is_cuda
     if traversal == 'song':
         wf32 = wf if on_dev else np.ascontiguousarray(wf, dtype=np.float32)      # (run_songs takes either)
-        events, _ = loop.run_songs([wf32], max_notes=iters, silence=silence)
+        events, st = loop.run_songs([wf32], max_notes=iters, silence=silence, residual=residual)
         evs = events.cpu().numpy()
-        return ev.song_events_to_notes(evs, 1 + len(wf32) // p.H, len(wf32), sr=p.sr), evs
+        notes = ev.song_events_to_notes(evs, 1 + len(wf32) // p.H, len(wf32), sr=p.sr)
+        return (notes, evs, st.residual[0]) if residual else (notes, evs)
     L = p.H * (p.timing_frames - 1)
     wf_dev = wf if on_dev else torch.from_numpy(np.ascontiguousarray(wf, dtype=np.float32)).cuda()
     wins, starts = cut_windows(wf.cpu().numpy() if on_dev else np.asarray(wf, dtype=np.float32), L, L // 2)
@@ -105,9 +113,9 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
 
 def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', 'instrument', 'velocity'),
                           groups=(0, 1, 2), weights_dir=None, guess='bank', loop=None, slots=8, silence=1e-3, poll=16,
-                          pool_frames=None):
+                          pool_frames=None, residual=False):
     """The song queue behind transcribe_songs (TranscriptionLoop.iter_song_queue): yields (index, notes, events) as
-    each song finishes, in finishing order.  wfs: a sequence or an iterator of mono float32 waveforms at params.sr; an
+    each song finishes, in finishing order -- (index, notes, events, residual waveform) with residual=True.  wfs: a sequence or an iterator of mono float32 waveforms at params.sr; an
     item may also be a (waveform [n] or [n, channels], sr) pair, which is resampled to params.sr on the device as it is
     pulled (audio.resample)."""
     p = params or Hyperparams(N=2048)
@@ -124,22 +132,23 @@ def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', '
                 w = np.ascontiguousarray(wf, dtype=np.float32).reshape(-1)
             lens[i] = len(w)
             yield w
-    for i, evs in loop.iter_song_queue(feed(), slots, max_notes=iters, silence=silence, poll=poll,
-                                       pool_frames=pool_frames):
+    for item in loop.iter_song_queue(feed(), slots, max_notes=iters, silence=silence, poll=poll,
+                                     pool_frames=pool_frames, residual=residual):
+        i, evs = item[0], item[1]
         n = lens.pop(i)
         one = evs.copy()
         one[:, 0] = 0                                              # song_events_to_notes indexes scalars by song 0
         notes = ev.song_events_to_notes(one, 1 + n // p.H, n, sr=p.sr)
         for note in notes:
             note['song'] = i
-        yield i, notes, evs
+        yield (i, notes, evs, item[2]) if residual else (i, notes, evs)
 
 
 def transcribe_songs(wfs, params=None, slots=8, **kw):
     """A collection of songs through the song queue: `slots` live windows, a finished slot refilled with the next
     song.  Returns [(notes, events [k, 9]), ...] in input order; a song's notes are those of
-    transcribe(wf, traversal='song') for it alone (with `song` = its index)."""
-    out = {i: (notes, evs) for i, notes, evs in iter_transcribe_songs(wfs, params, slots=slots, **kw)}
+    transcribe(wf, traversal='song') for it alone (with `song` = its index).  residual=True: (notes, events, residual)."""
+    out = {item[0]: tuple(item[1:]) for item in iter_transcribe_songs(wfs, params, slots=slots, **kw)}
     return [out[i] for i in range(len(out))]
 
 
@@ -157,8 +166,14 @@ def main_songs(argv):
     ap.add_argument('--guess', default='bank', choices=('bank', 'render'))
     ap.add_argument('--sr', type=int, default=None,
                     help='rate the model runs at; every file is resampled to it from its own rate (mixed rates allowed)')
+    ap.add_argument('--residual-dir', default=None,
+                    help='write <stem>.residual.flac per song as it finishes: what the walk left after every subtraction, '
+                         '24-bit FLAC at the rate the model runs at (with --sr, the resampled rate)')
     a = ap.parse_args(argv)
     os.makedirs(a.out_dir, exist_ok=True)
+    keep = a.residual_dir is not None
+    if keep:
+        os.makedirs(a.residual_dir, exist_ok=True)
     stems = [os.path.splitext(os.path.basename(f))[0] for f in a.songs]
     if len(set(stems)) != len(stems):
         raise SystemExit('--songs: two inputs would write the same .mid (equal file names)')
@@ -166,17 +181,24 @@ def main_songs(argv):
         if a.sr <= 0:
             raise SystemExit('--sr: the rate must be positive')
         queue = iter_transcribe_songs((flac.load_float(f) for f in a.songs), Hyperparams(N=2048, sr=a.sr), iters=a.iters,
-                                      weights_dir=a.weights, guess=a.guess, slots=a.slots)
+                                      weights_dir=a.weights, guess=a.guess, slots=a.slots, residual=keep)
+        rate = a.sr
     else:
-        queue = _same_rate_queue(a, flac)
-    for i, notes, _ in queue:
+        queue, rate = _same_rate_queue(a, flac, keep)
+    for item in queue:
+        i, notes = item[0], item[1]
         out = os.path.join(a.out_dir, stems[i] + '.mid')
         ev.write_midi(notes, out)
         print('%d notes -> %s' % (len(notes), out))
+        if keep:
+            out = os.path.join(a.residual_dir, stems[i] + '.residual.flac')
+            flac.save_float(item[3].cpu().numpy(), out, sr=rate)
+            print('residual -> %s' % out)
 
 
-def _same_rate_queue(a, flac):
-    """--songs without --sr: the model at the first file's rate, every other file refused unless it has that rate."""
+def _same_rate_queue(a, flac, residual=False):
+    """--songs without --sr: the model at the first file's rate, every other file refused unless it has that rate.
+    Returns (the queue, that rate)."""
     first = flac.load_float(a.songs[0])
     sr0 = first[1]
 
@@ -188,7 +210,7 @@ def _same_rate_queue(a, flac):
                                  % (f, sr, sr0))
             yield wf.mean(axis=1) if wf.ndim > 1 else wf
     return iter_transcribe_songs(load(), Hyperparams(N=2048, sr=sr0), iters=a.iters, weights_dir=a.weights,
-                                 guess=a.guess, slots=a.slots)
+                                 guess=a.guess, slots=a.slots, residual=residual), sr0
 
 
 def main(argv=None):
@@ -207,7 +229,12 @@ def main(argv=None):
                     help="'song': one sliding window per song with the residual kept (run_songs)")
     ap.add_argument('--sr', type=int, default=None,
                     help='rate the model runs at; the file is resampled to it from its own rate')
+    ap.add_argument('--residual', default=None, metavar='OUT.flac',
+                    help='with --traversal song: write what the walk left of the song after every subtraction, 24-bit FLAC '
+                         'at the rate the model runs at (with --sr, the resampled rate)')
     a = ap.parse_args(argv)
+    if a.residual is not None and a.traversal != 'song':
+        raise SystemExit('--residual needs --traversal song (independent windows have no song-level residual)')
     wf, sr = flac.load_float(a.infile)
     if a.sr is None:                             # the model at the file's rate
         if wf.ndim > 1:
@@ -217,10 +244,16 @@ def main(argv=None):
         raise SystemExit('--sr: the rate must be positive')
     else:                                        # the file at the model's rate: resampled and downmixed on the device
         model_sr, file_sr = a.sr, sr
-    notes, _ = transcribe(wf, Hyperparams(N=2048, sr=model_sr), iters=a.iters, weights_dir=a.weights, guess=a.guess,
-                          traversal=a.traversal, sr=file_sr)
+    got = transcribe(wf, Hyperparams(N=2048, sr=model_sr), iters=a.iters, weights_dir=a.weights, guess=a.guess,
+                     traversal=a.traversal, sr=file_sr, residual=a.residual is not None)
+    notes = got[0]
     ev.write_midi(notes, a.outfile)
     print('%d notes -> %s' % (len(notes), a.outfile))
+    if a.residual is not None:
+        if got[2] is None:
+            raise SystemExit('--residual: the walk stopped before the end of the song')
+        flac.save_float(got[2].cpu().numpy(), a.residual, sr=model_sr)
+        print('residual -> %s' % a.residual)
 
 
 if __name__ == '__main__':

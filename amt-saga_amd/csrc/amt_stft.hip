@@ -21,6 +21,9 @@
 //    bins, so every store instruction covers whole 128-B lines.
 //  * |X| max is reduced wave -> block -> one atomicMax per block (non-negative
 //    floats order like their bit patterns).
+//  * this file is built with packed-FP32 instructions (-ffp-contract=fast, no NO_PK): every launch from it, the
+//    song-length amt_istft_ragged included, belongs on the ONE compute stream the walk uses and must not overlap the
+//    networks' MFMA kernels on a side stream.
 #include "amt_fft.h"
 
 struct amt_stft_plan {
@@ -333,17 +336,27 @@ __global__ __launch_bounds__(AMT_FFT_THREADS) void istft_kernel(
 // five workgroups per CU instead of two); frames are visited in increasing t, so the sums are
 // formed in the same order as in istft_kernel.
 // ---------------------------------------------------------------------------------
+// hops per workgroup of the streaming form for B signals of total_p padded samples: at most 32, halved down to 4 while
+// fewer than ~2048 workgroups would be in flight
+__host__ __device__ inline int istft_stream_gh(int total_p, int hop, size_t B) {
+    int GH = 32;
+    while (GH > 4 && (size_t)((total_p + GH * hop - 1) / (GH * hop)) * B < 2048) GH >>= 1;
+    return GH;
+}
+
+// istft_segment: segment blockIdx.x (GH hops) of ONE signal (T frames at mg / ph, Lout samples at out) by the calling
+// workgroup -- the body both kernels below share, so that a signal gives the same bits whether it is one row of a
+// batch of equal lengths (istft_stream_kernel) or one of n signals of unequal lengths in one pool
+// (istft_ragged_kernel).
 template <int N>
-__global__ __launch_bounds__(AMT_FFT_THREADS) void istft_stream_kernel(
-    const float *__restrict__ mag, const float2 *__restrict__ phase, int T, int ldf,
-    size_t spec_stride, float *__restrict__ wave_out, size_t wave_stride, int Lout,
+__device__ __forceinline__ void istft_segment(
+    const float *__restrict__ mg, const float2 *__restrict__ ph, int T, int ldf, float *__restrict__ out, int Lout,
     const float2 *__restrict__ tw_global, int center, int GH) {
     static_assert(AMT_FFT_THREADS == 256 && N % 1024 == 0, "hop = N/4 must be a multiple of the block");
     constexpr int HOP = N / 4, HPT = HOP / 256, NA = N / 256;
     __shared__ float2 buf[N];
     __shared__ float2 tw[N];
     const int tid = threadIdx.x;
-    const int b = blockIdx.y;
     for (int i = tid; i < N; i += AMT_FFT_THREADS) tw[i] = tw_global[i];
     __syncthreads();
     const int pad = center ? N / 2 : 0;
@@ -351,9 +364,6 @@ __global__ __launch_bounds__(AMT_FFT_THREADS) void istft_stream_kernel(
     const int p_lo = blockIdx.x * seg;
     const int t_base = p_lo / HOP - 3;               // frame slot 0: the first frame reaching p_lo
     const int nslots = GH + 3;
-    const float *mg = mag + (size_t)b * spec_stride;
-    const float2 *ph = phase ? phase + (size_t)b * spec_stride : nullptr;
-    float *out = wave_out + (size_t)b * wave_stride;
     const float inv_n = 1.0f / (float)N;
     float a[NA];
 #pragma unroll
@@ -427,6 +437,45 @@ __global__ __launch_bounds__(AMT_FFT_THREADS) void istft_stream_kernel(
             for (int i = NA - HPT; i < NA; ++i) a[i] = 0.f;
         }
     }
+}
+
+template <int N>
+__global__ __launch_bounds__(AMT_FFT_THREADS) void istft_stream_kernel(
+    const float *__restrict__ mag, const float2 *__restrict__ phase, int T, int ldf,
+    size_t spec_stride, float *__restrict__ wave_out, size_t wave_stride, int Lout,
+    const float2 *__restrict__ tw_global, int center, int GH) {
+    const int b = blockIdx.y;
+    istft_segment<N>(mag + (size_t)b * spec_stride, phase ? phase + (size_t)b * spec_stride : nullptr, T, ldf,
+                     wave_out + (size_t)b * wave_stride, Lout, tw_global, center, GH);
+}
+
+// n signals of unequal lengths in one launch, the mirror of stft_ragged_kernel: signal b = frames [frame_base[b],
+// + t_frames[b]) of the packed pool (magnitudes [pool_frames][ldf], unit phases [pool_frames][ldf] float2), its
+// hop * (t_frames[b] - 1) samples (center) written from out[out_base[b]].  Grid (segments of the longest signal, n): a
+// workgroup past its own signal's last segment returns before it loads the twiddles.  A signal of one frame has no
+// samples; a signal whose frames or samples do not lie inside the two buffers is skipped as a whole (the host checks
+// the same and raises).  Segment length: the pairing of frames in the transforms depends on it (the last frame of a
+// segment rides alone, an inner one with its neighbour, and the two round differently), so a length chosen from the
+// work of the whole launch would make a signal's bits depend on its company.  Every signal is therefore cut as
+// launch_istft cuts it for B = 1, T = t_frames[b] (istft_stream_gh, evaluated here from the device-resident length) and
+// is bit-identical to that call; the launch as a whole still fills the chip, n signals at a time.
+// A workgroup never leaves its signal: the frames it sums and the window sum-of-squares stop at
+// that signal's first and last frame, as they do for a row of istft_stream_kernel.
+template <int N>
+__global__ __launch_bounds__(AMT_FFT_THREADS) void istft_ragged_kernel(
+    const float *__restrict__ mag, const float2 *__restrict__ phase, const int64_t *__restrict__ frame_base,
+    const int32_t *__restrict__ t_frames, long long pool_frames, int ldf, float *__restrict__ out,
+    const int64_t *__restrict__ out_base, long long n_out, const float2 *__restrict__ tw_global, int max_frames) {
+    constexpr int HOP = N / 4;
+    const int b = blockIdx.y;
+    const int T = t_frames[b];
+    if (T < 2 || T > max_frames) return;                          // hop * (T - 1) = 0 samples / longer than the grid
+    const int Lout = HOP * (T - 1);
+    const int GH = istft_stream_gh(N / 2 + Lout, HOP, 1);         // what launch_istft takes for this signal alone
+    if ((long long)blockIdx.x * GH * HOP >= (long long)N / 2 + Lout) return;   // whole workgroup: past the last segment
+    const long long f0 = frame_base[b], o0 = out_base[b];
+    if (f0 < 0 || f0 + T > pool_frames || o0 < 0 || o0 + Lout > n_out) return;
+    istft_segment<N>(mag + (size_t)f0 * ldf, phase + (size_t)f0 * ldf, T, ldf, out + o0, Lout, tw_global, 1, GH);
 }
 
 // np.max over a window's [T][ldf] block --------------------------------------------
@@ -525,9 +574,7 @@ static int launch_istft(const amt_stft_plan *plan, const float *mag, const float
     if constexpr (N % 1024 == 0) {
         if (hop * 4 == N) {
             const int pad_ = plan->center ? N / 2 : 0;
-            int GHs = 32;
-            // keep >= ~2048 workgroups in flight when the batch is small
-            while (GHs > 4 && (size_t)((pad_ + Lout + GHs * hop - 1) / (GHs * hop)) * B < 2048) GHs >>= 1;
+            const int GHs = istft_stream_gh(pad_ + Lout, hop, B);   // >= ~2048 workgroups in flight when the batch is small
             dim3 grid_s((pad_ + Lout + GHs * hop - 1) / (GHs * hop), B);
             istft_stream_kernel<N><<<grid_s, AMT_FFT_THREADS, 0, st>>>(
                 mag, reinterpret_cast<const float2 *>(phase), T, ldf, spec_stride, out, wave_stride, Lout,
@@ -547,6 +594,24 @@ static int launch_istft(const amt_stft_plan *plan, const float *mag, const float
         plan->tw_dev, hop, plan->center, GH);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
+}
+
+template <int N>
+static int launch_istft_ragged(const amt_stft_plan *plan, const float *mag, const float *phase,
+                               const int64_t *frame_base, const int32_t *t_frames, int n, int max_frames,
+                               long long pool_frames, int ldf, float *out, const int64_t *out_base, long long n_out,
+                               hipStream_t st) {
+    if constexpr (N % 1024 == 0) {
+        // the shortest segment any signal takes (4 hops) bounds the segments of the longest
+        const int total_p = N / 2 + plan->hop * (max_frames - 1);
+        dim3 grid((total_p + 4 * plan->hop - 1) / (4 * plan->hop), n);
+        istft_ragged_kernel<N><<<grid, AMT_FFT_THREADS, 0, st>>>(
+            mag, reinterpret_cast<const float2 *>(phase), frame_base, t_frames, pool_frames, ldf, out, out_base, n_out,
+            plan->tw_dev, max_frames);
+        AMT_LAUNCH_CHECK();
+        return AMT_OK;
+    }
+    return AMT_E_UNSUPPORTED;
 }
 
 // ---------------------------------------------------------------------------------
@@ -684,6 +749,27 @@ int amt_istft(const amt_stft_plan *plan, const float *mag, const float *phase_ri
         case 2048: return launch_istft<2048>(plan, mag, phase_ri, B, T, ldf, spec_stride, wave_out, wave_stride, Lout, st);
         case 4096: return launch_istft<4096>(plan, mag, phase_ri, B, T, ldf, spec_stride, wave_out, wave_stride, Lout, st);
     }
+    return AMT_E_UNSUPPORTED;
+}
+
+int amt_istft_ragged(const amt_stft_plan *plan, const float *mag, const float *phase_ri, const int64_t *frame_base,
+                     const int32_t *t_frames, int n, int max_frames, long long pool_frames, int ldf, float *out,
+                     const int64_t *out_base, long long n_out, void *stream) {
+    if (!plan || !mag || !phase_ri || !frame_base || !t_frames || !out || !out_base || n <= 0 || n > 65535)
+        return AMT_E_INVALID;
+    if (plan->hop * 4 != plan->n_fft || !plan->center) return AMT_E_UNSUPPORTED;   // the streaming form's plans
+    const int F = plan->n_fft / 2 + 1;
+    if (ldf < F || max_frames <= 0 || pool_frames <= 0 || n_out < 0) return AMT_E_SHAPE;
+    if (max_frames < 2) return AMT_OK;                              // no signal has a sample
+    hipStream_t st = (hipStream_t)stream;
+#define AMT_RAGGED(NF) launch_istft_ragged<NF>(plan, mag, phase_ri, frame_base, t_frames, n, max_frames, pool_frames, ldf, \
+                                               out, out_base, n_out, st)
+    switch (plan->n_fft) {
+        case 1024: return AMT_RAGGED(1024);
+        case 2048: return AMT_RAGGED(2048);
+        case 4096: return AMT_RAGGED(4096);
+    }
+#undef AMT_RAGGED
     return AMT_E_UNSUPPORTED;
 }
 

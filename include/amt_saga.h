@@ -96,6 +96,22 @@ int amt_istft(const amt_stft_plan *plan, const float *mag, const float *phase_ri
               int B, int T, int ldf, size_t spec_stride, float *wave_out,
               size_t wave_stride, void *stream);
 
+/* amt_istft for n signals of unequal lengths in ONE launch, the mirror of amt_stft_mag_ragged -- the song-length
+ * audio_complete.wf of a residual spectrogram (util_audio.py:94-97), what the reference dumps to listen to what a
+ * subtraction left (training.py:438-447: _full_window / _guessed / _after_subtr .flac).  Signal i = frames
+ * [frame_base[i], + t_frames[i]) of the packed pool mag [pool_frames][ldf] / phase_ri [pool_frames][ldf] float2; its
+ * hop * (t_frames[i] - 1) samples (centred) go to out[out_base[i] ...] of a buffer of n_out floats (any alignment).
+ * frame_base / out_base int64 [n], t_frames int32 [n]: device.  max_frames = the longest t_frames (host value: it
+ * sizes the grid; a longer signal is left unwritten).  Every signal is cut into segments as amt_istft cuts it for
+ * B = 1, T = t_frames[i], with the same per-segment arithmetic: its samples are bit-identical to that call, whatever
+ * else the launch holds.  A signal of one frame has no samples.  A signal whose frames or samples leave either buffer
+ * is left unwritten; the caller checks regions beforehand.  Plans: the streaming form's, hop == n_fft / 4, n_fft in
+ * {1024, 2048, 4096}, center = 1; anything else is AMT_E_UNSUPPORTED.  Packed-FP32 code: launch it on the one compute
+ * stream, never beside the networks on a side stream. */
+int amt_istft_ragged(const amt_stft_plan *plan, const float *mag, const float *phase_ri, const int64_t *frame_base,
+                     const int32_t *t_frames, int n, int max_frames, long long pool_frames, int ldf, float *out,
+                     const int64_t *out_base, long long n_out, void *stream);
+
 /* np.max over each window's [T][ldf] block (audio_complete.ref_mag, :170-174) */
 int amt_window_max(const float *spec, int B, int T, int ldf, size_t spec_stride,
                    float *out_max, void *stream);
@@ -354,6 +370,18 @@ int amt_song_pack_events(int n, int song0, int step, const int32_t *kind, const 
 int amt_song_slide(float *w_mag, float *w_ph, int B, int T, int ldf, size_t w_stride, const float *s_mag,
                    const float *s_ph, const int64_t *frame_base, const int32_t *t_song, const int32_t *slide,
                    int32_t *offset, int32_t *count, int32_t *finished, void *stream);
+/* amt_song_slide that keeps what leaves the window: in addition, window rows r = 0 .. half - 1 of w_mag, as they are
+ * before the move (the residual of every subtraction, training.py:449), are stored into pool frames
+ * frame_base[b] + offset[b] + r of s_mag, for rows with offset[b] + r < t_song[b] only (later rows are zero padding in
+ * the window and another song's region in the pool).  Phases are not written back: the subtraction changes magnitudes
+ * only (util_audio.py:253-259).  The written frames [offset, offset + half) and the fetched ones [offset + T,
+ * offset + T + half) are disjoint, and the walk never reads a frame again once it has left the window.  Every frame
+ * below t_song leaves the window exactly once before `finished` is set, so a finished song's region [frame_base,
+ * + t_song) of s_mag is its residual spectrogram -- with s_ph, what util_audio.py:94-97 resynthesises and
+ * training.py:438-447 writes out (amt_istft_ragged).  Window and state end exactly as after amt_song_slide. */
+int amt_song_slide_keep(float *w_mag, float *w_ph, int B, int T, int ldf, size_t w_stride, float *s_mag,
+                        const float *s_ph, const int64_t *frame_base, const int32_t *t_song, const int32_t *slide,
+                        int32_t *offset, int32_t *count, int32_t *finished, void *stream);
 
 /* Song queue: a finished slot takes the next song (the reference walks one song after the other per worker,
  * training.py:623-634; here B slots do).  admit [B]: 0 = leave the slot alone, 1 + j = the slot takes the j-th of
