@@ -29,6 +29,23 @@ class SubtractArgs(C.Structure):
                 ('relu', C.c_int32), ('overkill_factor', C.c_float)]
 
 
+class StemArgs(C.Structure):
+    _fields_ = [('stems', vp), ('frame_base', vp), ('offset', vp), ('t_song', vp), ('program', vp), ('prog_group', vp),
+                ('n_prog', C.c_int32), ('G', C.c_int32), ('pool_frames', C.c_int64)]
+
+
+def stem_args(**fields):
+    """StemArgs (amt_stem_args of amt_subtract_span_stems) from keyword arguments: a tensor gives its device pointer,
+    None a NULL, a number itself."""
+    a = StemArgs()
+    known = {name for name, _ in StemArgs._fields_}
+    for k, v in fields.items():
+        if k not in known:
+            raise ValueError('Requested attribute does not exist')
+        setattr(a, k, v.data_ptr() if hasattr(v, 'data_ptr') else v)
+    return a
+
+
 class CqtArgs(C.Structure):
     _fields_ = [('wave', vp), ('src_frame', vp), ('bin0', vp), ('phase_inc', vp),
                 ('length', vp), ('ref', vp), ('coef', vp), ('out', vp), ('wave_stride', C.c_size_t),
@@ -96,6 +113,7 @@ PROTOTYPES = {
     'amt_window_max': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp]),
     'amt_subtract': (C.c_int, [C.POINTER(SubtractArgs), vp]),
     'amt_subtract_span': (C.c_int, [C.POINTER(SubtractArgs), vp, C.c_int, vp]),
+    'amt_subtract_span_stems': (C.c_int, [C.POINTER(SubtractArgs), vp, C.c_int, C.POINTER(StemArgs), vp]),
     'amt_compress_bands': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp,
                                      C.c_int, vp, vp, vp, C.c_int, vp]),
     'amt_compress_bands_fmax': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp,

@@ -161,14 +161,19 @@ class AudioBatch:
 
     # -- subtraction -----------------------------------------------------------------
     def subtract(self, guess_mag, guess_max=None, guess_index=None, guess_frames=None,
-                 offset_frames=None, normalize=True, relu=True, overkill_factor=1.0, span=False):
+                 offset_frames=None, normalize=True, relu=True, overkill_factor=1.0, span=False, stems=None):
         """audio_complete.subtract for every window (util_audio.py:221-259).
         guess_mag [G, Tg, ldf] f32 frame-major; guess_index [B] int32 selects the
         guess per window; offset_frames [B] int32 is the already-clamped first frame
         max(_seconds_to_frames(offset) - attack_compensation, 0).
         span=True (the caller vouches that mag is non-negative and unchanged since the compress_bands(fmax=True) that
         left its per-frame maxima): amt_subtract_span touches only the frames the guess covers; same residual, same
-        maxima, ~2.5 x fewer bytes.  Falls back to the whole-window kernel when the maxima are not there."""
+        maxima, ~2.5 x fewer bytes.  Falls back to the whole-window kernel when the maxima are not there.
+        stems: None, or a _lib.StemArgs (SongState.step builds it) -- the step also adds what it removed into the
+        instrument stems of the song walk (amt_subtract_span_stems).  Only the span step has that form: ValueError
+        without span / relu, RuntimeError when the per-frame maxima are not there (no fall-back to the whole window)."""
+        if stems is not None and not (span and relu):
+            raise ValueError('subtract: stems need the span subtraction (span=True, relu=True)')
         B, T = self.mag.shape[0], self.mag.shape[1]
         a = _lib.SubtractArgs()
         new_max = empty((B,))
@@ -196,7 +201,14 @@ class AudioBatch:
         # and torch's in-place version counter; the kernels behind this class write through raw pointers, which the counter
         # does not see -- those writers are this class's own and refresh or drop the cache themselves)
         if span and relu and fm is not None and fm[1] == (self.mag.data_ptr(), self.mag._version) and fm[0].shape == (B, T):
-            _lib.check(self.lib.amt_subtract_span(C.byref(a), ptr(fm[0]), int(guess_mag.shape[1]), stream_ptr()))
+            if stems is not None:
+                _lib.check(self.lib.amt_subtract_span_stems(C.byref(a), ptr(fm[0]), int(guess_mag.shape[1]),
+                                                            C.byref(stems), stream_ptr()))
+            else:
+                _lib.check(self.lib.amt_subtract_span(C.byref(a), ptr(fm[0]), int(guess_mag.shape[1]), stream_ptr()))
+        elif stems is not None:
+            raise RuntimeError('subtract: stems need the per-frame maxima of compress_bands(fmax=True) on this '
+                               'spectrogram; there is no whole-window form that keeps stems')
         else:
             self._fmax = None
             _lib.check(self.lib.amt_subtract(C.byref(a), stream_ptr()))

@@ -209,11 +209,14 @@ class TranscriptionLoop:
     def needs_phase(self):
         return self.iters > 1 and self.needs_wave
 
-    def _step(self, b, wave_fn, fmax, before_subtract=None):
+    def _step(self, b, wave_fn, fmax, before_subtract=None, stems=None):
         """One detect -> subtract step on the windows of `b` -- the head sequence both traversals share (iterate() for
         independent windows, run_songs() for the song walk).  wave_fn() returns what the CQT heads read as the windows'
         waveform; before_subtract(onset, end, guess_frames) runs after the guess has been selected and before it is
-        subtracted (run_songs decides there which songs detect).  Returns (onset, end, pitch, program, velocity)."""
+        subtracted (run_songs decides there which songs detect).  stems: None, or the _lib.StemArgs of the song
+        walk (SongState.step) -- its `program` is set here to the step's decided programs (NULL without the instrument
+        head: stem 0) and it goes to the subtraction (AudioBatch.subtract(stems=)).
+        Returns (onset, end, pitch, program, velocity)."""
         p = self.p
         B, T = b.mag.shape[0], b.mag.shape[1]
         st = stream_ptr()
@@ -274,9 +277,11 @@ class TranscriptionLoop:
         if before_subtract is not None:
             before_subtract(onset, end, gfr)
         if self.do_subtract:
+            if stems is not None:
+                stems.program = program.data_ptr() if program is not None else None
             if self.guess == 'bank':
                 b.subtract(self.bank_mag, self.bank_max, gidx, gfr, onset, normalize=True, relu=True,
-                           span=self.span_subtract)
+                           span=self.span_subtract, stems=stems)
             else:
                 notes = empty((B, 1, 5))
                 _lib.check(self.lib.amt_guess_notes(
@@ -288,7 +293,8 @@ class TranscriptionLoop:
                 else:
                     gw = synth.render_windows_device(notes, self.bank_len, p.sr, timbres=self.timbres)
                 g = AudioBatch(gw, p.N, p.H).stft(with_phase=False)
-                b.subtract(g.mag, g.ref_max, None, gfr, onset, normalize=True, relu=True, span=self.span_subtract)
+                b.subtract(g.mag, g.ref_max, None, gfr, onset, normalize=True, relu=True, span=self.span_subtract,
+                           stems=stems)
         if self.trace is not None:
             self.trace.append({k: v.clone() for k, v in tr.items()})
         return onset, end, pitch, program, velocity
@@ -315,7 +321,7 @@ class TranscriptionLoop:
             self.iterate(b, it, events, window0)
         return events, b
 
-    def prepare_songs(self, songs, refs=None, spectra=None, song0=0, keep_residual=False):
+    def prepare_songs(self, songs, refs=None, spectra=None, song0=0, keep_residual=False, keep_stems=False):
         """Set-up of the song walk, once per batch of songs: a song_walk.SongState of one slot per song and ONE admission
         of song i into slot i (SongState.admit: the songs' STFT, training.py:265-269, the song-level constants, :269-282,
         the first windows, section(0, None, timing_frames), :284, the raw-sample table and the per-song integers).
@@ -323,20 +329,23 @@ class TranscriptionLoop:
         ref_C_inst, ref_C_foc) of [B] tensors instead of the constants computed here.  spectra: optional AudioBatch that
         already holds the songs' STFT (mag, ph, ref_max; songs of equal length, one per row) -- it is read, not changed.
         song0: the index of the first song (state.slot_song).  keep_residual: every slide writes the outgoing half
-        window back into the pool (SongState), for walk_songs(residual=True) / state.residual_waves().  Returns the
-        state walk_songs() advances."""
-        song_walk.check_walk(self)
-        return song_walk.prepare_songs(self, songs, refs=refs, spectra=spectra, song0=song0, keep_residual=keep_residual)
+        window back into the pool (SongState), for walk_songs(residual=True) / state.residual_waves().  keep_stems:
+        every subtraction adds what it removed into the instrument stems (SongState), for walk_songs(stems=True) /
+        state.stem_waves().  Returns the state walk_songs() advances."""
+        song_walk.check_walk(self, stems=keep_stems)
+        return song_walk.prepare_songs(self, songs, refs=refs, spectra=spectra, song0=song0, keep_residual=keep_residual,
+                                       keep_stems=keep_stems)
 
-    def walk_songs(self, st, max_notes=8, silence=1e-3, poll=16, song0=0, max_steps=None, residual=False):
+    def walk_songs(self, st, max_notes=8, silence=1e-3, poll=16, song0=0, max_steps=None, residual=False, stems=False):
         """The steps of the song walk on a state from prepare_songs(); see run_songs().  max_steps: stop after that many
         steps even if songs are unfinished (the state can be inspected, not resumed).  residual: see run_songs(); the
-        state must have been prepared with keep_residual.  Returns events [steps, B, 9] int32 (device)."""
-        song_walk.check_walk(self, max_notes, silence)
+        state must have been prepared with keep_residual; stems likewise, with keep_stems.  Returns events [steps, B, 9]
+        int32 (device)."""
+        song_walk.check_walk(self, max_notes, silence, stems=stems)
         return song_walk.walk_songs(st, max_notes, silence, poll=poll, song0=song0, max_steps=max_steps,
-                                    residual=residual)
+                                    residual=residual, stems=stems)
 
-    def run_songs(self, songs, max_notes=8, silence=1e-3, poll=16, song0=0, refs=None, residual=False):
+    def run_songs(self, songs, max_notes=8, silence=1e-3, poll=16, song0=0, refs=None, residual=False, stems=False):
         """The reference's own traversal (training.py:284, :296-328) with the predicted note where it has the gold
         note, for B songs at once: ONE live window of timing_frames frames per song, cut from the song's spectrogram
         (one STFT per song) and, whenever the predicted onset lies in its second half, slid by half a window with
@@ -364,13 +373,23 @@ class TranscriptionLoop:
         out back into the song's frames of the spectrogram pool (amt_song_slide_keep), and after the walk
         state.residual is a list with one 1-d float32 device tensor of hop * (frames - 1) samples per song: the iSTFT
         of the residual magnitudes times the song's own phases (util_audio.py:94-97), all songs in one launch
-        (amt_istft_ragged).  None stands for a song the walk did not finish.  Events are the same with and without."""
-        song_walk.check_walk(self, max_notes, silence)
-        st = song_walk.prepare_songs(self, songs, refs=refs, song0=song0, keep_residual=residual)
-        return song_walk.walk_songs(st, max_notes, silence, poll=poll, song0=song0, residual=residual), st
+        (amt_istft_ragged).  None stands for a song the walk did not finish.  Events are the same with and without.
+
+        stems=True: what the walk took OUT of every song, split by instrument group (the reference's _guessed.flac
+        beside _after_subtr.flac, training.py:426-447) -- a subtractive transcriber is a source separator for free.
+        Every subtraction adds before - after of the frames it touches into state.stems[g] at the song's own pool
+        frames (amt_subtract_span_stems), g = the index in this loop's `groups` of the decided program's group (0
+        without the instrument head).  After the walk state.stem_audio is a list with one [G, hop * (frames - 1)]
+        float32 device tensor per song (None: unfinished), the iSTFT of each stem times the song's phases.  For every
+        bin of a finished song, STFT magnitude = residual + sum of the stems within (2 max_notes + 2) 2^-24 of it
+        (DESIGN 14).  Independent of residual=; events are the same with and without.  ValueError with
+        AMT_SUBTRACT_SPAN=0: only the span subtraction keeps stems."""
+        song_walk.check_walk(self, max_notes, silence, stems=stems)
+        st = song_walk.prepare_songs(self, songs, refs=refs, song0=song0, keep_residual=residual, keep_stems=stems)
+        return song_walk.walk_songs(st, max_notes, silence, poll=poll, song0=song0, residual=residual, stems=stems), st
 
     def iter_song_queue(self, songs, slots, max_notes=8, silence=1e-3, poll=16, pool_frames=None, on_finish=None,
-                        residual=False):
+                        residual=False, stems=False):
         """Continuous batching of the song walk: any number of songs of any lengths walked through `slots` live windows,
         a finished slot handed to the next song of the queue (the reference's unit of work is a dataset of songs, one
         song after the other per worker, training.py:623-634).  State, admission and step are run_songs' own
@@ -410,19 +429,24 @@ class TranscriptionLoop:
         residual=True: yields (song_index, events, residual) -- the song's residual waveform as run_songs(residual=True)
         gives it for that song alone (1-d float32 device tensor).  At a poll point ONE residual_waves() call covers
         every song found finished there; it is enqueued before their regions are released, on the walk's stream, so it
-        reads them ahead of the STFT of any later admission."""
-        song_walk.check_walk(self, max_notes, silence, slots, pool_frames)
+        reads them ahead of the STFT of any later admission.
+        stems=True: the song's stems [G, samples] (run_songs(stems=True) for that song alone) are appended to what is
+        yielded -- (song_index, events[, residual][, stems]), the optional items in that order.  They too are produced
+        before the regions are released; an admission zeroes the stems of the regions it hands out."""
+        song_walk.check_walk(self, max_notes, silence, slots, pool_frames, stems=stems)
         return song_walk.iter_song_queue(self, songs, slots, max_notes, silence, poll=poll, pool_frames=pool_frames,
-                                         on_finish=on_finish, residual=residual)
+                                         on_finish=on_finish, residual=residual, stems=stems)
 
     def run_song_queue(self, songs, slots, max_notes=8, silence=1e-3, poll=16, pool_frames=None, on_finish=None,
-                       residual=False):
+                       residual=False, stems=False):
         """iter_song_queue() run to its end.  Returns the list of the songs' records, events [k, 9] int32 host arrays,
-        in queue order; with residual=True a list of (events, residual waveform) pairs."""
+        in queue order; with residual=True a list of (events, residual waveform) pairs, with stems=True of
+        (events[, residual], stems) tuples."""
         out = {}
         for item in self.iter_song_queue(songs, slots, max_notes=max_notes, silence=silence, poll=poll,
-                                         pool_frames=pool_frames, on_finish=on_finish, residual=residual):
-            out[item[0]] = tuple(item[1:]) if residual else item[1]
+                                         pool_frames=pool_frames, on_finish=on_finish, residual=residual,
+                                         stems=stems):
+            out[item[0]] = tuple(item[1:]) if residual or stems else item[1]
         return [out[i] for i in range(len(out))]
 
     def run_stream(self, host_batches, refs=None, window0=0):

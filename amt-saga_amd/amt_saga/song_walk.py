@@ -126,8 +126,10 @@ class FramePool:
         self.free = merged
 
 
-def check_walk(lp, max_notes=1, silence=0.0, slots=1, pool_frames=None):
+def check_walk(lp, max_notes=1, silence=0.0, slots=1, pool_frames=None, stems=False):
     """The argument checks of every public entry of the walk, before any device set-up."""
+    if stems and not lp.span_subtract:
+        raise ValueError('run_songs: stems need the span subtraction (AMT_SUBTRACT_SPAN=0 is set)')
     if int(slots) < 1:
         raise ValueError('run_song_queue: slots must be at least 1')
     if int(max_notes) < 1:
@@ -164,18 +166,25 @@ class SongState:
     keep_residual: every slide stores the half window it pushes out back into the song's pool frames
     (amt_song_slide_keep), so that a FINISHED song's region of s_mag holds its residual spectrogram -- what every
     subtraction left of it -- and residual_waves() can resynthesise it.  Off (the default), the pool is never written
-    after the admission's STFT."""
+    after the admission's STFT.
+    keep_stems: `stems` [G, pool_frames, ldf] beside s_mag, G = len(lp.groups) -- every subtraction adds what it removed
+    (before - after, the clipped amount) into the stem of the note's instrument group, lp.prog_group[program] (stem 0
+    without the instrument head), at the song's own pool frames (amt_subtract_span_stems).  A song's region of every
+    stem is zeroed when it is admitted; nothing is written on a slide, so the flag is independent of keep_residual.  For
+    every bin of a finished song, STFT magnitude = residual + sum of the stems, up to rounding (DESIGN 14);
+    stem_waves() resynthesises them."""
 
-    def __init__(self, lp, slots, pool_frames, keep_residual=False):
+    def __init__(self, lp, slots, pool_frames, keep_residual=False, keep_stems=False):
         if not lp._dev_ready:
             lp.setup_device()
         p, dev = lp.p, require_gpu()
         B, pool_frames = int(slots), int(pool_frames)
         tf, ldf = p.timing_frames, ldf_of(p.N)
-        self.lp, self.slots, self.keep_residual = lp, B, bool(keep_residual)
+        self.lp, self.slots, self.keep_residual, self.keep_stems = lp, B, bool(keep_residual), bool(keep_stems)
         self.pool = FramePool(pool_frames)
         self.s_mag, self.s_ph = empty((pool_frames, ldf)), empty((pool_frames, ldf, 2))
         self.samples = empty((pool_frames * p.H,))
+        self.stems = empty((len(lp.groups), pool_frames, ldf)) if self.keep_stems else None
         b = self.batch = AudioBatch(None, p.N, p.H)
         b.mag, b.ph, b.ref_max = zeros((B, tf, ldf)), zeros((B, tf, ldf, 2)), zeros((B,))
         self.ref_keys = ['ref_mag'] + [k for h, k, _ in NORMALISERS if h in lp.heads]
@@ -191,6 +200,7 @@ class SongState:
         self.song_of, self.region = [-1] * B, [None] * B           # host: the slot's song (-1: free) and pool region
         self.frames = [0] * B                                      # host: frames of the slot's song
         self.residual = None                                       # walk_songs(residual=True): one waveform per slot
+        self.stem_audio = None                                     # walk_songs(stems=True): one [G, samples] per slot
         self.steps = self.positions = self.bound = 0
         self.stats = dict(steps=0, songs=0, admissions=0, waits=0, bound=0, slot_steps=[0, 0, 0, 0])
 
@@ -221,6 +231,10 @@ class SongState:
         for (_, _, w, f0), L in zip(took, lens):
             self.samples[f0 * H:f0 * H + L].copy_(w)
         d_fb, d_sb = to_dev(fbase, torch.int64), to_dev(fbase * H, torch.int64)
+        if self.keep_stems:
+            # on the walk's stream: behind a stem_waves() of the region's earlier song, ahead of the first subtraction
+            for t, f0 in zip(t_song, fbase):
+                self.stems[:, f0:f0 + t].zero_()
         if spectra is None:
             ref_mag, d_len = empty((n,)), to_dev(np.asarray(lens, np.int32), torch.int32)
             _lib.check(lp.lib.amt_stft_mag_ragged(b.plan, ptr(self.samples), ptr(d_sb), ptr(d_len), n, max(lens),
@@ -283,28 +297,48 @@ class SongState:
         it is still in the window -- e.g. after a max_steps cut -- so its residual is not defined)."""
         if not self.keep_residual:
             raise ValueError('residual_waves: the state was built without keep_residual')
+        out, base, lens = self._region_waves('residual_waves', slots, self.s_mag[None])
+        return [out[0, int(a):int(a) + n] for a, n in zip(base, lens)]
+
+    def stem_waves(self, slots):
+        """What the walk took out of the songs in `slots` (every one finished), per instrument group, as audio: the
+        iSTFT of each stem's region times the song's own phases (util_audio.py:94-97; the _guessed.flac of
+        training.py:426-447 at song length, split by group), ONE amt_istft_ragged launch per group over the slots'
+        regions, on the walk's stream.  Returns one [G, hop * (t_song - 1)] float32 device tensor per slot, in the order
+        given; row g belongs to lp.groups[g].  ValueError: a state built without keep_stems, a free slot, or a song
+        that is not finished."""
+        if not self.keep_stems:
+            raise ValueError('stem_waves: the state was built without keep_stems')
+        out, base, lens = self._region_waves('stem_waves', slots, self.stems)
+        return [out[:, int(a):int(a) + n] for a, n in zip(base, lens)]
+
+    def _region_waves(self, who, slots, mags):
+        """The iSTFT of the slots' regions of every mags[g] ([G, pool_frames, ldf]) times s_ph, one amt_istft_ragged
+        launch per g.  Returns (out [G, samples], first sample per slot, samples per slot)."""
         slots = [int(b) for b in slots]
+        G = int(mags.shape[0])
         if not slots:
-            return []
+            return empty((G, 0)), [], []
         fin = self.finished.cpu().numpy()
         for b in slots:
             if not 0 <= b < self.slots or self.region[b] is None:
-                raise ValueError('residual_waves: slot %d holds no song' % b)
+                raise ValueError('%s: slot %d holds no song' % (who, b))
             if not fin[b]:
-                raise ValueError('residual_waves: the song in slot %d is not finished' % b)
+                raise ValueError('%s: the song in slot %d is not finished' % (who, b))
         lp, H = self.lp, self.lp.p.H
         frames = [self.frames[b] for b in slots]
         lens = [H * (t - 1) for t in frames]
         base = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-        out = empty((int(base[-1]),))
+        out = empty((G, int(base[-1])))
         if base[-1] > 0:
             d_fb = to_dev(np.asarray([self.region[b] for b in slots], np.int64), torch.int64)
             d_tf = to_dev(np.asarray(frames, np.int32), torch.int32)
             d_ob = to_dev(base[:-1].copy(), torch.int64)
-            _lib.check(lp.lib.amt_istft_ragged(self.batch.plan, ptr(self.s_mag), ptr(self.s_ph), ptr(d_fb), ptr(d_tf),
-                                               len(slots), max(frames), self.pool.frames, self.s_mag.shape[1], ptr(out),
-                                               ptr(d_ob), int(base[-1]), stream_ptr()))
-        return [out[int(a):int(a) + n] for a, n in zip(base[:-1], lens)]
+            for g in range(G):
+                _lib.check(lp.lib.amt_istft_ragged(self.batch.plan, ptr(mags[g]), ptr(self.s_ph), ptr(d_fb), ptr(d_tf),
+                                                   len(slots), max(frames), self.pool.frames, mags.shape[2], ptr(out[g]),
+                                                   ptr(d_ob), int(base[-1]), stream_ptr()))
+        return out, base[:-1], lens
 
     def step(self, max_notes, silence, row, song0=None):
         """One step of the walk for every slot: the loop's _step() (the head sequence of iterate()) with the walk's
@@ -333,7 +367,13 @@ class SongState:
                                            ptr(self.slide), ptr(self.detect), ptr(self.kind), ptr(gfr), ptr(wmax), sp))
             b.ref_max = wmax                                       # np.max(audio_w.mag) at the subtraction (:170-174)
 
-        onset, end, pitch, program, velocity = lp._step(b, wave_fn, fmax=True, before_subtract=decide)
+        stem = None
+        if self.keep_stems:
+            # (_step adds the step's decided programs; without the instrument head everything is stem 0)
+            stem = _lib.stem_args(stems=self.stems, frame_base=self.frame_base, offset=self.offset, t_song=self.t_song,
+                                  prog_group=lp.prog_group, n_prog=int(lp.prog_group.shape[0]),
+                                  G=int(self.stems.shape[0]), pool_frames=self.pool.frames)
+        onset, end, pitch, program, velocity = lp._step(b, wave_fn, fmax=True, before_subtract=decide, stems=stem)
         note = (ptr(self.kind), ptr(pitch), ptr(program), ptr(velocity), ptr(onset), ptr(end), ptr(self.offset),
                 ptr(row), sp)
         if song0 is None:
@@ -348,23 +388,28 @@ class SongState:
         self.steps += 1
 
 
-def prepare_songs(lp, songs, refs=None, spectra=None, song0=0, keep_residual=False):
+def prepare_songs(lp, songs, refs=None, spectra=None, song0=0, keep_residual=False, keep_stems=False):
     """A fixed batch: as many slots as songs, a pool of exactly their frames, ONE admission of song i into slot i."""
     waves = [check_song(lp.p, s) for s in songs]
     if not waves:
         raise ValueError('run_songs: no songs given')
-    st = SongState(lp, len(waves), sum(1 + w.numel() // lp.p.H for w in waves), keep_residual=keep_residual)
+    st = SongState(lp, len(waves), sum(1 + w.numel() // lp.p.H for w in waves), keep_residual=keep_residual,
+                   keep_stems=keep_stems)
     st.admit([(i, int(song0) + i, w) for i, w in enumerate(waves)], refs=refs, spectra=spectra)
     return st
 
 
-def walk_songs(st, max_notes, silence, poll=16, song0=0, max_steps=None, residual=False):
+def walk_songs(st, max_notes, silence, poll=16, song0=0, max_steps=None, residual=False, stems=False):
     """Steps a fixed batch to its end (or max_steps) with nothing read back but finished.sum() every `poll` steps.
     residual (a state with keep_residual): afterwards st.residual = one entry per slot, the finished songs' residual
     waveforms from ONE residual_waves() call, None for a song the walk left unfinished.
+    stems (a state with keep_stems): afterwards st.stem_audio = one entry per slot, the finished songs' [G, samples]
+    stem waveforms from ONE stem_waves() call, None for an unfinished song.
     Returns events [steps, slots, 9] int32 (device), FINISHED records of idle slots included."""
     if residual and not st.keep_residual:
         raise ValueError('walk_songs: residual needs a state prepared with keep_residual')
+    if stems and not st.keep_stems:
+        raise ValueError('walk_songs: stems need a state prepared with keep_stems')
     B = st.slots
     st.bound = st.positions * (int(max_notes) + 1)
     if max_steps is not None:
@@ -375,16 +420,22 @@ def walk_songs(st, max_notes, silence, poll=16, song0=0, max_steps=None, residua
         st.step(max_notes, silence, events[st.steps], song0)
         if st.steps % max(int(poll), 1) == 0 and int(st.finished.sum()) == B:
             break
-    if residual:
+    if residual or stems:
         fin = st.finished.cpu().numpy()
         done = [b for b in range(B) if fin[b] and st.region[b] is not None]
+    if residual:
         st.residual = [None] * B
         for b, w in zip(done, st.residual_waves(done)):
             st.residual[b] = w
+    if stems:
+        st.stem_audio = [None] * B
+        for b, w in zip(done, st.stem_waves(done)):
+            st.stem_audio[b] = w
     return events[:st.steps]
 
 
-def iter_song_queue(lp, songs, slots, max_notes, silence, poll=16, pool_frames=None, on_finish=None, residual=False):
+def iter_song_queue(lp, songs, slots, max_notes, silence, poll=16, pool_frames=None, on_finish=None, residual=False,
+                    stems=False):
     """Pulls and checks the first `slots` songs (no song at all is an error of the call, not of the first next()) and
     returns the generator of the queue's walk."""
     p, B, poll = lp.p, int(slots), max(int(poll), 1)
@@ -406,7 +457,7 @@ def iter_song_queue(lp, songs, slots, max_notes, silence, poll=16, pool_frames=N
         pool_frames = B * max(1 + w.numel() // p.H for _, w in ahead)
 
     def walk():
-        st = SongState(lp, B, pool_frames, keep_residual=residual)
+        st = SongState(lp, B, pool_frames, keep_residual=residual, keep_stems=stems)
         stats = lp.queue_stats = st.stats
         chunk = empty((poll, B, len(SONG_EVENT_FIELDS)), torch.int32)
         host_chunk = torch.empty(tuple(chunk.shape), dtype=torch.int32, pin_memory=True)
@@ -446,14 +497,16 @@ def iter_song_queue(lp, songs, slots, max_notes, silence, poll=16, pool_frames=N
                     done.append((slot, idx))
             # the residual of every song found finished here, in ONE launch, enqueued BEFORE any region is released:
             # on the walk's stream it runs ahead of the STFT a later admission writes into such a region
+            # (and their stems likewise: the zeroing of a later admission follows on the same stream)
             waves = st.residual_waves([slot for slot, _ in done]) if residual and done else []
+            stem_w = st.stem_waves([slot for slot, _ in done]) if stems and done else []
             for k, (slot, idx) in enumerate(done):
                 if on_finish is not None:
                     on_finish(idx, slot, st)
                 out = np.concatenate(records.pop(idx))
                 out[:, 1] = np.arange(len(out))
                 st.release(slot)
-                yield (idx, out, waves[k]) if residual else (idx, out)
+                yield (idx, out) + ((waves[k],) if residual else ()) + ((stem_w[k],) if stems else ())
             admit()
             if st.steps > stats['bound']:
                 raise RuntimeError('run_song_queue: %d steps, past the bound of the admitted songs (%d)'

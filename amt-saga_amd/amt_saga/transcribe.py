@@ -17,6 +17,8 @@ provide for the inference direction:
     (audio.resample, the `sr=` of librosa.load, util_audio.py:962-964); without it the model is built at the file's rate.
     --residual OUT.flac (with --traversal song) / --residual-dir DIR (with --songs): what the walk left of the song after
     every subtraction, as 24-bit FLAC at the model's rate (the reference's _after_subtr.flac, training.py:438-447).
+    --stems-dir DIR (with --traversal song, or with --songs): what the walk took out of the song, one file per instrument
+    group, <input stem>.group<g>.flac (the reference's _guessed.flac, training.py:426-447, at song length).
 
 Weights: a directory with {timing_start,timing_end,pitch,instrument,velocity}.npz in the
 naming of amt_saga/rdcnn.py; without it the heads carry their seeded synthetic weights (the
@@ -63,7 +65,7 @@ def _make_loop(p, iters, heads, groups, weights_dir, guess):
 
 def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument', 'velocity'),
                groups=(0, 1, 2), weights_dir=None, guess='bank', loop=None, batch=1024, traversal='windows',
-               silence=1e-3, sr=None, residual=False):
+               silence=1e-3, sr=None, residual=False, stems=False):
     """wf: float32 mono waveform at params.sr -- or, with `sr` given, a waveform [n] or [n, channels] at `sr`, resampled
     to params.sr (and downmixed) on the device first (audio.resample): everything below, the length the note times are
     computed from included, then sees the resampled signal.  Returns (notes, events) where notes is the
@@ -75,11 +77,16 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
     `silence` x the song's maximum skipped; events are then the [steps, 1, 9] song records and nothing needs merging.
     residual=True (traversal='song' only; the independent windows have no song-level residual: ValueError): returns
     (notes, events, residual) with the song's residual waveform at params.sr, a 1-d float32 device tensor of
-    hop * (frames - 1) samples (run_songs(residual=True)); None if the walk stopped before the song's end."""
+    hop * (frames - 1) samples (run_songs(residual=True)); None if the walk stopped before the song's end.
+    stems=True (traversal='song' only: ValueError): the song's instrument stems, a [len(groups), hop * (frames - 1)]
+    float32 device tensor (run_songs(stems=True); row g belongs to groups[g]), are appended to what is returned --
+    (notes, events[, residual][, stems])."""
     if traversal not in ('windows', 'song'):
         raise ValueError('Requested attribute does not exist')
     if residual and traversal != 'song':
         raise ValueError("transcribe: residual=True needs traversal='song'")
+    if stems and traversal != 'song':
+        raise ValueError("transcribe: stems=True needs traversal='song'")
     p = params or Hyperparams(N=2048)
     if loop is None:
         loop = _make_loop(p, iters, heads, groups, weights_dir, guess)
@@ -89,10 +96,10 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
     on_dev = isinstance(wf, torch.Tensor) and wf.is_cuda
     if traversal == 'song':
         wf32 = wf if on_dev else np.ascontiguousarray(wf, dtype=np.float32)      # (run_songs takes either)
-        events, st = loop.run_songs([wf32], max_notes=iters, silence=silence, residual=residual)
+        events, st = loop.run_songs([wf32], max_notes=iters, silence=silence, residual=residual, stems=stems)
         evs = events.cpu().numpy()
         notes = ev.song_events_to_notes(evs, 1 + len(wf32) // p.H, len(wf32), sr=p.sr)
-        return (notes, evs, st.residual[0]) if residual else (notes, evs)
+        return (notes, evs) + ((st.residual[0],) if residual else ()) + ((st.stem_audio[0],) if stems else ())
     L = p.H * (p.timing_frames - 1)
     wf_dev = wf if on_dev else torch.from_numpy(np.ascontiguousarray(wf, dtype=np.float32)).cuda()
     wins, starts = cut_windows(wf.cpu().numpy() if on_dev else np.asarray(wf, dtype=np.float32), L, L // 2)
@@ -113,9 +120,10 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
 
 def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', 'instrument', 'velocity'),
                           groups=(0, 1, 2), weights_dir=None, guess='bank', loop=None, slots=8, silence=1e-3, poll=16,
-                          pool_frames=None, residual=False):
+                          pool_frames=None, residual=False, stems=False):
     """The song queue behind transcribe_songs (TranscriptionLoop.iter_song_queue): yields (index, notes, events) as
-    each song finishes, in finishing order -- (index, notes, events, residual waveform) with residual=True.  wfs: a sequence or an iterator of mono float32 waveforms at params.sr; an
+    each song finishes, in finishing order -- (index, notes, events[, residual waveform][, stems [G, samples]]) with
+    residual=True / stems=True.  wfs: a sequence or an iterator of mono float32 waveforms at params.sr; an
     item may also be a (waveform [n] or [n, channels], sr) pair, which is resampled to params.sr on the device as it is
     pulled (audio.resample)."""
     p = params or Hyperparams(N=2048)
@@ -133,7 +141,7 @@ def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', '
             lens[i] = len(w)
             yield w
     for item in loop.iter_song_queue(feed(), slots, max_notes=iters, silence=silence, poll=poll,
-                                     pool_frames=pool_frames, residual=residual):
+                                     pool_frames=pool_frames, residual=residual, stems=stems):
         i, evs = item[0], item[1]
         n = lens.pop(i)
         one = evs.copy()
@@ -141,15 +149,28 @@ def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', '
         notes = ev.song_events_to_notes(one, 1 + n // p.H, n, sr=p.sr)
         for note in notes:
             note['song'] = i
-        yield (i, notes, evs, item[2]) if residual else (i, notes, evs)
+        yield (i, notes, evs) + tuple(item[2:])
 
 
 def transcribe_songs(wfs, params=None, slots=8, **kw):
     """A collection of songs through the song queue: `slots` live windows, a finished slot refilled with the next
     song.  Returns [(notes, events [k, 9]), ...] in input order; a song's notes are those of
-    transcribe(wf, traversal='song') for it alone (with `song` = its index).  residual=True: (notes, events, residual)."""
+    transcribe(wf, traversal='song') for it alone (with `song` = its index).  residual=True / stems=True:
+    (notes, events[, residual][, stems])."""
     out = {item[0]: tuple(item[1:]) for item in iter_transcribe_songs(wfs, params, slots=slots, **kw)}
     return [out[i] for i in range(len(out))]
+
+
+CLI_GROUPS = (0, 1, 2)                                             # the command line's instrument groups (reference ids)
+
+
+def _write_stems(flac, waves, out_dir, name, rate):
+    """<name>.group<g>.flac per row of waves [G, samples], g the reference group id of the row (CLI_GROUPS)."""
+    y = waves.cpu().numpy()
+    for row, g in zip(y, CLI_GROUPS):
+        out = os.path.join(out_dir, '%s.group%d.flac' % (name, g))
+        flac.save_float(np.ascontiguousarray(row), out, sr=rate)
+        print('stem of group %d -> %s' % (g, out))
 
 
 def main_songs(argv):
@@ -169,11 +190,15 @@ def main_songs(argv):
     ap.add_argument('--residual-dir', default=None,
                     help='write <stem>.residual.flac per song as it finishes: what the walk left after every subtraction, '
                          '24-bit FLAC at the rate the model runs at (with --sr, the resampled rate)')
+    ap.add_argument('--stems-dir', default=None,
+                    help='write <stem>.group<g>.flac per song and instrument group as it finishes: what the subtractions '
+                         'took out of the song, 24-bit FLAC at the rate the model runs at')
     a = ap.parse_args(argv)
     os.makedirs(a.out_dir, exist_ok=True)
-    keep = a.residual_dir is not None
-    if keep:
-        os.makedirs(a.residual_dir, exist_ok=True)
+    keep, keep_stems = a.residual_dir is not None, a.stems_dir is not None
+    for d in (a.residual_dir, a.stems_dir):
+        if d is not None:
+            os.makedirs(d, exist_ok=True)
     stems = [os.path.splitext(os.path.basename(f))[0] for f in a.songs]
     if len(set(stems)) != len(stems):
         raise SystemExit('--songs: two inputs would write the same .mid (equal file names)')
@@ -181,10 +206,11 @@ def main_songs(argv):
         if a.sr <= 0:
             raise SystemExit('--sr: the rate must be positive')
         queue = iter_transcribe_songs((flac.load_float(f) for f in a.songs), Hyperparams(N=2048, sr=a.sr), iters=a.iters,
-                                      weights_dir=a.weights, guess=a.guess, slots=a.slots, residual=keep)
+                                      weights_dir=a.weights, guess=a.guess, slots=a.slots, residual=keep,
+                                      stems=keep_stems, groups=CLI_GROUPS)
         rate = a.sr
     else:
-        queue, rate = _same_rate_queue(a, flac, keep)
+        queue, rate = _same_rate_queue(a, flac, keep, keep_stems)
     for item in queue:
         i, notes = item[0], item[1]
         out = os.path.join(a.out_dir, stems[i] + '.mid')
@@ -194,9 +220,11 @@ def main_songs(argv):
             out = os.path.join(a.residual_dir, stems[i] + '.residual.flac')
             flac.save_float(item[3].cpu().numpy(), out, sr=rate)
             print('residual -> %s' % out)
+        if keep_stems:
+            _write_stems(flac, item[-1], a.stems_dir, stems[i], rate)
 
 
-def _same_rate_queue(a, flac, residual=False):
+def _same_rate_queue(a, flac, residual=False, stems=False):
     """--songs without --sr: the model at the first file's rate, every other file refused unless it has that rate.
     Returns (the queue, that rate)."""
     first = flac.load_float(a.songs[0])
@@ -210,7 +238,7 @@ def _same_rate_queue(a, flac, residual=False):
                                  % (f, sr, sr0))
             yield wf.mean(axis=1) if wf.ndim > 1 else wf
     return iter_transcribe_songs(load(), Hyperparams(N=2048, sr=sr0), iters=a.iters, weights_dir=a.weights,
-                                 guess=a.guess, slots=a.slots, residual=residual), sr0
+                                 guess=a.guess, slots=a.slots, residual=residual, stems=stems, groups=CLI_GROUPS), sr0
 
 
 def main(argv=None):
@@ -232,9 +260,14 @@ def main(argv=None):
     ap.add_argument('--residual', default=None, metavar='OUT.flac',
                     help='with --traversal song: write what the walk left of the song after every subtraction, 24-bit FLAC '
                          'at the rate the model runs at (with --sr, the resampled rate)')
+    ap.add_argument('--stems-dir', default=None, metavar='DIR',
+                    help='with --traversal song: write <input stem>.group<g>.flac per instrument group, what the '
+                         'subtractions took out of the song, 24-bit FLAC at the rate the model runs at')
     a = ap.parse_args(argv)
     if a.residual is not None and a.traversal != 'song':
         raise SystemExit('--residual needs --traversal song (independent windows have no song-level residual)')
+    if a.stems_dir is not None and a.traversal != 'song':
+        raise SystemExit('--stems-dir needs --traversal song (independent windows have no song-level stems)')
     wf, sr = flac.load_float(a.infile)
     if a.sr is None:                             # the model at the file's rate
         if wf.ndim > 1:
@@ -245,7 +278,8 @@ def main(argv=None):
     else:                                        # the file at the model's rate: resampled and downmixed on the device
         model_sr, file_sr = a.sr, sr
     got = transcribe(wf, Hyperparams(N=2048, sr=model_sr), iters=a.iters, weights_dir=a.weights, guess=a.guess,
-                     traversal=a.traversal, sr=file_sr, residual=a.residual is not None)
+                     traversal=a.traversal, sr=file_sr, residual=a.residual is not None, stems=a.stems_dir is not None,
+                     groups=CLI_GROUPS)
     notes = got[0]
     ev.write_midi(notes, a.outfile)
     print('%d notes -> %s' % (len(notes), a.outfile))
@@ -254,6 +288,11 @@ def main(argv=None):
             raise SystemExit('--residual: the walk stopped before the end of the song')
         flac.save_float(got[2].cpu().numpy(), a.residual, sr=model_sr)
         print('residual -> %s' % a.residual)
+    if a.stems_dir is not None:
+        if got[-1] is None:
+            raise SystemExit('--stems-dir: the walk stopped before the end of the song')
+        os.makedirs(a.stems_dir, exist_ok=True)
+        _write_stems(flac, got[-1], a.stems_dir, os.path.splitext(os.path.basename(a.infile))[0], model_sr)
 
 
 if __name__ == '__main__':

@@ -179,6 +179,31 @@ int amt_subtract(const amt_subtract_args *args, void *stream);
  * (the guess tensor's frames).  Residual and maxima are bit-identical to amt_subtract's. */
 int amt_subtract_span(const amt_subtract_args *args, float *frame_max, int span_cap, void *stream);
 
+/* amt_subtract_span that keeps what it removed -- the instrument stems of a song walk (the reference dumps exactly this
+ * pair per subtraction, _guessed.flac beside _after_subtr.flac, training.py:426-447; the step itself is
+ * audio_complete.subtract, util_audio.py:221-259).  Window row t of slot b is song frame offset[b] + t, i.e. pool row
+ * frame_base[b] + offset[b] + t of every stem; the step adds before - after of each element of the row (after =
+ * max(before - guess * scale * overkill, 0): the clipped amount, not the scaled guess) into stem
+ * prog_group[clamp(program[b], 0, n_prog - 1)], the group clamped into [0, G).  program or prog_group NULL: stem 0.
+ * Rows with offset[b] + t >= t_song[b] (zero padding in the window, another song's region in the pool) or outside
+ * [0, pool_frames) are subtracted as ever, but their stem row is neither read nor written.  One wave owns a row and
+ * slots own disjoint regions: no atomics.  Un-fused float32 (numpy reproduces every bit); residual, frame_max and
+ * new_max are bit-identical to amt_subtract_span's on the same inputs.  Checks: amt_subtract_span's, and AMT_E_INVALID
+ * for a NULL stems / frame_base / offset / t_song, G < 1, pool_frames < 1.  Packed-FP32 code: launch it on the one
+ * compute stream, never beside the networks on a side stream. */
+typedef struct amt_stem_args {
+    float         *stems;        /* [G][pool_frames][ldf] */
+    const int64_t *frame_base;   /* [B] first pool frame of the slot's song */
+    const int32_t *offset;       /* [B] song frame of the window's frame 0 */
+    const int32_t *t_song;       /* [B] frames of the slot's song */
+    const int32_t *program;      /* [B] or NULL => stem 0 */
+    const int32_t *prog_group;   /* [n_prog] or NULL => stem 0 */
+    int32_t        n_prog, G;
+    int64_t        pool_frames;
+} amt_stem_args;
+int amt_subtract_span_stems(const amt_subtract_args *args, float *frame_max, int span_cap,
+                            const amt_stem_args *stem, void *stream);
+
 /* ------------------------------------------------------------------------ *
  * Feature gathers (audio_complete.compress_bands :436-466, ._resize :384-409,
  * .resize :469-507, .section_power :334-349 and the recipe of
