@@ -1025,3 +1025,95 @@ def resample(wf, sr_in, sr_out):
     if rs is None:
         rs = _RESAMPLERS[(sr_in, sr_out)] = Resampler(sr_in, sr_out)
     return rs(wf)
+
+
+# ======================================================================================
+# FLAC encoding on the device (the soundfile.write of audio_to_flac, util_audio.py:966-968)
+# ======================================================================================
+def _flac_signals(waves):
+    """The 1-d float32 device signals of `waves`: a tensor [n] or [G, n], or a list of those.  Rows of a 2-d tensor are
+    taken as views; only a signal whose samples are not adjacent in memory is copied."""
+    items = [waves] if isinstance(waves, torch.Tensor) else list(waves)
+    sigs = []
+    for w in items:
+        if not (isinstance(w, torch.Tensor) and w.is_cuda and w.dtype == torch.float32 and w.dim() in (1, 2)):
+            raise ValueError('Invalid Input shape. Expected: float32 device tensors [n] or [G, n] . Got: %s'
+                             % (tuple(w.shape) if hasattr(w, 'shape') else type(w).__name__,))
+        for r in ([w] if w.dim() == 1 else w.unbind(0)):
+            sigs.append(r if r.numel() <= 1 or r.stride(0) == 1 else r.contiguous())
+    if not sigs:
+        raise ValueError('Invalid Input shape. Expected: at least one signal . Got: an empty list')
+    if len({s.device for s in sigs}) != 1:
+        raise ValueError('Invalid Input shape. Expected: signals of one device . Got: several')
+    return sigs
+
+
+def flac_encode_streams(waves, bps=24, blocksize=4096, first_frame=0):
+    """amt_flac_encode_ragged for the signals of `waves` (see _flac_signals), one call on the current stream: returns
+    (out, stream_off, frame_minmax, md5, frame_bytes) -- out a uint8 device buffer in which signal i's frames lie back
+    to back at [stream_off[i], stream_off[i + 1]); stream_off int64 [n + 1], frame_minmax int32 [n, 2], md5 uint8
+    [n, 16], frame_bytes int64 [n, frames of the longest]: all device tensors, nothing is synchronised."""
+    lib = _lib.load()
+    sigs = _flac_signals(waves)
+    bound = int(lib.amt_flac_frame_bound(int(blocksize), int(bps)))
+    if bound < 0 or int(first_frame) < 0:
+        _lib.check(_lib.AMT_E_INVALID)
+    n = len(sigs)
+    lens = [int(s.numel()) for s in sigs]
+    max_len = max(lens)
+    frames = [-(-l // int(blocksize)) for l in lens]
+    live = [s.data_ptr() for s, l in zip(sigs, lens) if l]
+    anchor = min(live) if live else 0
+    base = [(s.data_ptr() - anchor) // 4 if l else 0 for s, l in zip(sigs, lens)]
+    dev = sigs[0].device
+    meta = torch.tensor([base, lens], dtype=torch.int64).to(dev)
+    scratch = torch.empty((max(int(lib.amt_flac_scratch_bytes(n, max_len, int(blocksize), int(bps))), 8),),
+                          dtype=torch.uint8, device=dev)
+    out = torch.empty((max(sum(frames) * bound, 8),), dtype=torch.uint8, device=dev)
+    frame_bytes = torch.empty((n, max(frames)), dtype=torch.int64, device=dev)
+    stream_off = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+    minmax = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    md5 = torch.empty((n, 16), dtype=torch.uint8, device=dev)
+    # (a host-side 8 stands where a buffer would be empty: the ABI refuses NULL)
+    fb = frame_bytes if frame_bytes.numel() else torch.empty((1,), dtype=torch.int64, device=dev)
+    _lib.check(lib.amt_flac_encode_ragged(
+        C.c_void_p(anchor if live else scratch.data_ptr()), ptr(meta[0]), ptr(meta[1]), n, max_len, int(blocksize),
+        int(bps), int(first_frame), ptr(scratch), scratch.numel(), ptr(out), out.numel(), ptr(fb), ptr(stream_off),
+        ptr(minmax), ptr(md5), stream_ptr()))
+    # the signals and the scratch stay referenced until the call is enqueued; torch's allocator keeps a freed block
+    # for the stream that used it, so work enqueued later on this stream cannot overtake the encoder
+    return out, stream_off, minmax, md5, frame_bytes
+
+
+def flac_stream_header(n_samples, sr, bps, blocksize, min_frame, max_frame, md5):
+    """fLaC + the STREAMINFO block (the last metadata block), 42 bytes, as flac.encode writes it for a mono stream."""
+    si = int(blocksize).to_bytes(2, 'big') * 2 + int(min_frame).to_bytes(3, 'big') + int(max_frame).to_bytes(3, 'big')
+    si += ((int(sr) << 44) | ((int(bps) - 1) << 36) | int(n_samples)).to_bytes(8, 'big') + bytes(md5)
+    return b'fLaC' + bytes([0x80]) + len(si).to_bytes(3, 'big') + si
+
+
+def flac_encode(waves, sr, bps=24, blocksize=4096):
+    """audio_to_flac (util_audio.py:966-968) without the file: every signal of `waves` -- a list of 1-d float32 device
+    tensors; a [G, n] tensor counts as G signals, its rows are not copied -- as the bytes of a complete mono FLAC file
+    (fLaC, STREAMINFO, frames).  One encode call for the whole list, on the current stream, so it is ordered after
+    whatever produced the tensors; the frames come back in one device-to-host copy."""
+    sigs = _flac_signals(waves)
+    out, stream_off, minmax, md5, _ = flac_encode_streams(sigs, bps=bps, blocksize=blocksize)
+    off = stream_off.cpu().tolist()
+    minmax, md5 = minmax.cpu().tolist(), md5.cpu().numpy()
+    if off[-1] > out.numel():
+        raise RuntimeError('flac_encode: the streams need %d bytes, the buffer has %d' % (off[-1], out.numel()))
+    data = out[:off[-1]].cpu().numpy().tobytes()
+    return [flac_stream_header(s.numel(), sr, bps, blocksize, minmax[i][0], minmax[i][1], md5[i].tobytes())
+            + data[off[i]:off[i + 1]] for i, s in enumerate(sigs)]
+
+
+def save_flac(waves, paths, sr, bps=24):
+    """flac_encode(waves, sr, bps) written to `paths`, one file per signal, one write per file."""
+    files = flac_encode(waves, sr, bps=bps)
+    paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
+    if len(paths) != len(files):
+        raise ValueError('Invalid Input shape. Expected: one path per signal (%d) . Got: %d' % (len(files), len(paths)))
+    for data, path in zip(files, paths):
+        with open(path, 'wb') as f:
+            f.write(data)

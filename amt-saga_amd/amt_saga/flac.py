@@ -12,6 +12,7 @@ Returns integer PCM; load_float scales by 2**-(bps-1) like libsndfile does.
 
 Writer: VERBATIM subframes (valid FLAC, no compression), fixed block size 4096,
 PCM-24 by default like audio_to_flac; STREAMINFO MD5 of the unencoded samples is written.
+The compressing encoder is the device's (audio.flac_encode / save_flac, amt_flac.hip); this writer stays the default.
 
 Integrity: the reader verifies every frame header's CRC-8, every frame's CRC-16 and the
 STREAMINFO MD5 signature of the decoded samples (when the file carries one) and raises
@@ -272,7 +273,7 @@ def _utf8_num(v):
         out.append(0x80 | (v & 0x3F))
         v >>= 6
         n += 1
-    lead = (0xFF << (6 - n)) & 0xFF
+    lead = (0xFF << (7 - n)) & 0xFF
     out.append(lead | v)
     return bytes(reversed(out))
 

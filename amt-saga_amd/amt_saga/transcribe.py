@@ -19,6 +19,8 @@ provide for the inference direction:
     every subtraction, as 24-bit FLAC at the model's rate (the reference's _after_subtr.flac, training.py:438-447).
     --stems-dir DIR (with --traversal song, or with --songs): what the walk took out of the song, one file per instrument
     group, <input stem>.group<g>.flac (the reference's _guessed.flac, training.py:426-447, at song length).
+    --flac {host,device}: the writer of those files -- host (default): amt_saga.flac's VERBATIM writer; device: the HIP
+    encoder (audio.save_flac), a song's residual and stems in one call, compressed.
 
 Weights: a directory with {timing_start,timing_end,pitch,instrument,velocity}.npz in the
 naming of amt_saga/rdcnn.py; without it the heads carry their seeded synthetic weights (the
@@ -164,13 +166,40 @@ def transcribe_songs(wfs, params=None, slots=8, **kw):
 CLI_GROUPS = (0, 1, 2)                                             # the command line's instrument groups (reference ids)
 
 
-def _write_stems(flac, waves, out_dir, name, rate):
-    """<name>.group<g>.flac per row of waves [G, samples], g the reference group id of the row (CLI_GROUPS)."""
-    y = waves.cpu().numpy()
-    for row, g in zip(y, CLI_GROUPS):
-        out = os.path.join(out_dir, '%s.group%d.flac' % (name, g))
-        flac.save_float(np.ascontiguousarray(row), out, sr=rate)
-        print('stem of group %d -> %s' % (g, out))
+FLAC_WRITERS = ('host', 'device')
+_FLAC_HELP = ("writer of --residual / --residual-dir / --stems-dir: 'host' = the VERBATIM writer (uncompressed FLAC, the "
+              "default), 'device' = the HIP encoder (fixed predictors + Rice coding, one call per song)")
+
+
+def write_song_audio(rate, residual=None, residual_path=None, stems=None, stems_dir=None, name=None, flac='host'):
+    """What a song walk kept, as 24-bit FLAC at `rate`: `residual` (1-d device tensor) to residual_path, and / or the rows
+    of `stems` [G, samples] to <stems_dir>/<name>.group<g>.flac, g the reference group id of the row (CLI_GROUPS).
+    flac='host': the VERBATIM writer of amt_saga.flac, file by file (the default: the bytes every earlier call wrote);
+    flac='device': audio.save_flac -- the residual and all stems of the song in ONE encode call on the device,
+    compressed, and no sample crosses to the host before it is coded."""
+    if flac not in FLAC_WRITERS:
+        raise ValueError('Requested attribute does not exist')
+    waves, paths, notes = [], [], []
+    if residual is not None:
+        waves.append(residual)
+        paths.append(residual_path)
+        notes.append('residual -> %s' % residual_path)
+    if stems is not None:
+        for row, g in zip(stems, CLI_GROUPS):
+            waves.append(row)
+            paths.append(os.path.join(stems_dir, '%s.group%d.flac' % (name, g)))
+            notes.append('stem of group %d -> %s' % (g, paths[-1]))
+    if not waves:
+        return
+    if flac == 'device':
+        from . import audio
+        audio.save_flac(waves, paths, rate)
+    else:
+        from . import flac as host
+        for w, path in zip(waves, paths):
+            host.save_float(np.ascontiguousarray(w.cpu().numpy()), path, sr=rate)
+    for line in notes:
+        print(line)
 
 
 def main_songs(argv):
@@ -193,6 +222,7 @@ def main_songs(argv):
     ap.add_argument('--stems-dir', default=None,
                     help='write <stem>.group<g>.flac per song and instrument group as it finishes: what the subtractions '
                          'took out of the song, 24-bit FLAC at the rate the model runs at')
+    ap.add_argument('--flac', default='host', choices=FLAC_WRITERS, help=_FLAC_HELP)
     a = ap.parse_args(argv)
     os.makedirs(a.out_dir, exist_ok=True)
     keep, keep_stems = a.residual_dir is not None, a.stems_dir is not None
@@ -216,12 +246,9 @@ def main_songs(argv):
         out = os.path.join(a.out_dir, stems[i] + '.mid')
         ev.write_midi(notes, out)
         print('%d notes -> %s' % (len(notes), out))
-        if keep:
-            out = os.path.join(a.residual_dir, stems[i] + '.residual.flac')
-            flac.save_float(item[3].cpu().numpy(), out, sr=rate)
-            print('residual -> %s' % out)
-        if keep_stems:
-            _write_stems(flac, item[-1], a.stems_dir, stems[i], rate)
+        write_song_audio(rate, residual=item[3] if keep else None,
+                         residual_path=os.path.join(a.residual_dir, stems[i] + '.residual.flac') if keep else None,
+                         stems=item[-1] if keep_stems else None, stems_dir=a.stems_dir, name=stems[i], flac=a.flac)
 
 
 def _same_rate_queue(a, flac, residual=False, stems=False):
@@ -263,6 +290,7 @@ def main(argv=None):
     ap.add_argument('--stems-dir', default=None, metavar='DIR',
                     help='with --traversal song: write <input stem>.group<g>.flac per instrument group, what the '
                          'subtractions took out of the song, 24-bit FLAC at the rate the model runs at')
+    ap.add_argument('--flac', default='host', choices=FLAC_WRITERS, help=_FLAC_HELP)
     a = ap.parse_args(argv)
     if a.residual is not None and a.traversal != 'song':
         raise SystemExit('--residual needs --traversal song (independent windows have no song-level residual)')
@@ -283,16 +311,15 @@ def main(argv=None):
     notes = got[0]
     ev.write_midi(notes, a.outfile)
     print('%d notes -> %s' % (len(notes), a.outfile))
-    if a.residual is not None:
-        if got[2] is None:
-            raise SystemExit('--residual: the walk stopped before the end of the song')
-        flac.save_float(got[2].cpu().numpy(), a.residual, sr=model_sr)
-        print('residual -> %s' % a.residual)
+    if a.residual is not None and got[2] is None:
+        raise SystemExit('--residual: the walk stopped before the end of the song')
     if a.stems_dir is not None:
         if got[-1] is None:
             raise SystemExit('--stems-dir: the walk stopped before the end of the song')
         os.makedirs(a.stems_dir, exist_ok=True)
-        _write_stems(flac, got[-1], a.stems_dir, os.path.splitext(os.path.basename(a.infile))[0], model_sr)
+    write_song_audio(model_sr, residual=got[2] if a.residual is not None else None, residual_path=a.residual,
+                     stems=got[-1] if a.stems_dir is not None else None, stems_dir=a.stems_dir,
+                     name=os.path.splitext(os.path.basename(a.infile))[0], flac=a.flac)
 
 
 if __name__ == '__main__':

@@ -148,6 +148,40 @@ int amt_resample_ragged(const amt_resampler *rs, const float *in, const int64_t 
                         float *out, const int64_t *out_base, long long out_floats, void *stream);
 
 /* ------------------------------------------------------------------------ *
+ * FLAC encoder  (replaces the soundfile.write of audio_to_flac, util_audio.py:966-968, for audio that is already on
+ * the device: the residual and the stems of a song walk)
+ *
+ * Mono, bps in {16, 24}, fixed block size in [16, 4096] (the last block of a signal shorter), one subframe per frame:
+ * CONSTANT, FIXED order 0..4 with partitioned Rice2 coding, or VERBATIM, chosen by exact bit count (smallest bits,
+ * then smallest partition order, then smallest predictor order; VERBATIM unless a FIXED form is strictly smaller).
+ * q = clip(rint(y 2^(bps-1))), NaN -> 0.  All integer: every byte is defined.
+ * ------------------------------------------------------------------------ */
+/* audio_to_flac (util_audio.py:966-968): the largest frame in bytes, 13 + ceil((8 + blocksize bps) / 8) + 2 -- header,
+ * VERBATIM subframe, CRC-16.  Negative (AMT_E_INVALID) for bps not in {16, 24} or blocksize outside [16, 4096].
+ * Host only. */
+long long amt_flac_frame_bound(int blocksize, int bps);
+/* audio_to_flac (util_audio.py:966-968): bytes of `scratch` amt_flac_encode_ragged needs for n signals of at most
+ * max_len samples: one slot of amt_flac_frame_bound bytes per frame of an [n][frames(max_len)] grid, rounded up to 8,
+ * then one int64 per slot (the frame's byte offset inside its stream).  Negative for invalid arguments.  Host only. */
+long long amt_flac_scratch_bytes(int n, long long max_len, int blocksize, int bps);
+/* audio_to_flac (util_audio.py:966-968) for n signals in ONE call: signal i = wave[base[i] .. + len[i]) (floats; base
+ * may be any offset, negative included, that lands in memory the caller owns; a len above max_len is cut to max_len).
+ * Its frames, numbered first_frame, first_frame + 1, ..., go to out[stream_off[i] .. stream_off[i + 1]) back to back;
+ * frame_bytes [n][frames(max_len)] receives every frame's size (0 past a signal's last frame), stream_off [n + 1] the
+ * byte offsets of the streams and their total, frame_minmax [2 n] each signal's smallest and largest frame (0, 0 for
+ * an empty signal), md5 [16 n] the MD5 of each signal's little-endian PCM, as STREAMINFO wants it.  base, len and all
+ * outputs: device.  max_len (host) sizes the grid.
+ * AMT_E_INVALID: a NULL pointer, n < 1, bps not in {16, 24}, blocksize outside [16, 4096], first_frame < 0 or
+ * first_frame + frames(max_len) >= 2^31.  AMT_E_SHAPE: scratch_bytes < amt_flac_scratch_bytes(...), or out_bytes <
+ * frames(max_len) * bound (the longest signal alone must fit).  out_bytes >= (sum of the signals' frame counts) * bound
+ * always suffices; a frame that would pass out_bytes is not copied, and stream_off[n] > out_bytes tells the caller.
+ * All checks return before any HIP call.  Integer code without packed-FP32 instructions: any stream. */
+int amt_flac_encode_ragged(const float *wave, const long long *base, const long long *len, int n, long long max_len,
+                           int blocksize, int bps, long long first_frame, unsigned char *scratch,
+                           long long scratch_bytes, unsigned char *out, long long out_bytes, long long *frame_bytes,
+                           long long *stream_off, int *frame_minmax, unsigned char *md5, void *stream);
+
+/* ------------------------------------------------------------------------ *
  * Spectral subtraction  (replaces audio_complete.subtract, util_audio.py:221-259)
  * ------------------------------------------------------------------------ */
 typedef struct amt_subtract_args {
