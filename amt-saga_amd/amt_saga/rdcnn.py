@@ -315,6 +315,16 @@ class res_net:
         self._ensure()
         return float(self._lib.amt_rdcnn_flops_per_window(self._net))
 
+    @property
+    def fc_pooled_layers(self):
+        """How many conv layers leave their output W-pooled (mode 3: the last FFT-domain layer in front of a max pool
+        (ph, 8); 0 under AMT_FC_POOLED=0, which is read when the native net is created).  A diagnostic export of the
+        library, bound here and not in _lib.PROTOTYPES."""
+        self._ensure()
+        fn = self._lib.amt_rdcnn_fc_pooled_layers
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p]
+        return int(fn(self._net))
+
     def set_mode(self, mode):
         """0 = f32 MFMA convolutions, 1 = split-bf16 (6 bf16 MFMAs per product block), 2 = split-fp16 (3 f16 MFMAs per
         product block), 3 = split-fp16 + the FFT-domain form of the 32 -> 32 (4 x 16) layers on images of at most 20 x 561

@@ -9,6 +9,9 @@ struct FcEpilogue {
     const float *sc = nullptr; size_t sc_stride = 0;                          // identity shortcut [B][H][W][32]
     const float *sc1 = nullptr; size_t sc1_stride = 0;                        // rank-1 shortcut input [B][H][W]
     const float *sc1_w = nullptr, *sc1_s = nullptr, *sc1_t = nullptr;         // device [32]
+    // W-pooled pair in place of the spatial output (either form; identity shortcut, no next transform): wmax / wavg
+    // [B][H][W / 8][C] = max / mean of the output's columns 8 g .. 8 g + 7 (EPI = 5 of both row kernels); out_sp is then null
+    float *wmax = nullptr, *wavg = nullptr; size_t wp_stride = 0;
 };
 
 // kernel: host [4][16][32][32] (Keras layout kh, kw, cin, cout)

@@ -49,6 +49,7 @@ struct FcRowArgs {
     const float2 *tw;                            // [576] e^{-2 pi i m / 576}
     int B, H, W;
     int sf, sh;                                  // float strides of the frequency tensors: pair fp, image row h (window: 289 H 64)
+    float *wmax, *wavg; size_t wp_stride;        // W-pooled pair [B][H][W / 8][32] in place of out_sp (EPI = 5), or null
 };
 
 // One 384-thread workgroup per image row (b, h); TWO such workgroups share a CU (<= 128 registers: 4 + 4 + 2 + 2 waves fit
@@ -61,6 +62,14 @@ struct FcRowArgs {
 // in one burst after the transform (a wave's instruction covers four positions x 128 bytes = 512 contiguous bytes) and the
 // outputs leave from the registers the same way.  (Round 3 sent that form through an LDS round trip -- position-major
 // copy, compact loop, re-gather, three barriers: 16.5 us of a row's 37.)
+// EPI = 5: EPI = 2 with a shortcut tensor (not the rank-1 form), no forward transform, and the W-POOLED PAIR in place of
+// the spatial output -- for a layer whose only readers are a max pool (ph, 8) and the average pool (., 8) of a later
+// projected shortcut: wmax[b][h][g][c] = max and wavg[b][h][g][c] = 0.125 x sum of the output's positions 8 g .. 8 g + 7,
+// for g < W / 8 (the positions behind 8 (W / 8) are dropped, as both pools drop them).  A thread holds w = 24 n1 + n2: a
+// pool window never straddles an n1 block (24 = 3 x 8), and its eight positions are n2 = 8 k .. 8 k + 7 = the four lanes
+// tid & 3 of the waves 2 k and 2 k + 1.  The quad is reduced by DPP, lane tid & 3 = q keeps the windows of n1 = q mod 4,
+// the odd wave hands its halves to the even one through `buf`.  THE ORDER OF THE SUM, fixed:
+// ((v0 + v1) + (v2 + v3)) + ((v4 + v5) + (v6 + v7)); the 0.125 is exact.  amax_out stays the maximum over the whole row.
 template <bool IN_FREQ, int EPI>
 __global__ __launch_bounds__(FC_THREADS, 4) void fc_row_kernel(FcRowArgs a) {
     extern __shared__ __attribute__((aligned(16))) float fc_smem[];
@@ -112,7 +121,10 @@ __global__ __launch_bounds__(FC_THREADS, 4) void fc_row_kernel(FcRowArgs a) {
         fc_fft24<true>(x);
         // ---- epilogue on the registers
         const float inv_n = 1.0f / (float)FC_NF;
-        const int c0 = 2 * c16;
+        int c0 = 2 * c16;
+        // (opaque for the pooled form: the eight per-channel constants below are loads by c0, and hipcc otherwise issues
+        // them at the top of the kernel and carries them -- through scratch memory -- across the transforms)
+        if constexpr (EPI == 5) asm volatile("" : "+v"(c0));
         // sigmoid(x / N * s1 + t1) = 1 / (1 + 2^(x k1 + k0))
         const float k1a = -a.s1[c0] * (inv_n * FC_LOG2E), k1b = -a.s1[c0 + 1] * (inv_n * FC_LOG2E);
         const float k0a = -a.t1[c0] * FC_LOG2E, k0b = -a.t1[c0 + 1] * FC_LOG2E;
@@ -128,12 +140,13 @@ __global__ __launch_bounds__(FC_THREADS, 4) void fc_row_kernel(FcRowArgs a) {
         } else {
             // EPI = 2: identity shortcut tensor; 3: rank-1 shortcut (the projected one-channel input); 4: none.  All write
             // the spatial output.
-            constexpr bool RES = EPI == 2 || EPI == 3;
+            constexpr bool RES = EPI == 2 || EPI == 3 || EPI == 5;
+            constexpr bool IDSC = EPI == 2 || EPI == 5;
             const float s2a = RES ? a.s2[c0] : 1.f, s2b = RES ? a.s2[c0 + 1] : 1.f;
             const float t2a = RES ? a.t2[c0] : 0.f, t2b = RES ? a.t2[c0 + 1] : 0.f;
-            const float *scb = EPI == 2 ? a.sc + (size_t)b * a.sc_stride + (size_t)h * a.W * 32 : nullptr;
+            const float *scb = IDSC ? a.sc + (size_t)b * a.sc_stride + (size_t)h * a.W * 32 : nullptr;
             const float *sc1b = EPI == 3 ? a.sc1 + (size_t)b * a.sc1_stride + (size_t)h * a.W : nullptr;
-            float *ob = a.out_sp + (size_t)b * a.out_stride + (size_t)h * a.W * 32;
+            float *ob = EPI == 5 ? nullptr : a.out_sp + (size_t)b * a.out_stride + (size_t)h * a.W * 32;
             // (opaque copy: the access offsets below depend only on thread constants, and hipcc otherwise forms all of
             // them at the top of the kernel and carries them -- through scratch memory -- across the transforms)
             int n2e = n2;
@@ -152,11 +165,13 @@ __global__ __launch_bounds__(FC_THREADS, 4) void fc_row_kernel(FcRowArgs a) {
 #pragma unroll
                 for (int i = 0; i < NB; ++i) {
                     const unsigned int o = min(voff + (unsigned)(24 * (batch * NB + i) * 128), wlim);
-                    if constexpr (EPI == 2) dst[i] = fc_at<float2>(scb, o);
+                    if constexpr (IDSC) dst[i] = fc_at<float2>(scb, o);
                     if constexpr (EPI == 3) dst[i].x = fc_at<float>(sc1b, (o >> 7) * 4);
                 }
             };
             float vmax = 0.f;
+            float2 pm[24 / NB], ps[24 / NB];                // EPI = 5: quad maxima / sums of the windows of n1 = NB batch + (tid & 3)
+            static_assert(EPI != 5 || NB == 4, "one n1 of a batch per lane of the quad");
             if constexpr (RES) request(0, scv[0]);
 #pragma unroll
             for (int batch = 0; batch < 24 / NB; ++batch) {
@@ -170,7 +185,7 @@ __global__ __launch_bounds__(FC_THREADS, 4) void fc_row_kernel(FcRowArgs a) {
                     float2 v;
                     v.x = fc_sigmoid_affine(x[n1].x, k1a, k0a);
                     v.y = fc_sigmoid_affine(x[n1].y, k1b, k0b);
-                    if constexpr (EPI == 2) {
+                    if constexpr (IDSC) {
                         v.x = (v.x + scv[batch & 1][i].x) * s2a + t2a;
                         v.y = (v.y + scv[batch & 1][i].y) * s2b + t2b;
                     }
@@ -181,14 +196,55 @@ __global__ __launch_bounds__(FC_THREADS, 4) void fc_row_kernel(FcRowArgs a) {
                     }
                     if (w >= a.W) v = make_float2(0.f, 0.f);
                     vmax = fmaxf(vmax, fmaxf(fabsf(v.x), fabsf(v.y)));
-                    if (w < a.W) fc_at<float2>(ob, voff + (unsigned)(24 * n1 * 128)) = v;
-                    x[n1] = v;
+                    if constexpr (EPI == 5) {
+                        float2 m, s;
+                        m.x = fmaxf(v.x, fc_quad_xor1(v.x)); m.x = fmaxf(m.x, fc_quad_xor2(m.x));
+                        m.y = fmaxf(v.y, fc_quad_xor1(v.y)); m.y = fmaxf(m.y, fc_quad_xor2(m.y));
+                        s.x = v.x + fc_quad_xor1(v.x); s.x = s.x + fc_quad_xor2(s.x);
+                        s.y = v.y + fc_quad_xor1(v.y); s.y = s.y + fc_quad_xor2(s.y);
+                        if (i == 0 || (n2e & 3) == i) { pm[batch] = m; ps[batch] = s; }
+                    } else {
+                        if (w < a.W) fc_at<float2>(ob, voff + (unsigned)(24 * n1 * 128)) = v;
+                        x[n1] = v;
+                    }
                 }
                 if constexpr (RES) __builtin_amdgcn_sched_barrier(0);
             }
             if (a.amax_out) {
                 vmax = wave_max(vmax);
-                if ((tid & 63) == 0) atomicMax(reinterpret_cast<int *>(a.amax_out) + b, __float_as_int(vmax));
+                // (the pooled form takes its lane number from the opaque copies, as below: `tid` then does not live across the
+                // transforms)
+                const bool lane0 = EPI == 5 ? (n2e & 3) + 2 * c0 == 0 : (tid & 63) == 0;
+                if (lane0) atomicMax(reinterpret_cast<int *>(a.amax_out) + b, __float_as_int(vmax));
+            }
+            if constexpr (EPI == 5) {
+                __syncthreads();                            // every thread has read its column: `buf` is free
+                // [batch][pair of waves][lane] float4 (max.x, max.y, sum.x, sum.y): 1 KB contiguous per wave and instruction
+                // (wave and lane from the opaque copy: n2 = (tid & 3) + 4 (tid >> 6), lane = (tid & 3) + 4 c16)
+                const int wv = n2e >> 2, q = n2e & 3;
+                float4 *xch = reinterpret_cast<float4 *>(buf) + (wv >> 1) * 64 + (q + 2 * c0);
+                if (wv & 1) {
+#pragma unroll
+                    for (int k = 0; k < 24 / NB; ++k) xch[k * 192] = make_float4(pm[k].x, pm[k].y, ps[k].x, ps[k].y);
+                }
+                __syncthreads();
+                if (wv & 1) return;
+                const int G = a.W >> 3;
+                float *mb = a.wmax + (size_t)b * a.wp_stride + (size_t)h * G * 32;
+                float *ab = a.wavg + (size_t)b * a.wp_stride + (size_t)h * G * 32;
+                int cs = c0;                                // (opaque again: uniform bases + one 32-bit lane offset, formed here)
+                asm volatile("" : "+v"(cs));
+#pragma unroll
+                for (int k = 0; k < 24 / NB; ++k) {
+                    const float4 hi = xch[k * 192];
+                    const int g = 3 * (NB * k + q) + (wv >> 1);         // positions 24 n1 + 8 (wv / 2) .. + 7
+                    if (g < G) {
+                        const unsigned int o = (unsigned)((g * 32 + cs) * 4);
+                        fc_at<float2>(mb, o) = make_float2(fmaxf(pm[k].x, hi.x), fmaxf(pm[k].y, hi.y));
+                        fc_at<float2>(ab, o) = make_float2((ps[k].x + hi.z) * 0.125f, (ps[k].y + hi.w) * 0.125f);
+                    }
+                }
+                return;
             }
             if (!a.Xf) return;
         }
@@ -540,6 +596,10 @@ static int fc_row_launch_t(const FcRowArgs &a, hipStream_t st) {
 template <bool IN_FREQ>
 static int fc_row_launch(const FcRowArgs &a, hipStream_t st) {
     if (!IN_FREQ) return fc_row_launch_t<false, 1>(a, st);
+    if (a.wmax) {                                           // the W-pooled pair in place of the spatial output
+        if (!a.wavg || !a.sc || a.sc1 || a.out_sp || a.Xf || a.W < 8) return AMT_E_UNSUPPORTED;
+        return fc_row_launch_t<true, 5>(a, st);
+    }
     if (!a.out_sp) {
         if (a.sc || a.sc1 || a.amax_out || !a.Xf) return AMT_E_UNSUPPORTED;        // (no layer of the chain: a shortcut sum is always read later)
         return fc_row_launch_t<true, 1>(a, st);
@@ -583,13 +643,14 @@ int amt_fftconv_gemm(const amt_fftconv_layer *L, const float *Xf, const float *a
 int amt_fftconv_inverse_epilogue(const amt_fftconv_layer *L, const float *Yf, const FcEpilogue &ep, int B, int H, int W,
                                  float *out_sp, size_t out_stride, float *Xf_next, float *amaxf_next, float *amax_out,
                                  hipStream_t st) {
-    if (!L || !Yf || !ep.s1 || !ep.t1 || (!out_sp && !Xf_next)) return AMT_E_INVALID;
+    if (!L || !Yf || !ep.s1 || !ep.t1 || (!out_sp && !Xf_next && !ep.wmax)) return AMT_E_INVALID;
     if (Xf_next && !amaxf_next) return AMT_E_INVALID;
     if (Xf_next) AMT_HIP_CHECK(hipMemsetAsync(amaxf_next, 0, (size_t)B * sizeof(float), st));
     FcRowArgs a{};
     a.Yf = Yf; a.out_sp = out_sp; a.out_stride = out_stride; a.Xf = Xf_next; a.amaxf = amaxf_next; a.amax_out = amax_out;
     a.s1 = ep.s1; a.t1 = ep.t1; a.s2 = ep.s2; a.t2 = ep.t2; a.sc = ep.sc; a.sc_stride = ep.sc_stride;
     a.sc1 = ep.sc1; a.sc1_stride = ep.sc1_stride; a.sc1_w = ep.sc1_w; a.sc1_s = ep.sc1_s; a.sc1_t = ep.sc1_t;
+    a.wmax = ep.wmax; a.wavg = ep.wavg; a.wp_stride = ep.wp_stride;
     a.tw = L->tw; a.B = B; a.H = H; a.W = W;
     fc_strides(H, &a.sf, &a.sh);
     return fc_row_launch<true>(a, st);

@@ -75,6 +75,14 @@ template <typename T> __device__ __forceinline__ T &fc_at(void *base, unsigned i
     return *reinterpret_cast<T *>(reinterpret_cast<unsigned char *>(base) + off);
 }
 
+// the value of lane ^ 1 / lane ^ 2 inside a quad of lanes (DPP quad_perm [1, 0, 3, 2] / [2, 3, 0, 1]: no LDS crossbar)
+__device__ __forceinline__ float fc_quad_xor1(float v) {
+    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float fc_quad_xor2(float v) {
+    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xf, 0xf, true));
+}
+
 __device__ __forceinline__ int fc_scale_exp(float amax) {
     int e = 0;
     if (amax > 0.f && amax < 3.0e38f) (void)frexpf(amax, &e);

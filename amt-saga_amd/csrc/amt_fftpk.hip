@@ -69,9 +69,17 @@ struct PkRowArgs {
     const float *sc; size_t sc_stride;           // shortcut tensor [B][10][64][64], or null
     const float2 *tw;                            // [PK_TWN] e^{-2 pi i m / 1152}
     int B;
+    float *wmax, *wavg; size_t wp_stride;        // W-pooled pair [B][10][8][64] in place of out_sp (EPI = 5), or null
 };
 
 // EPI (IN_FREQ only): 1 = no shortcut, no spatial output; 2 = shortcut tensor + spatial output; 4 = spatial output only.
+// 5 = 2 without a forward transform and with the W-POOLED PAIR of amt_fftconv.hip (EPI = 5 there) in place of the spatial
+// output: wmax / wavg [b][row][g][c] = max / 0.125 x sum of the output's columns 8 g .. 8 g + 7.  A thread's points are
+// spread over the image (row n1 / 2, column 48 (n1 & 1) + n2), so the outputs go position-major through `buf` (free after
+// the second transposition's reads; pitch PK_WPS per channel pair) and a compact loop reduces the 640 (row, g, pair)
+// windows of the workgroup; THE ORDER OF THE SUM is the row form's: ((v0 + v1) + (v2 + v3)) + ((v4 + v5) + (v6 + v7)).
+#define PK_WPS 1288                     // dwords per channel pair of that copy (10 x 64 positions x 2 + 8: a half wave's 64-bit
+                                        // writes, 8 pairs x 4 columns, touch every bank pair once)
 template <bool IN_FREQ, int EPI>
 __global__ __launch_bounds__(PK_THREADS, 4) void pk_row_kernel(PkRowArgs a) {
     extern __shared__ __attribute__((aligned(16))) float pk_smem[];
@@ -145,11 +153,13 @@ __global__ __launch_bounds__(PK_THREADS, 4) void pk_row_kernel(PkRowArgs a) {
                 x[n1] = v;
             }
         } else {
-            constexpr bool RES = EPI == 2;
+            constexpr bool RES = EPI == 2 || EPI == 5;
             const float s2a = RES ? a.s2[c0] : 1.f, s2b = RES ? a.s2[c0 + 1] : 1.f;
             const float t2a = RES ? a.t2[c0] : 0.f, t2b = RES ? a.t2[c0 + 1] : 0.f;
             const float *scb = RES ? a.sc + (size_t)b * a.sc_stride : nullptr;
-            float *ob = a.out_sp + (size_t)b * a.out_stride;
+            float *ob = EPI == 5 ? nullptr : a.out_sp + (size_t)b * a.out_stride;
+            if constexpr (EPI == 5) __syncthreads();        // every thread has read its column: `buf` takes the outputs
+            float *wb = buf + p8 * PK_WPS + 2 * n2;         // EPI = 5: (row, column) of pair p8 at 2 (64 row + column)
             // byte offset of (column, channel pair) inside an image row: even registers column n2, odd ones 48 + n2
             // (clamped to the row: lanes beyond column 63 are masked, their address must still be inside the tensor)
             const unsigned int ve = (unsigned)((n2 * PK_C + c0) * 4);
@@ -184,16 +194,43 @@ __global__ __launch_bounds__(PK_THREADS, 4) void pk_row_kernel(PkRowArgs a) {
                     const bool ok = !(n1 & 1) || odd_ok;
                     if (!ok) v = make_float2(0.f, 0.f);
                     vmax = fmaxf(vmax, fmaxf(fabsf(v.x), fabsf(v.y)));
-                    if (ok) fc_at<float2>(ob + (n1 >> 1) * PK_W * PK_C, (n1 & 1) ? vo : ve) = v;
-                    x[n1] = v;
+                    if constexpr (EPI == 5) {
+                        if (ok) *reinterpret_cast<float2 *>(wb + 2 * ((n1 >> 1) * PK_W + 48 * (n1 & 1))) = v;
+                    } else {
+                        if (ok) fc_at<float2>(ob + (n1 >> 1) * PK_W * PK_C, (n1 & 1) ? vo : ve) = v;
+                        x[n1] = v;
+                    }
                 }
                 if constexpr (RES) __builtin_amdgcn_sched_barrier(0);
             }
+            if constexpr (EPI != 5) {
 #pragma unroll
-            for (int n1 = 2 * PK_H; n1 < 24; ++n1) x[n1] = make_float2(0.f, 0.f);
+                for (int n1 = 2 * PK_H; n1 < 24; ++n1) x[n1] = make_float2(0.f, 0.f);
+            }
             if (a.amax_out) {
                 vmax = wave_max(vmax);
                 if ((tid & 63) == 0) atomicMax(reinterpret_cast<int *>(a.amax_out) + b, __float_as_int(vmax));
+            }
+            if constexpr (EPI == 5) {
+                __syncthreads();
+                float *mb = a.wmax + (size_t)b * a.wp_stride + pg * 16;
+                float *ab = a.wavg + (size_t)b * a.wp_stride + pg * 16;
+                int pq = p8;                                // (opaque copies: tid = 8 n2 + p8, formed here -- see fc_row_kernel)
+                asm volatile("" : "+v"(pq));
+                for (int o = 8 * n2 + pq; o < PK_H * (PK_W / 8) * 8; o += PK_THREADS) {
+                    const int p = o & 7, gi = o >> 3;       // gi = 8 row + g: positions 8 gi .. 8 gi + 7 of the copy
+                    const float4 *src = reinterpret_cast<const float4 *>(buf + p * PK_WPS + 16 * gi);
+                    const float4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
+                    float2 m, sm;
+                    m.x = fmaxf(fmaxf(fmaxf(q0.x, q0.z), fmaxf(q1.x, q1.z)), fmaxf(fmaxf(q2.x, q2.z), fmaxf(q3.x, q3.z)));
+                    m.y = fmaxf(fmaxf(fmaxf(q0.y, q0.w), fmaxf(q1.y, q1.w)), fmaxf(fmaxf(q2.y, q2.w), fmaxf(q3.y, q3.w)));
+                    sm.x = ((q0.x + q0.z) + (q1.x + q1.z)) + ((q2.x + q2.z) + (q3.x + q3.z));
+                    sm.y = ((q0.y + q0.w) + (q1.y + q1.w)) + ((q2.y + q2.w) + (q3.y + q3.w));
+                    const unsigned int oo = (unsigned)((gi * PK_C + 2 * p) * 4);
+                    fc_at<float2>(mb, oo) = m;
+                    fc_at<float2>(ab, oo) = make_float2(sm.x * 0.125f, sm.y * 0.125f);
+                }
+                return;
             }
             if (!a.Xf) return;
         }
@@ -571,14 +608,19 @@ int amt_fftpk_gemm(const amt_fftpk_layer *L, const float *Xf, const float *amaxf
 
 int amt_fftpk_inverse_epilogue(const amt_fftpk_layer *L, const float *Yf, const FcEpilogue &ep, int B, float *out_sp, size_t out_stride,
                                float *Xf_next, float *amaxf_next, float *amax_out, hipStream_t st) {
-    if (!L || !Yf || !ep.s1 || !ep.t1 || (!out_sp && !Xf_next) || B <= 0) return AMT_E_INVALID;
+    if (!L || !Yf || !ep.s1 || !ep.t1 || (!out_sp && !Xf_next && !ep.wmax) || B <= 0) return AMT_E_INVALID;
     if (Xf_next && !amaxf_next) return AMT_E_INVALID;
     if (ep.sc1) return AMT_E_UNSUPPORTED;
     if (Xf_next) AMT_HIP_CHECK(hipMemsetAsync(amaxf_next, 0, (size_t)B * sizeof(float), st));
     PkRowArgs a{};
     a.Yf = Yf; a.out_sp = out_sp; a.out_stride = out_stride; a.Xf = Xf_next; a.amaxf = amaxf_next; a.amax_out = amax_out;
     a.s1 = ep.s1; a.t1 = ep.t1; a.s2 = ep.s2; a.t2 = ep.t2; a.sc = ep.sc; a.sc_stride = ep.sc_stride;
+    a.wmax = ep.wmax; a.wavg = ep.wavg; a.wp_stride = ep.wp_stride;
     a.tw = L->tw; a.B = B;
+    if (a.wmax) {                                           // the W-pooled pair in place of the spatial output
+        if (!a.wavg || !a.sc || !a.s2 || !a.t2 || out_sp || Xf_next) return AMT_E_UNSUPPORTED;
+        return pk_row_launch_t<true, 5>(a, st);
+    }
     if (!out_sp) {
         if (a.sc || a.amax_out) return AMT_E_UNSUPPORTED;
         return pk_row_launch_t<true, 1>(a, st);

@@ -82,6 +82,8 @@ struct amt_rdcnn {
     int flat = 0;
     double flops = 0;
     mutable int mode = 0;      // 0: f32 MFMA, 1: split-bf16 where built, 2: split-fp16 where built, 3: 2 + FFT-domain forms
+    bool fc_pooled = true;     // mode 3: the last FFT-domain layer in front of a max pool (ph, 8) leaves its output W-pooled
+                               // (fc_wpooled_ok); AMT_FC_POOLED=0, read when the net is created, keeps the full-size output
 };
 
 // host bytes -> a new device allocation owned by the net
@@ -446,6 +448,10 @@ static bool impl_is_fft(ConvImpl impl) { return impl == IMPL_FFT_ROW || impl == 
 static bool impl_forms_rank1_shortcut(ConvImpl impl, const ConvOp &c) {
     return impl == IMPL_FFT_ROW || (impl == IMPL_F16X3 && (!c.f16.masked || c.f16.wm_ms > 0));
 }
+// ... and does so for this projection: 1 x 1 kernel on the unpooled one-channel input
+static bool shortcut_is_rank1(ConvImpl impl, const ConvOp &c, const ProjOp &pr) {
+    return impl_forms_rank1_shortcut(impl, c) && pr.cin == 1 && pr.ph == 1 && pr.pw == 1 && pr.w;
+}
 // the kernel leaves max |output| per window for the split-fp16 scaling of its consumer
 static bool impl_writes_amax(ConvImpl impl) {
     return impl == IMPL_FIRST_MFMA || impl_is_fft(impl) || impl == IMPL_F16X3;
@@ -602,6 +608,7 @@ int amt_rdcnn_create(amt_rdcnn **out, const amt_rdcnn_desc *desc, const float *w
     if (!tp.shortcut_ok) return AMT_E_UNSUPPORTED;
     amt_rdcnn *n = new amt_rdcnn();
     n->d = d;
+    if (const char *e = getenv("AMT_FC_POOLED")) n->fc_pooled = e[0] != '0';
     n->flat = tp.flat;
     n->towers.resize(d.n_towers);
     for (int t = 0; t < d.n_towers; ++t) {
@@ -665,6 +672,18 @@ int amt_rdcnn_set_mode(amt_rdcnn *net, int mode) {
     }
     net->mode = mode;
     return AMT_OK;
+}
+
+// Diagnostic export (not in include/amt_saga.h; tests/test_gpu_pooled_epilogue.py): how many layers of the net take the
+// W-pooled epilogue in its current mode (fc_wpooled_ok, below)
+static bool fc_wpooled_ok(const amt_rdcnn *net, const Tower &tw, int i, ConvImpl impl, int H, int W);
+int amt_rdcnn_fc_pooled_layers(const amt_rdcnn *net) {
+    if (!net) return AMT_E_INVALID;
+    int n = 0;
+    for (const Tower &tw : net->towers)
+        for (size_t i = 0; i < tw.convs.size(); ++i)
+            n += fc_wpooled_ok(net, tw, (int)i, conv_impl(tw.convs[i], net->mode), tw.convs[i].H, tw.convs[i].W) ? 1 : 0;
+    return n;
 }
 
 int amt_rdcnn_profile(amt_rdcnn *net, int enable) {
@@ -784,13 +803,33 @@ static int prof_end(const amt_rdcnn *net, const ProfPending &pp, hipStream_t st)
 // transformed in Xf] -> per-frequency GEMM -> inverse + epilogue [+ forward transform for the next such layer]; the
 // spatial output is written only where something reads it (a later shortcut, a pooling, a layer of another kind)
 struct FcBufs { float *Xf, *Yf, *amaxf; };
+// The W-pooled epilogue (FcEpilogue::wmax / wavg, EPI = 5 of both row kernels) in place of layer i's full-size output.
+// THE rule: an FFT-form layer (row or packed) that adds a shortcut TENSOR (the block's input or its projection; not the
+// rank-1 form), a max pool (ph, 8) behind it, and no reader of its output that the pooled pair cannot serve.  The
+// readers are that max pool -- from wmax, with (ph, 1) -- and at most the next closing layer's projected shortcut, whose
+// source is this output: it is served from wavg with (sc_ph, 1) only if its average pool spans the max pool's 8 columns.
+// That is not automatic: a 6 x 20 image pooled (2, 8) gives a shortcut pool of (3, 10).  (Rows are not pooled by the
+// epilogue, so the shortcut's row count is free: 3 x 17 gives (3, 8) against (2, 8).)
+static bool fc_wpooled_ok(const amt_rdcnn *net, const Tower &tw, int i, ConvImpl impl, int H, int W) {
+    const ConvOp &c = tw.convs[i];
+    if (!net->fc_pooled || !impl_is_fft(impl) || !c.pool_after || tw.pw != 8 || W < 8) return false;
+    if (!c.residual || (c.sc_proj >= 0 && shortcut_is_rank1(impl, c, tw.projs[c.sc_proj]))) return false;
+    for (size_t j = (size_t)i + 1; j < tw.convs.size(); ++j) {
+        const ConvOp &r = tw.convs[j];
+        if (!r.residual) continue;
+        if (r.sc_proj < 0) return false;
+        const ProjOp &pr = tw.projs[r.sc_proj];
+        return pr.H == H && pr.W == W && pr.cin == c.cout && pr.pw == 8 && pr.WO == W / 8;
+    }
+    return true;
+}
 static int run_fc(const ConvOp &c, const float *in, size_t in_stride, bool have_xf, int Bc, const FcEpilogue &ep,
                   const FcBufs &f, float *o, size_t o_stride, bool next_fc, float *amax_o, hipStream_t st) {
     int rc = AMT_OK;
     if (!have_xf) rc = fc_forward_fft(c.fc, in, in_stride, Bc, f.Xf, f.amaxf, st);
     if (rc == AMT_OK) rc = fc_gemm(c.fc, f.Xf, f.amaxf, Bc, f.Yf, st);
     if (rc != AMT_OK) return rc;
-    const bool need_sp = !next_fc || c.residual;
+    const bool need_sp = !ep.wmax && (!next_fc || c.residual);
     return fc_inverse_epilogue(c.fc, f.Yf, ep, Bc, need_sp ? o : nullptr, o_stride, next_fc ? f.Xf : nullptr, f.amaxf,
                                next_fc ? nullptr : amax_o, st);
 }
@@ -825,6 +864,7 @@ int amt_rdcnn_forward(const amt_rdcnn *net, const float *const *x, int B, float 
                 RD_TRY(launch_absmax(cur, cur_stride, cur_stride, Bc, amax_row(0), st));
             }
             const float *p0 = cur; size_t p0_stride = cur_stride;
+            bool p0_wpooled = false;                     // p0 is the W-pooled average of a layer's output (fc_wpooled_ok)
             int H = tw.in_h, W = tw.in_w;
             const int L = (int)tw.convs.size();
             bool xf_valid = false;                       // mode 3: the previous layer left its output transformed in Xf
@@ -845,12 +885,13 @@ int amt_rdcnn_forward(const amt_rdcnn *net, const float *const *x, int B, float 
                 const ProjOp *rank1 = nullptr;
                 if (c.residual && c.sc_proj >= 0) {
                     const ProjOp &pr = tw.projs[c.sc_proj];
-                    if (impl_forms_rank1_shortcut(impl, c) && pr.cin == 1 && pr.ph == 1 && pr.pw == 1 && pr.w) {
+                    if (shortcut_is_rank1(impl, c, pr)) {
                         rank1 = &pr;
                     } else {
                         float *sb = pick(cur, p0, o);
                         ProjParams pp{p0, p0_stride, sb, (size_t)pr.HO * pr.WO * pr.cout, pr.w, pr.s, pr.t,
                                       Bc, pr.H, pr.W, pr.cin, pr.cout, pr.ph, pr.pw, pr.HO, pr.WO};
+                        if (p0_wpooled) { pp.W = pr.W / 8; pp.PW = 1; }      // 1 / (sc_ph * 1) x the epilogue's 0.125 = 1 / (sc_ph * 8)
                         proj_kernel<<<dim3((pr.WO + PJ_TW - 1) / PJ_TW, pr.HO, Bc), 256,
                                       (size_t)PJ_TW * pr.cin * sizeof(float), st>>>(pp);
                         sc = sb; sc_stride = (size_t)pr.HO * pr.WO * pr.cout;
@@ -860,6 +901,9 @@ int amt_rdcnn_forward(const amt_rdcnn *net, const float *const *x, int B, float 
                 }
                 const float *s2 = c.residual ? c.s2 : nullptr, *t2 = c.residual ? c.t2 : nullptr;
                 float *amax_o = mode >= 2 ? amax_row(i + 1) : nullptr;
+                // the pooled pair shares the layer's output buffer: [Bc] wavg, then [Bc] wmax (a quarter of it together)
+                const bool wpooled = fc_wpooled_ok(net, tw, i, impl, H, W);
+                const size_t wp_stride = (size_t)H * (W / 8) * c.cout;
                 ProfPending prof{nullptr, nullptr, t, i, Bc};
                 RD_TRY(prof_begin(net, prof, st));
                 switch (impl) {
@@ -878,6 +922,7 @@ int amt_rdcnn_forward(const amt_rdcnn *net, const float *const *x, int B, float 
                     if (rank1) { ep.sc1 = p0; ep.sc1_stride = p0_stride; ep.sc1_w = rank1->w; ep.sc1_s = rank1->s; ep.sc1_t = rank1->t; }
                     else { ep.sc = sc; ep.sc_stride = sc_stride; }
                     const bool next_fc = i + 1 < L && !c.pool_after && conv_impl(tw.convs[i + 1], mode) == impl;
+                    if (wpooled) { ep.wavg = o; ep.wmax = o + (size_t)Bc * wp_stride; ep.wp_stride = wp_stride; }
                     RD_TRY(run_fc(c, cur, cur_stride, xf_valid, Bc, ep, fcb, o, o_stride, next_fc, amax_o, st));
                     xf_valid = next_fc;
                     break;
@@ -898,15 +943,16 @@ int amt_rdcnn_forward(const amt_rdcnn *net, const float *const *x, int B, float 
                     // kernel is not built for; none of the reference's head topologies)
                     RD_TRY(launch_absmax(o, (size_t)H * W * c.cout, o_stride, Bc, amax_o, st));
                 RD_TRY(prof_end(net, prof, st));
-                if (c.residual) { p0 = o; p0_stride = o_stride; }
+                if (c.residual) { p0 = o; p0_stride = wpooled ? wp_stride : o_stride; p0_wpooled = wpooled; }
                 cur = o; cur_stride = o_stride;
+                if (wpooled) { cur = o + (size_t)Bc * wp_stride; cur_stride = wp_stride; }
                 if (c.pool_after) {
                     const int HO = H / tw.ph, WO = W / tw.pw;
                     const bool last = (i == L - 1);
                     float *po = last ? flatbuf + flat_off : pick(cur, p0, nullptr);
                     const size_t po_stride = last ? (size_t)flat : (size_t)HO * WO * c.cout;
                     maxpool_kernel<<<grid_for((size_t)Bc * HO * WO * c.cout / 4), 256, 0, st>>>(
-                        cur, cur_stride, po, po_stride, Bc, H, W, c.cout, tw.ph, tw.pw, HO, WO);
+                        cur, cur_stride, po, po_stride, Bc, H, wpooled ? W / 8 : W, c.cout, tw.ph, wpooled ? 1 : tw.pw, HO, WO);
                     cur = po; cur_stride = po_stride; H = HO; W = WO;
                 }
             }
