@@ -1117,3 +1117,148 @@ def save_flac(waves, paths, sr, bps=24):
     for data, path in zip(files, paths):
         with open(path, 'wb') as f:
             f.write(data)
+
+
+# ======================================================================================
+# FLAC decoding on the device (the librosa.load of audio_from_file, util_audio.py:962-964)
+# ======================================================================================
+FLAC_VERIFY = {True: 2, 'crc': 1, False: 0}
+# scratch a file may ask for, in samples: the real frames hold `total` (plus less than one block); the recorded libFLAC
+# files carry 0.6 false candidates per frame.  16 x leaves room for false ones that declare large blocks.
+FLAC_SLOT_FACTOR, FLAC_SLOT_SLACK = 16, 1 << 20
+_FLAC_FRAME_ERRORS = {1: 'the stream ends inside the frame', 2: 'a reserved or impossible code',
+                      3: 'a sample outside its bit range', 4: 'bits per sample above 24 are not supported',
+                      5: 'a table entry out of range'}
+
+
+def _flac_tables(datas, verify):
+    """The host's O(frames) share of flac_decode, no GPU involved: argument checks, STREAMINFO and the candidate
+    headers of every file.  Returns (infos, stream_meta int64 [n, 9], cand_meta int64 [n_cand, 7], md5 uint8 [n, 16],
+    slot_ints, out_values)."""
+    from . import flac as _flac
+    if not isinstance(verify, (bool, str)) or verify not in FLAC_VERIFY:
+        raise ValueError("Requested attribute does not exist: verify must be True, 'crc' or False")
+    if isinstance(datas, (bytes, bytearray, memoryview)) or not isinstance(datas, (list, tuple)):
+        raise ValueError('Invalid Input shape. Expected: a list of bytes . Got: %s' % type(datas).__name__)
+    if not datas:
+        raise ValueError('Invalid Input shape. Expected: at least one file . Got: an empty list')
+    infos, sm, cm, md5s = [], [], [], []
+    off = slot = out = 0
+    for i, d in enumerate(datas):
+        if not isinstance(d, (bytes, bytearray)):
+            raise ValueError('Invalid Input shape. Expected: a list of bytes . Got: %s in it' % type(d).__name__)
+        sr, ch, bps, total, md5, first = _flac.read_streaminfo(d)
+        if bps > 24:
+            raise ValueError('FLAC file %d: %d bits per sample; above 24 is not supported (float32 is exact to 24)'
+                             % (i, bps))
+        pos, hdr, bs, ca, fb = _flac.frame_candidates(d, first)
+        fb = np.where(fb == 0, bps, fb)
+        lo = sum(len(c) for c in cm)
+        slots = slot + np.concatenate([[0], np.cumsum(bs.astype(np.int64) * ch)])
+        cm.append(np.stack([np.full(len(pos), i, np.int64), pos, hdr.astype(np.int64), bs.astype(np.int64),
+                            ca.astype(np.int64), fb.astype(np.int64), slots[:-1]], axis=1).reshape(-1, 7))
+        # every candidate, false ones included, gets a slot: a file of nothing but plausible headers that declare large
+        # blocks is refused here, before it asks for scratch it could never fill
+        if int(slots[-1]) - slot > FLAC_SLOT_FACTOR * total * ch + FLAC_SLOT_SLACK:
+            raise ValueError('FLAC file %d: its %d candidate frame headers declare %d samples for the %d of the stream '
+                             '(more than %d x + %d): refused' % (i, len(pos), int(bs.astype(np.int64).sum()), total,
+                                                                 FLAC_SLOT_FACTOR, FLAC_SLOT_SLACK // ch))
+        slot = int(slots[-1])
+        sm.append([off, len(d), first, ch, bps, total, out, lo, lo + len(pos)])
+        infos.append((sr, ch, bps, total))
+        md5s.append(np.frombuffer(md5, np.uint8))
+        off += len(d)
+        out += total * ch
+    return (infos, np.asarray(sm, np.int64).reshape(-1, 9), np.concatenate(cm).astype(np.int64).reshape(-1, 7),
+            np.stack(md5s), slot, out)
+
+
+def flac_decode_streams(datas, verify=True, pcm=False):
+    """amt_flac_decode_ragged for the files `datas` (a list of bytes), one call on the current stream, nothing
+    synchronised and nothing raised for a damaged stream: returns a dict of device tensors -- out float32 [values],
+    pcm int32 [values] or None, status int64 [n, 4], cand_out int64 [n_cand, 3], md5 uint8 [n, 16] -- and the host
+    tables infos [(sr, channels, bps, total)], stream_meta, cand_meta (see include/amt_saga.h)."""
+    infos, sm, cm, md5, slot_ints, out_values = _flac_tables(datas, verify)
+    lib = _lib.load()
+    n, n_cand = len(infos), len(cm)
+    dev = torch.device('cuda', torch.cuda.current_device())
+    data = torch.frombuffer(bytearray(b''.join(datas)), dtype=torch.uint8).to(dev)
+    tab = torch.from_numpy(np.concatenate([sm.reshape(-1), cm.reshape(-1)])).to(dev)
+    sm_d, cm_d = tab[:sm.size], tab[sm.size:]
+    md5_in = torch.from_numpy(md5.copy()).to(dev)
+    need = int(lib.amt_flac_decode_scratch_bytes(n_cand, slot_ints))
+    if need < 0:
+        _lib.check(_lib.AMT_E_INVALID)
+    scratch = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
+    out = torch.empty((max(out_values, 1),), dtype=torch.float32, device=dev)
+    out_i = torch.empty((max(out_values, 1),), dtype=torch.int32, device=dev) if pcm else None
+    status = torch.empty((n, 4), dtype=torch.int64, device=dev)
+    cand_out = torch.empty((max(n_cand, 1), 3), dtype=torch.int64, device=dev)
+    md5_out = torch.zeros((n, 16), dtype=torch.uint8, device=dev)
+    # (a one-element buffer stands where a table would be empty: the ABI refuses NULL)
+    cm_p = cm_d if n_cand else torch.zeros((7,), dtype=torch.int64, device=dev)
+    _lib.check(lib.amt_flac_decode_ragged(
+        ptr(data), data.numel(), ptr(sm_d), n, ptr(cm_p), n_cand, ptr(md5_in), FLAC_VERIFY[verify], ptr(scratch),
+        scratch.numel(), slot_ints, ptr(out), ptr(out_i) if pcm else None, out_values, ptr(status), ptr(cand_out),
+        ptr(md5_out), stream_ptr()))
+    return dict(out=out, pcm=out_i, status=status, cand_out=cand_out[:n_cand], md5=md5_out, infos=infos,
+                stream_meta=sm, cand_meta=cm)
+
+
+def flac_status_error(row, cand_meta=None, cand_err=None):
+    """The ValueError text of one stream's status row (host integers), or None: the reader's texts where the condition
+    is the reader's."""
+    code, at, crc_at, md5_bad = (int(v) for v in row)
+    big = (1 << 63) - 1
+    if code == 5:
+        return 'FLAC decode: a table entry out of range'
+    if crc_at != big and (code == 0 or crc_at < at):
+        return 'FLAC frame CRC-16 mismatch at byte %d' % crc_at
+    if code == 1:
+        return 'lost sync at byte %d' % at
+    if code == 2:
+        return 'lost sync at byte %d: the frame there does not decode' % at
+    if md5_bad:
+        return 'FLAC STREAMINFO MD5 mismatch: decoded samples differ from the encoded audio'
+    return None
+
+
+def flac_decode(datas, verify=True, pcm=False):
+    """audio_from_file (util_audio.py:962-964) without the host reader: the files `datas` (a list of bytes) decoded on
+    the device in ONE call.  Returns a list of (wave, sr, bps) -- wave a float32 device tensor pcm 2^-(bps-1), [n] for
+    mono and [n, channels] otherwise, views of one buffer -- or (wave, sr, bps, pcm int32) with pcm=True.
+    verify: True = CRC-16 of every frame and the STREAMINFO MD5 when the file carries one, 'crc' = CRC-16 only (the MD5
+    is one sequential chain per file), False = neither.  CRC-8 is checked in every case: a header that fails it is no
+    candidate.  The status of all files comes back in one small copy; a damaged file raises ValueError."""
+    r = flac_decode_streams(datas, verify=verify, pcm=pcm)
+    status = r['status'].cpu().tolist()
+    res = []
+    for i, ((sr, ch, bps, total), row, m) in enumerate(zip(r['infos'], status, r['stream_meta'].tolist())):
+        msg = flac_status_error(row)
+        if msg is not None:
+            if row[0] == 2:                                          # which refusal: one more small copy, errors only
+                at = int(row[1])
+                cmeta = r['cand_meta']
+                hit = np.flatnonzero((cmeta[:, 0] == i) & (cmeta[:, 1] == at))
+                if len(hit):
+                    e = int(r['cand_out'][int(hit[0]), 1].item())
+                    msg += ' (%s)' % _FLAC_FRAME_ERRORS.get(e, 'error %d' % e)
+            raise ValueError(msg + (' (file %d of the call)' % i if len(status) > 1 else ''))
+        base = m[6]
+
+        def view(t):
+            v = t[base:base + total * ch]
+            return v if ch == 1 else v.view(total, ch)
+        res.append((view(r['out']), sr, bps) + ((view(r['pcm']),) if pcm else ()))
+    return res
+
+
+def load_flac(paths, verify=True, pcm=False):
+    """flac_decode of the files at `paths` (one path or a list), read whole and decoded in one call."""
+    single = isinstance(paths, (str, bytes, os.PathLike))
+    datas = []
+    for p in ([paths] if single else list(paths)):
+        with open(p, 'rb') as f:
+            datas.append(f.read())
+    res = flac_decode(datas, verify=verify, pcm=pcm)
+    return res[0] if single else res

@@ -234,6 +234,95 @@ def load_float(path):
 
 
 # ------------------------------------------------------------------------------------
+# host side of the device reader (audio.flac_decode): O(frames) work, nothing per bit or per sample
+# ------------------------------------------------------------------------------------
+def read_streaminfo(data):
+    """(sample rate, channels, bps, total samples, md5, first frame byte) of a FLAC file's bytes; every metadata block
+    is skipped by its length, whatever its type."""
+    if bytes(data[:4]) != b'fLaC':
+        raise ValueError('not a FLAC file')
+    pos, info = 4, None
+    while True:
+        if pos + 4 > len(data):
+            raise ValueError('FLAC metadata ends at byte %d, inside a block header' % len(data))
+        last, btype = data[pos] >> 7, data[pos] & 0x7F
+        blen = int.from_bytes(data[pos + 1:pos + 4], 'big')
+        if pos + 4 + blen > len(data):
+            raise ValueError('FLAC metadata ends at byte %d, inside the block at byte %d' % (len(data), pos))
+        if btype == 0:
+            if blen < 34:
+                raise ValueError('FLAC STREAMINFO block of %d bytes' % blen)
+            v = int.from_bytes(data[pos + 14:pos + 22], 'big')
+            info = (v >> 44, ((v >> 41) & 7) + 1, ((v >> 36) & 31) + 1, v & ((1 << 36) - 1),
+                    bytes(data[pos + 22:pos + 38]))
+        pos += 4 + blen
+        if last:
+            break
+    if info is None:
+        raise ValueError('FLAC file without a STREAMINFO block')
+    return info + (pos,)
+
+
+_CRC8_TAB = None
+_BS_CODE = {1: 192, 2: 576, 3: 1152, 4: 2304, 5: 4608}
+_SS_CODE = {0: 0, 1: 8, 2: 12, 4: 16, 5: 20, 6: 24}
+
+
+def frame_candidates(data, first_byte):
+    """Every position >= first_byte that carries a plausible frame header: the sync pattern FF F8 / FF F9 (found with
+    numpy, no Python loop per byte), then per candidate the reserved bits and codes, a well-formed UTF-8 style number of
+    1 .. 7 bytes, the block-size and sample-rate tails and CRC-8.  Returns (position int64, header bytes int32 -- CRC-8
+    included --, block size int32, channel assignment int32, frame bps int32 -- 0: STREAMINFO's --), ascending.
+    A sync pattern inside a payload can pass all of this; the chain walk of the decoder is what tells it apart."""
+    global _CRC8_TAB
+    if _CRC8_TAB is None:
+        _CRC8_TAB = [_crc8(bytes([i])) for i in range(256)]
+    a = np.frombuffer(data, dtype=np.uint8)
+    n = len(a)
+    hits = np.flatnonzero((a[first_byte:n - 1] == 0xFF) & ((a[first_byte + 1:] & 0xFE) == 0xF8)) + first_byte \
+        if n - first_byte >= 2 else np.zeros(0, np.int64)
+    rows = []
+    for p in hits.tolist():
+        h = data[p:p + 16]
+        if len(h) < 6:
+            continue
+        bs_code, sr_code, ca, ss_code = h[2] >> 4, h[2] & 15, h[3] >> 4, (h[3] >> 1) & 7
+        if bs_code == 0 or sr_code == 15 or ca > 10 or ss_code not in _SS_CODE or h[3] & 1:
+            continue
+        lead = h[4]
+        nnum = 1 if lead < 0x80 else 8 - (lead ^ 0xFF).bit_length() if lead != 0xFF else 0
+        if nnum < 1 or nnum == 1 and lead >= 0x80:
+            continue
+        at = 4 + nnum
+        if at > len(h) or any(b & 0xC0 != 0x80 for b in h[5:at]):
+            continue
+        if bs_code == 6:
+            if at + 1 > len(h):
+                continue
+            bs = h[at] + 1
+            at += 1
+        elif bs_code == 7:
+            if at + 2 > len(h):
+                continue
+            bs = (h[at] << 8 | h[at + 1]) + 1
+            at += 2
+        else:
+            bs = _BS_CODE[bs_code] if bs_code < 8 else 256 << (bs_code - 8)
+        at += 1 if sr_code == 12 else 2 if sr_code in (13, 14) else 0
+        if at + 1 > len(h):
+            continue
+        crc = 0
+        for b in h[:at]:
+            crc = _CRC8_TAB[crc ^ b]
+        if crc != h[at]:
+            continue
+        rows.append((p, at + 1, bs, ca, _SS_CODE[ss_code]))
+    t = np.asarray(rows, dtype=np.int64).reshape(-1, 5)
+    return (t[:, 0].copy(), t[:, 1].astype(np.int32), t[:, 2].astype(np.int32), t[:, 3].astype(np.int32),
+            t[:, 4].astype(np.int32))
+
+
+# ------------------------------------------------------------------------------------
 # writer
 # ------------------------------------------------------------------------------------
 def _crc8(data):

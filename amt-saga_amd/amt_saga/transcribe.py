@@ -21,6 +21,8 @@ provide for the inference direction:
     group, <input stem>.group<g>.flac (the reference's _guessed.flac, training.py:426-447, at song length).
     --flac {host,device}: the writer of those files -- host (default): amt_saga.flac's VERBATIM writer; device: the HIP
     encoder (audio.save_flac), a song's residual and stems in one call, compressed.
+    --decode {host,device}: the reader of the input files -- host (default): amt_saga.flac's reader; device: the HIP
+    decoder (audio.load_flac), --slots files per decode call with --songs, the samples never on the host.
 
 Weights: a directory with {timing_start,timing_end,pitch,instrument,velocity}.npz in the
 naming of amt_saga/rdcnn.py; without it the heads carry their seeded synthetic weights (the
@@ -171,6 +173,14 @@ _FLAC_HELP = ("writer of --residual / --residual-dir / --stems-dir: 'host' = the
               "default), 'device' = the HIP encoder (fixed predictors + Rice coding, one call per song)")
 
 
+DECODERS = ('host', 'device')
+_DECODE_HELP = ("reader of the input files: 'host' = the pure-Python reader (the default), 'device' = the HIP decoder "
+                "(--songs: --slots files per decode call, as the queue pulls them; CRC-8, CRC-16 and MD5 verified as the "
+                "host reader does).  A mono "
+                "file gives the same samples and the same .mid either way; a file with channels and no --sr is mixed "
+                "down in float32 on the device and in float64 on the host, so its samples may differ in the last bit")
+
+
 def write_song_audio(rate, residual=None, residual_path=None, stems=None, stems_dir=None, name=None, flac='host'):
     """What a song walk kept, as 24-bit FLAC at `rate`: `residual` (1-d device tensor) to residual_path, and / or the rows
     of `stems` [G, samples] to <stems_dir>/<name>.group<g>.flac, g the reference group id of the row (CLI_GROUPS).
@@ -223,6 +233,7 @@ def main_songs(argv):
                     help='write <stem>.group<g>.flac per song and instrument group as it finishes: what the subtractions '
                          'took out of the song, 24-bit FLAC at the rate the model runs at')
     ap.add_argument('--flac', default='host', choices=FLAC_WRITERS, help=_FLAC_HELP)
+    ap.add_argument('--decode', default='host', choices=DECODERS, help=_DECODE_HELP)
     a = ap.parse_args(argv)
     os.makedirs(a.out_dir, exist_ok=True)
     keep, keep_stems = a.residual_dir is not None, a.stems_dir is not None
@@ -235,7 +246,7 @@ def main_songs(argv):
     if a.sr is not None:
         if a.sr <= 0:
             raise SystemExit('--sr: the rate must be positive')
-        queue = iter_transcribe_songs((flac.load_float(f) for f in a.songs), Hyperparams(N=2048, sr=a.sr), iters=a.iters,
+        queue = iter_transcribe_songs(_load_songs(a, flac), Hyperparams(N=2048, sr=a.sr), iters=a.iters,
                                       weights_dir=a.weights, guess=a.guess, slots=a.slots, residual=keep,
                                       stems=keep_stems, groups=CLI_GROUPS)
         rate = a.sr
@@ -251,9 +262,36 @@ def main_songs(argv):
                          stems=item[-1] if keep_stems else None, stems_dir=a.stems_dir, name=stems[i], flac=a.flac)
 
 
+def _load_songs(a, flac):
+    """(waveform, rate) of every --songs file in order: read one by one on the host, or -- with --decode device -- in
+    decode calls of --slots files each, as the queue pulls them, the waveforms device tensors: the bytes, the scratch
+    and the samples on the device are those of one such group and of the songs in flight, not of the collection."""
+    if a.decode == 'device':
+        from . import audio
+        step = max(1, a.slots)
+        for k in range(0, len(a.songs), step):
+            for wf, sr, _ in audio.load_flac(list(a.songs[k:k + step])):
+                yield wf, sr
+    else:
+        for f in a.songs:
+            yield flac.load_float(f)
+
+
 def _same_rate_queue(a, flac, residual=False, stems=False):
     """--songs without --sr: the model at the first file's rate, every other file refused unless it has that rate.
     Returns (the queue, that rate)."""
+    if a.decode == 'device':
+        with open(a.songs[0], 'rb') as f0:
+            sr0 = flac.read_streaminfo(f0.read())[0]                # the first file's header, on the host
+
+        def load():
+            for f, (wf, sr) in zip(a.songs, _load_songs(a, flac)):
+                if sr != sr0:
+                    raise SystemExit('%s: sample rate %d differs from the first file\'s %d; one queue runs at one rate'
+                                     % (f, sr, sr0))
+                yield wf, sr                        # a pair: audio.resample at equal rates, the downmix alone
+        return iter_transcribe_songs(load(), Hyperparams(N=2048, sr=sr0), iters=a.iters, weights_dir=a.weights,
+                                     guess=a.guess, slots=a.slots, residual=residual, stems=stems, groups=CLI_GROUPS), sr0
     first = flac.load_float(a.songs[0])
     sr0 = first[1]
 
@@ -291,14 +329,21 @@ def main(argv=None):
                     help='with --traversal song: write <input stem>.group<g>.flac per instrument group, what the '
                          'subtractions took out of the song, 24-bit FLAC at the rate the model runs at')
     ap.add_argument('--flac', default='host', choices=FLAC_WRITERS, help=_FLAC_HELP)
+    ap.add_argument('--decode', default='host', choices=DECODERS, help=_DECODE_HELP)
     a = ap.parse_args(argv)
     if a.residual is not None and a.traversal != 'song':
         raise SystemExit('--residual needs --traversal song (independent windows have no song-level residual)')
     if a.stems_dir is not None and a.traversal != 'song':
         raise SystemExit('--stems-dir needs --traversal song (independent windows have no song-level stems)')
-    wf, sr = flac.load_float(a.infile)
+    if a.decode == 'device':
+        from . import audio
+        wf, sr, _ = audio.load_flac(a.infile)
+    else:
+        wf, sr = flac.load_float(a.infile)
     if a.sr is None:                             # the model at the file's rate
-        if wf.ndim > 1:
+        if a.decode == 'device':
+            wf = audio.resample(wf, sr, sr)      # [n, channels] -> mono on the device; mono passes through
+        elif wf.ndim > 1:
             wf = wf.mean(axis=1)                 # [n, channels] -> mono
         model_sr, file_sr = sr, None
     elif a.sr <= 0:

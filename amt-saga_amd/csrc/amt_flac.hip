@@ -37,6 +37,7 @@
 #include <math.h>
 
 #include "amt_common.h"
+#include "amt_flac_common.h"
 
 #define AMT_FL_THREADS 256
 #define AMT_FL_MAXBS 4096
@@ -91,22 +92,6 @@ __device__ __forceinline__ void fl_put(unsigned *buf, unsigned pos, int n, unsig
 
 __device__ __forceinline__ unsigned fl_byte(const unsigned *buf, int i) { return (buf[i >> 2] >> (24 - 8 * (i & 3))) & 0xffu; }
 
-__device__ __forceinline__ unsigned fl_crc8_step(unsigned crc, unsigned byte) {
-    crc ^= byte;
-    for (int i = 0; i < 8; ++i) crc = (crc & 0x80u) ? ((crc << 1) ^ 0x07u) & 0xffu : (crc << 1) & 0xffu;
-    return crc;
-}
-
-// a(x) b(x) modulo x^16 + x^15 + x^2 + 1
-__device__ __forceinline__ unsigned fl_mulmod16(unsigned a, unsigned b) {
-    unsigned r = 0;
-    for (int i = 15; i >= 0; --i) {
-        r = (r & 0x8000u) ? ((r << 1) ^ 0x8005u) & 0xffffu : (r << 1);
-        if ((b >> i) & 1u) r ^= a;
-    }
-    return r;
-}
-
 // exclusive prefix sum over the 256 threads; lds: 4 words.  Every thread gets the block total as well.
 __device__ __forceinline__ fl_u64 fl_block_scan(fl_u64 v, fl_u64 *lds, fl_u64 *total) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -160,11 +145,7 @@ __global__ __launch_bounds__(AMT_FL_THREADS) void flac_frame_kernel(
 
     for (int i = tid; i < bs; i += AMT_FL_THREADS) q[i] = fl_quant(x[i], bps);
     for (int i = tid; i < AMT_FL_WORDS; i += AMT_FL_THREADS) bits[i] = 0u;
-    {
-        unsigned c = (unsigned)tid << 8;
-        for (int i = 0; i < 8; ++i) c = (c & 0x8000u) ? ((c << 1) ^ 0x8005u) & 0xffffu : (c << 1);
-        crctab[tid] = (unsigned short)c;
-    }
+    crctab[tid] = fl_crc16_entry((unsigned)tid);
     __syncthreads();
 
     int same = 1;
@@ -408,38 +389,7 @@ __global__ __launch_bounds__(AMT_FL_THREADS) void flac_compact_kernel(
     for (int i = threadIdx.x; i < (int)size; i += AMT_FL_THREADS) dst[i] = src[i];
 }
 
-struct fl_md5_consts { unsigned k[64]; };
-
 #define AMT_FL_MD5_LANES 64
-
-__device__ __forceinline__ unsigned fl_rotl(unsigned v, int s) { return (v << s) | (v >> (32 - s)); }
-
-// one MD5 block of 16 words at m (LDS; every lane reads the same address)
-__device__ __forceinline__ void fl_md5_block(unsigned *st, const unsigned *m, const fl_md5_consts &kc) {
-    unsigned a = st[0], b = st[1], c = st[2], d = st[3];
-#pragma unroll
-    for (int i = 0; i < 64; ++i) {
-        unsigned fv;
-        int g, s;
-        if (i < 16) {
-            fv = (b & c) | (~b & d); g = i;
-            s = (i & 3) == 0 ? 7 : (i & 3) == 1 ? 12 : (i & 3) == 2 ? 17 : 22;
-        } else if (i < 32) {
-            fv = (d & b) | (~d & c); g = (5 * i + 1) & 15;
-            s = (i & 3) == 0 ? 5 : (i & 3) == 1 ? 9 : (i & 3) == 2 ? 14 : 20;
-        } else if (i < 48) {
-            fv = b ^ c ^ d; g = (3 * i + 5) & 15;
-            s = (i & 3) == 0 ? 4 : (i & 3) == 1 ? 11 : (i & 3) == 2 ? 16 : 23;
-        } else {
-            fv = c ^ (b | ~d); g = (7 * i) & 15;
-            s = (i & 3) == 0 ? 6 : (i & 3) == 1 ? 10 : (i & 3) == 2 ? 15 : 21;
-        }
-        fv = fv + a + kc.k[i] + m[g];
-        a = d; d = c; c = b;
-        b = b + fl_rotl(fv, s);
-    }
-    st[0] += a; st[1] += b; st[2] += c; st[3] += d;
-}
 
 // MD5 of the little-endian PCM of every signal: one wave per signal.  The chain of rounds is sequential, everything
 // around it is not: per 64 samples (2 or 3 blocks) lane w < 16 bps / 8 builds message word w -- its four bytes lie in two
@@ -550,7 +500,7 @@ int amt_flac_encode_ragged(const float *wave, const long long *base, const long 
         AMT_LAUNCH_CHECK();
     }
     fl_md5_consts kc;
-    for (int i = 0; i < 64; ++i) kc.k[i] = (unsigned)(long long)floor(fabs(sin((double)(i + 1))) * 4294967296.0);
+    fl_md5_fill(kc);
     flac_md5_kernel<<<n, AMT_FL_MD5_LANES, 0, stream>>>(wave, base, len, max_len, bps, md5, kc);
     AMT_LAUNCH_CHECK();
     return AMT_OK;

@@ -182,6 +182,42 @@ int amt_flac_encode_ragged(const float *wave, const long long *base, const long 
                            long long *stream_off, int *frame_minmax, unsigned char *md5, void *stream);
 
 /* ------------------------------------------------------------------------ *
+ * FLAC decoder  (replaces the librosa.load of audio_from_file, util_audio.py:962-964, for files whose bytes are put
+ * on the device: the front of the song queue)
+ *
+ * The host parses STREAMINFO and lists the plausible frame headers (amt_saga/flac.py: read_streaminfo,
+ * frame_candidates); the device decodes every candidate speculatively, follows the chain of frames that the
+ * sequential reader would visit, checks CRC-16 and MD5, and writes interleaved samples.  Subset: 1 .. 8 channels,
+ * all four channel assignments, CONSTANT / VERBATIM / FIXED 0..4 / LPC 1..32 subframes, Rice and Rice2 with escapes,
+ * wasted bits, block sizes 1 .. 65536, bps 4 .. 24 (above 24 is refused: float32 is exact to 24 bits).  DESIGN.md 16.
+ * ------------------------------------------------------------------------ */
+/* audio_from_file (util_audio.py:962-964): bytes of `scratch` amt_flac_decode_ragged needs for n_cand candidates whose
+ * slots (channels * block size int32 each) sum to slot_ints: the slots rounded up to 8, then two int64 per candidate.
+ * Negative for invalid arguments.  Host only. */
+long long amt_flac_decode_scratch_bytes(long long n_cand, long long slot_ints);
+/* audio_from_file (util_audio.py:962-964) for n streams in ONE call.  data [data_bytes]: the files' bytes.
+ * stream_meta int64 [n][9]: byte offset in data, size, first frame byte (relative to the offset), channels, bps, total
+ * samples per channel, first output value, first and one-past-last candidate.  cand_meta int64 [n_cand][7], sorted by
+ * position inside a stream: stream, position (relative), header bytes (CRC-8 included), block size, channel
+ * assignment, frame bps, slot offset in int32.  expect_md5 [n][16]: STREAMINFO's digests (all zero: none).
+ * verify: 0 nothing, 1 CRC-16 of every on-chain frame, 2 CRC-16 and MD5.
+ * out [out_values] float32 pcm 2^-(bps-1), stream i at its first output value, interleaved [samples][channels];
+ * out_pcm: the int32 PCM in the same layout, or NULL.  status int64 [n][4]: code (0 ok, 1 no candidate where the chain
+ * arrived, 2 the frame there does not decode, 5 a table entry out of range), the byte it speaks of, the first byte of
+ * the lowest frame whose CRC-16 fails (INT64_MAX: none), 1 if the MD5 differs.  cand_out int64 [n_cand][3]: end byte,
+ * frame error (0 ok, 1 stream ends inside, 2 format, 3 sample out of range, 4 bps above 24, 5 table), on-chain flag.
+ * md5 [n][16]: written with verify 2.  All tables and outputs: device.  Every stream-derived index is checked on the
+ * device; nothing outside the outputs and the scratch is written, whatever the bytes or the tables hold.
+ * AMT_E_INVALID: a NULL pointer (out_pcm excepted), n < 1, a negative size, verify outside 0 .. 2.  AMT_E_SHAPE:
+ * scratch_bytes < amt_flac_decode_scratch_bytes(n_cand, slot_ints).  All checks return before any HIP call.  Integer
+ * code without packed-FP32 instructions: any stream. */
+int amt_flac_decode_ragged(const unsigned char *data, long long data_bytes, const long long *stream_meta, int n,
+                           const long long *cand_meta, long long n_cand, const unsigned char *expect_md5, int verify,
+                           unsigned char *scratch, long long scratch_bytes, long long slot_ints, float *out,
+                           int *out_pcm, long long out_values, long long *status, long long *cand_out,
+                           unsigned char *md5, void *stream);
+
+/* ------------------------------------------------------------------------ *
  * Spectral subtraction  (replaces audio_complete.subtract, util_audio.py:221-259)
  * ------------------------------------------------------------------------ */
 typedef struct amt_subtract_args {
