@@ -9,6 +9,7 @@
 //   song_pack     the step's event records
 //   song_slide    slice(half, 2 half) + section(offset + half, None, half) + concat (training.py:318-323)
 // Decisions live in int32 masks; a song that neither slides nor detects is carried along untouched.
+#include <type_traits>
 #include "amt_common.h"
 
 // ---- decision ----------------------------------------------------------------------------------------------------------
@@ -97,62 +98,29 @@ __global__ void song_pack_kernel(int n, const int32_t *__restrict__ slot_song, i
 // For every song with slide[b] != 0: rows half .. 2 half of the window move to 0 .. half (residual kept) and rows
 // half .. 2 half are refilled with song frames [offset + 2 half, offset + 3 half) -- the second half of the window at
 // the new offset -- zero past the song's last frame.  T = 2 half: source and destination rows of the move are
-// disjoint, and one thread carries an element through both halves (read W, write W, read S, write W), so each byte
+// disjoint, and one thread carries an element through both halves (read S, read W, write W, write W), so each byte
 // moves once.  A row is ldf magnitudes + 2 ldf phase floats = 3 ldf / 4 float4.  State (offset, count, finished)
 // advances in a second launch, after every workgroup has read the old offset.
+//
+// KEEP: in addition window rows r = 0 .. half - 1 (the residual that leaves the window, as it is before the move) are
+// stored into pool frames frame_base[b] + offset[b] + r, for rows with offset[b] + r < t_song[b]: rows at or past the
+// song's last frame are zero padding in the window and ANOTHER song's region in the pool.  Magnitudes only: the
+// subtraction never touches a phase (util_audio.py:253-259), s_ph already is the residual's phase.
+// Aliasing: `s_mag` is then read and written through the same pointer, which is therefore not __restrict__ (the plain
+// slide's is, and the phases, only read, keep theirs).  Per song the kernel writes pool frames [offset, offset + half)
+// and reads pool frames [offset + 2 half, offset + 3 half) of the same region: disjoint, and a region belongs to one
+// song, so no thread reads a float another thread (of this or any workgroup) writes and no ordering between them is
+// needed (the source order -- every load of an element before its stores -- would be right even if they did overlap;
+// measured: the same time as with the store first).  The written frames have been consumed for good: the walk only
+// reads forward (the next slides fetch later frames, an admission reads frames [0, T) of NEW regions).  Per row ldf
+// floats more read and ldf more written than the plain slide's 12 ldf: 14 / 12 of its bytes.
+template <bool KEEP> using pool_mag_t = std::conditional_t<KEEP, float *, const float *__restrict__>;
+template <bool KEEP>
 __global__ __launch_bounds__(256) void song_slide_kernel(
         float *__restrict__ w_mag, float *__restrict__ w_ph, size_t w_stride /* floats of one window's mag */,
-        const float *__restrict__ s_mag, const float *__restrict__ s_ph, const int64_t *__restrict__ frame_base,
-        const int32_t *__restrict__ t_song, const int32_t *__restrict__ slide, const int32_t *__restrict__ offset,
-        int half, int ld4) {
-    const int b = blockIdx.y;
-    if (!slide[b]) return;                                        // whole workgroup: the window stays as it is
-    const int row4 = 3 * ld4;
-    const int n4 = half * row4;
-    const int first = offset[b] + 2 * half;                       // song frame that lands in window row `half`
-    const int ts = t_song[b];
-    const int64_t fb = frame_base[b];
-    float4 *wm = reinterpret_cast<float4 *>(w_mag + (size_t)b * w_stride);
-    float4 *wp = reinterpret_cast<float4 *>(w_ph + (size_t)b * w_stride * 2);
-    const float4 *sm = reinterpret_cast<const float4 *>(s_mag);
-    const float4 *sp = reinterpret_cast<const float4 *>(s_ph);
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
-        const int r = i / row4, c = i - r * row4;
-        const int f = first + r;
-        const bool have = f < ts;
-        float4 fresh = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (c < ld4) {
-            if (have) fresh = sm[(size_t)(fb + f) * ld4 + c];
-            wm[(size_t)r * ld4 + c] = wm[(size_t)(half + r) * ld4 + c];
-            wm[(size_t)(half + r) * ld4 + c] = fresh;
-        } else {
-            const int c2 = c - ld4;
-            if (have) fresh = sp[(size_t)(fb + f) * 2 * ld4 + c2];
-            wp[(size_t)r * 2 * ld4 + c2] = wp[(size_t)(half + r) * 2 * ld4 + c2];
-            wp[(size_t)(half + r) * 2 * ld4 + c2] = fresh;
-        }
-    }
-}
-
-// ---- slide that keeps the outgoing half ---------------------------------------------------------------------------
-// song_slide_kernel, and in addition window rows r = 0 .. half - 1 (the residual that leaves the window, as it is before
-// the move) are stored into pool frames frame_base[b] + offset[b] + r, for rows with offset[b] + r < t_song[b]: rows at or
-// past the song's last frame are zero padding in the window and ANOTHER song's region in the pool.  Magnitudes only:
-// the subtraction never touches a phase (util_audio.py:253-259), s_ph already is the residual's phase.
-// Aliasing: `s_mag` is read and written through the same pointer, which is therefore not __restrict__ (and the phases,
-// only read, keep theirs).  Per song the kernel writes pool frames [offset, offset + half) and reads pool frames
-// [offset + 2 half, offset + 3 half) of the same region: disjoint, and a region belongs to one song, so no thread
-// reads a float another thread (of this or any workgroup) writes and no ordering between them is needed (the source
-// order -- every load of an element before its stores -- would be right even if they did overlap).  The written
-// frames have been consumed for good: the walk only reads forward (the next slides fetch later frames, an admission
-// reads frames [0, T) of NEW regions).  One thread still carries an element through every place it goes (read W row r,
-// read S, read W row half + r, write S, write W, write W); per row ldf floats more read and ldf more written than the
-// slide's 12 ldf: 14 / 12 of its bytes.
-__global__ __launch_bounds__(256) void song_slide_keep_kernel(
-        float *__restrict__ w_mag, float *__restrict__ w_ph, size_t w_stride /* floats of one window's mag */,
-        float *s_mag, const float *__restrict__ s_ph, const int64_t *__restrict__ frame_base,
-        const int32_t *__restrict__ t_song, const int32_t *__restrict__ slide, const int32_t *__restrict__ offset,
-        int half, int ld4) {
+        pool_mag_t<KEEP> s_mag, const float *__restrict__ s_ph,
+        const int64_t *__restrict__ frame_base, const int32_t *__restrict__ t_song, const int32_t *__restrict__ slide,
+        const int32_t *__restrict__ offset, int half, int ld4) {
     const int b = blockIdx.y;
     if (!slide[b]) return;                                        // whole workgroup: the window stays as it is
     const int row4 = 3 * ld4;
@@ -163,7 +131,7 @@ __global__ __launch_bounds__(256) void song_slide_keep_kernel(
     const int64_t fb = frame_base[b];
     float4 *wm = reinterpret_cast<float4 *>(w_mag + (size_t)b * w_stride);
     float4 *wp = reinterpret_cast<float4 *>(w_ph + (size_t)b * w_stride * 2);
-    float4 *sm = reinterpret_cast<float4 *>(s_mag);
+    auto *sm = reinterpret_cast<std::conditional_t<KEEP, float4 *, const float4 *>>(s_mag);
     const float4 *sp = reinterpret_cast<const float4 *>(s_ph);
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
         const int r = i / row4, c = i - r * row4;
@@ -171,13 +139,13 @@ __global__ __launch_bounds__(256) void song_slide_keep_kernel(
         const bool have = f < ts;
         float4 fresh = make_float4(0.f, 0.f, 0.f, 0.f);
         if (c < ld4) {
-            // the three loads first, then the three stores: no load of s_mag has to wait behind a store through the
-            // same pointer (measured: the same time as with the store first)
-            const bool keep = off + r < ts;
-            const float4 out = wm[(size_t)r * ld4 + c];
+            // every load first, then the stores: no load of s_mag has to wait behind a store through the same pointer
+            float4 out;
+            if constexpr (KEEP) out = wm[(size_t)r * ld4 + c];
             if (have) fresh = sm[(size_t)(fb + f) * ld4 + c];
             const float4 moved = wm[(size_t)(half + r) * ld4 + c];
-            if (keep) sm[(size_t)(fb + off + r) * ld4 + c] = out;
+            if constexpr (KEEP)
+                if (off + r < ts) sm[(size_t)(fb + off + r) * ld4 + c] = out;
             wm[(size_t)r * ld4 + c] = moved;
             wm[(size_t)(half + r) * ld4 + c] = fresh;
         } else {
@@ -259,6 +227,37 @@ __global__ __launch_bounds__(256) void song_admit_state_kernel(amt_song_admit_ar
     a.clean[b] = 1;
 }
 
+// the two event entries: slot_song NULL = records numbered song0 + slot
+static int pack_events(int n, const int32_t *slot_song, int song0, int step, const int32_t *kind, const int32_t *pitch,
+                       const int32_t *program, const int32_t *velocity, const int32_t *onset, const int32_t *end,
+                       const int32_t *offset, int32_t *events, void *stream) {
+    if (!kind || !onset || !end || !offset || !events || n <= 0) return AMT_E_INVALID;
+    song_pack_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(n, slot_song, song0, step, kind, pitch, program,
+                                                                        velocity, onset, end, offset, events);
+    AMT_LAUNCH_CHECK();
+    return AMT_OK;
+}
+
+// the two slide entries: checks, the slide's grid, then the state
+template <bool KEEP>
+static int slide_launch(float *w_mag, float *w_ph, int B, int T, int ldf, size_t w_stride, pool_mag_t<KEEP> s_mag,
+                        const float *s_ph, const int64_t *frame_base, const int32_t *t_song, const int32_t *slide,
+                        int32_t *offset, int32_t *count, int32_t *finished, void *stream) {
+    if (!w_mag || !w_ph || !s_mag || !s_ph || !frame_base || !t_song || !slide || !offset || !count || !finished)
+        return AMT_E_INVALID;
+    if (B <= 0 || T < 2 || (T & 1)) return AMT_E_INVALID;         // odd T: the two halves of the move would overlap
+    if (ldf <= 0 || (ldf & 3) || (w_stride & 3) || w_stride < (size_t)T * ldf) return AMT_E_SHAPE;
+    const int half = T / 2, ld4 = ldf >> 2;
+    hipStream_t st = (hipStream_t)stream;
+    int gx = (half * 3 * ld4 + 256 * 4 - 1) / (256 * 4);          // ~4 float4 (two reads, two writes each) per thread
+    if (gx < 1) gx = 1;
+    song_slide_kernel<KEEP><<<dim3(gx, B), 256, 0, st>>>(w_mag, w_ph, w_stride, s_mag, s_ph, frame_base, t_song, slide,
+                                                         offset, half, ld4);
+    song_advance_kernel<<<(B + 255) / 256, 256, 0, st>>>(B, half, slide, t_song, offset, count, finished);
+    AMT_LAUNCH_CHECK();
+    return AMT_OK;
+}
+
 extern "C" {
 
 int amt_song_admit(const amt_song_admit_args *args, void *stream) {
@@ -279,16 +278,6 @@ int amt_song_admit(const amt_song_admit_args *args, void *stream) {
     song_admit_kernel<<<dim3(gx, a.B), 256, 0, st>>>(a.w_mag, a.w_ph, a.w_stride, a.s_mag, a.s_ph, a.admit, a.n_new,
                                                      a.new_frame_base, a.new_t_song, a.T, ld4);
     song_admit_state_kernel<<<a.B, 256, 0, st>>>(a);
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
-}
-
-int amt_song_pack_events_slots(int n, const int32_t *slot_song, int step, const int32_t *kind, const int32_t *pitch,
-                               const int32_t *program, const int32_t *velocity, const int32_t *onset, const int32_t *end,
-                               const int32_t *offset, int32_t *events, void *stream) {
-    if (!slot_song || !kind || !onset || !end || !offset || !events || n <= 0) return AMT_E_INVALID;
-    song_pack_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(n, slot_song, 0, step, kind, pitch, program, velocity,
-                                                                        onset, end, offset, events);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }
@@ -321,47 +310,28 @@ int amt_song_wave(const float *samples, const int64_t *sample_base, const int32_
 int amt_song_pack_events(int n, int song0, int step, const int32_t *kind, const int32_t *pitch, const int32_t *program,
                          const int32_t *velocity, const int32_t *onset, const int32_t *end, const int32_t *offset,
                          int32_t *events, void *stream) {
-    if (!kind || !onset || !end || !offset || !events || n <= 0) return AMT_E_INVALID;
-    song_pack_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(n, nullptr, song0, step, kind, pitch, program,
-                                                                        velocity, onset, end, offset, events);
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
+    return pack_events(n, nullptr, song0, step, kind, pitch, program, velocity, onset, end, offset, events, stream);
+}
+
+int amt_song_pack_events_slots(int n, const int32_t *slot_song, int step, const int32_t *kind, const int32_t *pitch,
+                               const int32_t *program, const int32_t *velocity, const int32_t *onset, const int32_t *end,
+                               const int32_t *offset, int32_t *events, void *stream) {
+    if (!slot_song) return AMT_E_INVALID;
+    return pack_events(n, slot_song, 0, step, kind, pitch, program, velocity, onset, end, offset, events, stream);
 }
 
 int amt_song_slide(float *w_mag, float *w_ph, int B, int T, int ldf, size_t w_stride, const float *s_mag,
                    const float *s_ph, const int64_t *frame_base, const int32_t *t_song, const int32_t *slide,
                    int32_t *offset, int32_t *count, int32_t *finished, void *stream) {
-    if (!w_mag || !w_ph || !s_mag || !s_ph || !frame_base || !t_song || !slide || !offset || !count || !finished)
-        return AMT_E_INVALID;
-    if (B <= 0 || T < 2 || (T & 1)) return AMT_E_INVALID;         // odd T: the two halves of the move would overlap
-    if (ldf <= 0 || (ldf & 3) || (w_stride & 3) || w_stride < (size_t)T * ldf) return AMT_E_SHAPE;
-    const int half = T / 2, ld4 = ldf >> 2;
-    hipStream_t st = (hipStream_t)stream;
-    int gx = (half * 3 * ld4 + 256 * 4 - 1) / (256 * 4);          // ~4 float4 (two reads, two writes each) per thread
-    if (gx < 1) gx = 1;
-    song_slide_kernel<<<dim3(gx, B), 256, 0, st>>>(w_mag, w_ph, w_stride, s_mag, s_ph, frame_base, t_song, slide, offset,
-                                                   half, ld4);
-    song_advance_kernel<<<(B + 255) / 256, 256, 0, st>>>(B, half, slide, t_song, offset, count, finished);
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
+    return slide_launch<false>(w_mag, w_ph, B, T, ldf, w_stride, s_mag, s_ph, frame_base, t_song, slide, offset, count,
+                               finished, stream);
 }
 
 int amt_song_slide_keep(float *w_mag, float *w_ph, int B, int T, int ldf, size_t w_stride, float *s_mag,
                         const float *s_ph, const int64_t *frame_base, const int32_t *t_song, const int32_t *slide,
                         int32_t *offset, int32_t *count, int32_t *finished, void *stream) {
-    if (!w_mag || !w_ph || !s_mag || !s_ph || !frame_base || !t_song || !slide || !offset || !count || !finished)
-        return AMT_E_INVALID;
-    if (B <= 0 || T < 2 || (T & 1)) return AMT_E_INVALID;
-    if (ldf <= 0 || (ldf & 3) || (w_stride & 3) || w_stride < (size_t)T * ldf) return AMT_E_SHAPE;
-    const int half = T / 2, ld4 = ldf >> 2;
-    hipStream_t st = (hipStream_t)stream;
-    int gx = (half * 3 * ld4 + 256 * 4 - 1) / (256 * 4);          // the slide's grid
-    if (gx < 1) gx = 1;
-    song_slide_keep_kernel<<<dim3(gx, B), 256, 0, st>>>(w_mag, w_ph, w_stride, s_mag, s_ph, frame_base, t_song, slide,
-                                                        offset, half, ld4);
-    song_advance_kernel<<<(B + 255) / 256, 256, 0, st>>>(B, half, slide, t_song, offset, count, finished);
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
+    return slide_launch<true>(w_mag, w_ph, B, T, ldf, w_stride, s_mag, s_ph, frame_base, t_song, slide, offset, count,
+                              finished, stream);
 }
 
 }  // extern "C"

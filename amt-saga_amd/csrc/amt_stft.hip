@@ -24,7 +24,9 @@
 //  * this file is built with packed-FP32 instructions (-ffp-contract=fast, no NO_PK): every launch from it, the
 //    song-length amt_istft_ragged included, belongs on the ONE compute stream the walk uses and must not overlap the
 //    networks' MFMA kernels on a side stream.
+#include <type_traits>
 #include "amt_fft.h"
+#include "amt_ordered.h"
 
 struct amt_stft_plan {
     int n_fft, hop, center;
@@ -494,14 +496,6 @@ __global__ __launch_bounds__(256) void window_max_kernel(const float *__restrict
     m = block_max(m, red);
     if (threadIdx.x == 0) atomicMax(out + blockIdx.y, float_to_ordered(m));
 }
-__global__ void ordered_init_kernel(unsigned int *p, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = AMT_ORDERED_NEG_INF;
-}
-__global__ void ordered_decode_kernel(unsigned int *p, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = __float_as_uint(ordered_to_float(p[i]));
-}
 
 // host launchers
 // diagnostics both STFT launchers read: AMT_STFT_PPB = most frame pairs per workgroup (default 16), AMT_STFT_REUSE=0 =
@@ -614,6 +608,15 @@ static int launch_istft_ragged(const amt_stft_plan *plan, const float *mag, cons
     return AMT_E_UNSUPPORTED;
 }
 
+// the transform size of a plan as a compile-time constant: f(std::integral_constant<int, N>) for the first N of the list
+// that equals n_fft, AMT_E_UNSUPPORTED if none does
+template <int N0, int... Ns, class F>
+static int with_n_fft(int n_fft, F f) {
+    if (n_fft == N0) return f(std::integral_constant<int, N0>{});
+    if constexpr (sizeof...(Ns) > 0) return with_n_fft<Ns...>(n_fft, f);
+    else return AMT_E_UNSUPPORTED;
+}
+
 // ---------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------
@@ -697,14 +700,9 @@ int amt_stft_mag(const amt_stft_plan *plan, const float *wave, int B, int L, siz
     if (plan->center && L <= plan->n_fft / 2) return AMT_E_SHAPE;   // reflect pad needs L > n_fft/2
     hipStream_t st = (hipStream_t)stream;
     if (ref_max) AMT_HIP_CHECK(hipMemsetAsync(ref_max, 0, sizeof(float) * B, st));
-    switch (plan->n_fft) {
-        case 256:  return launch_stft<256>(plan, wave, B, L, wave_stride, mag, phase_ri, ref_max, T, ldf, spec_stride, st);
-        case 512:  return launch_stft<512>(plan, wave, B, L, wave_stride, mag, phase_ri, ref_max, T, ldf, spec_stride, st);
-        case 1024: return launch_stft<1024>(plan, wave, B, L, wave_stride, mag, phase_ri, ref_max, T, ldf, spec_stride, st);
-        case 2048: return launch_stft<2048>(plan, wave, B, L, wave_stride, mag, phase_ri, ref_max, T, ldf, spec_stride, st);
-        case 4096: return launch_stft<4096>(plan, wave, B, L, wave_stride, mag, phase_ri, ref_max, T, ldf, spec_stride, st);
-    }
-    return AMT_E_UNSUPPORTED;
+    return with_n_fft<256, 512, 1024, 2048, 4096>(plan->n_fft, [&](auto N) {
+        return launch_stft<N()>(plan, wave, B, L, wave_stride, mag, phase_ri, ref_max, T, ldf, spec_stride, st);
+    });
 }
 
 int amt_stft_mag_ragged(const amt_stft_plan *plan, const float *samples, const int64_t *sample_base,
@@ -719,17 +717,10 @@ int amt_stft_mag_ragged(const amt_stft_plan *plan, const float *samples, const i
     if (plan->center ? max_len <= plan->n_fft / 2 : max_len < plan->n_fft) return AMT_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     if (ref_max) AMT_HIP_CHECK(hipMemsetAsync(ref_max, 0, sizeof(float) * n, st));
-#define AMT_RAGGED(NF) launch_stft_ragged<NF>(plan, samples, sample_base, length, n, max_len, n_samples, total_len, mag, \
-                                              phase_ri, ref_max, frame_base, pool_frames, ldf, st)
-    switch (plan->n_fft) {
-        case 256:  return AMT_RAGGED(256);
-        case 512:  return AMT_RAGGED(512);
-        case 1024: return AMT_RAGGED(1024);
-        case 2048: return AMT_RAGGED(2048);
-        case 4096: return AMT_RAGGED(4096);
-    }
-#undef AMT_RAGGED
-    return AMT_E_UNSUPPORTED;
+    return with_n_fft<256, 512, 1024, 2048, 4096>(plan->n_fft, [&](auto N) {
+        return launch_stft_ragged<N()>(plan, samples, sample_base, length, n, max_len, n_samples, total_len, mag, phase_ri,
+                                       ref_max, frame_base, pool_frames, ldf, st);
+    });
 }
 
 int amt_istft(const amt_stft_plan *plan, const float *mag, const float *phase_ri, int B, int T,
@@ -742,14 +733,9 @@ int amt_istft(const amt_stft_plan *plan, const float *mag, const float *phase_ri
     // spec_stride: bins with a phase array; floats of the interleaved complex array without one (a float2 per bin)
     if (spec_stride < (size_t)T * ldf * (phase_ri ? 1 : 2) || (!phase_ri && (spec_stride & 1))) return AMT_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
-    switch (plan->n_fft) {
-        case 256:  return launch_istft<256>(plan, mag, phase_ri, B, T, ldf, spec_stride, wave_out, wave_stride, Lout, st);
-        case 512:  return launch_istft<512>(plan, mag, phase_ri, B, T, ldf, spec_stride, wave_out, wave_stride, Lout, st);
-        case 1024: return launch_istft<1024>(plan, mag, phase_ri, B, T, ldf, spec_stride, wave_out, wave_stride, Lout, st);
-        case 2048: return launch_istft<2048>(plan, mag, phase_ri, B, T, ldf, spec_stride, wave_out, wave_stride, Lout, st);
-        case 4096: return launch_istft<4096>(plan, mag, phase_ri, B, T, ldf, spec_stride, wave_out, wave_stride, Lout, st);
-    }
-    return AMT_E_UNSUPPORTED;
+    return with_n_fft<256, 512, 1024, 2048, 4096>(plan->n_fft, [&](auto N) {
+        return launch_istft<N()>(plan, mag, phase_ri, B, T, ldf, spec_stride, wave_out, wave_stride, Lout, st);
+    });
 }
 
 int amt_istft_ragged(const amt_stft_plan *plan, const float *mag, const float *phase_ri, const int64_t *frame_base,
@@ -762,15 +748,10 @@ int amt_istft_ragged(const amt_stft_plan *plan, const float *mag, const float *p
     if (ldf < F || max_frames <= 0 || pool_frames <= 0 || n_out < 0) return AMT_E_SHAPE;
     if (max_frames < 2) return AMT_OK;                              // no signal has a sample
     hipStream_t st = (hipStream_t)stream;
-#define AMT_RAGGED(NF) launch_istft_ragged<NF>(plan, mag, phase_ri, frame_base, t_frames, n, max_frames, pool_frames, ldf, \
-                                               out, out_base, n_out, st)
-    switch (plan->n_fft) {
-        case 1024: return AMT_RAGGED(1024);
-        case 2048: return AMT_RAGGED(2048);
-        case 4096: return AMT_RAGGED(4096);
-    }
-#undef AMT_RAGGED
-    return AMT_E_UNSUPPORTED;
+    return with_n_fft<1024, 2048, 4096>(plan->n_fft, [&](auto N) {
+        return launch_istft_ragged<N()>(plan, mag, phase_ri, frame_base, t_frames, n, max_frames, pool_frames, ldf, out,
+                                        out_base, n_out, st);
+    });
 }
 
 int amt_window_max(const float *spec, int B, int T, int ldf, size_t spec_stride, float *out_max,
@@ -778,13 +759,13 @@ int amt_window_max(const float *spec, int B, int T, int ldf, size_t spec_stride,
     if (!spec || !out_max || B <= 0 || T <= 0 || ldf <= 0 || (ldf & 3)) return AMT_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     unsigned int *o = reinterpret_cast<unsigned int *>(out_max);
-    ordered_init_kernel<<<(B + 255) / 256, 256, 0, st>>>(o, B);
+    ordered_init_kernel<><<<(B + 255) / 256, 256, 0, st>>>(o, B);
     const int n = T * ldf;
     int gx = (n / 4 + 255) / 256;
     if (gx > 64) gx = 64;
     if (gx < 1) gx = 1;
     window_max_kernel<<<dim3(gx, B), 256, 0, st>>>(spec, n, spec_stride, o);
-    ordered_decode_kernel<<<(B + 255) / 256, 256, 0, st>>>(o, B);
+    ordered_decode_kernel<><<<(B + 255) / 256, 256, 0, st>>>(o, B);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }
