@@ -23,9 +23,14 @@ CASES = {
     # BASELINE config C3 at the metric size: 516 frames, timing(start, end) + pitch + velocity, one subtraction
     'c3': dict(hp=dict(N=2048), heads=('timing', 'pitch', 'velocity'), iters=1, groups=(0,), seed=303, notes=(3, 3),
                max_onset=0.5, keep=16),
-    # BASELINE config C5 as stated: all heads, five iterations, the three instrument groups, 516 frames
+    # BASELINE config C5 as stated: all heads, five iterations, the three instrument groups, 516 frames.  keep=7 is the
+    # most this seed gives under the generator's rule (at most the spare candidates dropped): of the 12 candidates of
+    # keep=8, five lie within 10 bands of a tie (margins / band 1.14, 9.46, 0.43, 3.97, 3.27) and the generator refuses
     'c5': dict(hp=dict(N=2048), heads=('timing', 'pitch', 'instrument', 'velocity'), iters=5, groups=(0, 1, 2), seed=505,
-               notes=(2, 4), max_onset=0.5, keep=3),
+               notes=(2, 4), max_onset=0.5, keep=7),
+    # BASELINE config C4 as stated: pitch + instrument heads, three iterations, the three instrument groups, 516 frames
+    'c4': dict(hp=dict(N=2048), heads=('pitch', 'instrument'), iters=3, groups=(0, 1, 2), seed=404, notes=(2, 4),
+               max_onset=0.5, keep=8),
     # the main small case of tests/test_gpu_loop.py (86 frames, 32 windows): only the oracle's OWN song-level
     # normalisers are stored; the oracle loop itself runs live in that test
     'main32': dict(hp=dict(N=2048, window_size_note_time=1), heads=('timing', 'pitch', 'velocity'), iters=2, groups=(0,),

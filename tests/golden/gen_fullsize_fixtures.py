@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Test infrastructure: full-size parity fixtures, computed by oracle/ in the BUILD CONTAINER (no GPU) and committed.
 
-    python tests/golden/gen_fullsize_fixtures.py [case ...]        (default: every case; ~10 minutes on 8 cores)
+    python tests/golden/gen_fullsize_fixtures.py [case ...]        (default: every case; ~30 minutes on 8 cores: c4 7, c5 14)
 
 The oracle loop needs seconds per BASELINE-sized window and its song-level normalisers (`LoopOracle.ref_levels`: every
 bin of the 87- / 348- / 1392-bin grids over all 516 frames, training.py:271-282) half a minute, so the GPU tests cannot
@@ -10,7 +10,8 @@ run them live at the metric size.  This script runs them here, once, and stores 
 
   * c3     config C3 at 516 frames, 16 windows: timing(start, end) + pitch + velocity, one subtraction
            (training.py:296-449 with the predicted note);
-  * c5     config C5 as stated: all heads, five iterations, instrument groups 0-2, 516 frames, 3 windows;
+  * c5     config C5 as stated: all heads, five iterations, instrument groups 0-2, 516 frames, 7 windows;
+  * c4     config C4 as stated: pitch + instrument heads, three iterations, instrument groups 0-2, 516 frames, 8 windows;
   * main32 the oracle's own normalisers for the 32 small windows of tests/test_gpu_loop.py's main case.
 
 Per kept window: the oracle's OWN normalisers (ref_mag, ref_C_1, ref_C_inst, ref_C_foc -- the product's prepare() is
@@ -39,7 +40,7 @@ from oracle.loop import LoopOracle                           # noqa: E402
 REF_KEYS = ('ref_mag', 'ref_C_1', 'ref_C_inst', 'ref_C_foc')
 HEAD_KEYS = ('timing_start', 'timing_end', 'pitch', 'instrument', 'velocity')
 MARGIN = 10.0                                                # x band
-FULL_RESID = {'c3': 2, 'c5': 3}
+FULL_RESID = {'c3': 2, 'c4': 1, 'c5': 3}
 _ORC = None
 
 

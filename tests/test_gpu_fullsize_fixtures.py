@@ -1,6 +1,7 @@
 """GPU parity at the metric size against fixtures oracle/ computed in the build container
 (tests/golden/gen_fullsize_fixtures.py -> tests/golden/fullsize_fixtures.npz): config C3 on 16 windows of 516 frames,
-config C5 as stated (all heads, five iterations, instrument groups 0-2) on 3, and the song-level normalisers of every
+config C5 as stated (all heads, five iterations, instrument groups 0-2) on 7, config C4 as stated (pitch + instrument
+heads, three iterations, instrument groups 0-2) on 8, and the song-level normalisers of every
 one of those windows on all three CQT grids (87 / 348 / 1392 bins, training.py:271-282).
 
 The oracle ran on its OWN normalisers (LoopOracle.ref_levels), not on the product's; the product runs on its own
@@ -35,12 +36,58 @@ def _waves(case, fx):
     return fw.pcm_to_wave(pcm)
 
 
-@pytest.mark.parametrize('case,streams', [('c3', 1), ('c5', 1), ('c3', 2), ('c5', 2)])
+def compare_with_fixture(case, fx, p, iters, rows, refs, ev, trace, mag, rmax):
+    """The K fixture windows of `case` against what the product returned for them, wherever they sat in its batch
+    (rows[k] = the batch row of fixture window k; every array below holds those K rows, in fixture order): its own
+    normalisers to 1e-4 (refs: name -> [K]), events bit for bit with column 0 = the row (ev [iters, K, 7]), the heads'
+    pre-rounding floats within the bands of oracle/compare.py (trace: per iteration name -> [K, ...]), and the residual
+    mag [K, T, ldf] / rmax [K] to the fixture's bars: frame maxima, ref_max and the 20-band compression to 1e-4 of the
+    maximum, the 16-bit quantised residual of the first windows to 1e-4 + one step.  Returns the worst float distance
+    per head."""
+    from oracle import audio as oa
+    from oracle.compare import bands_for
+    rows = np.asarray(rows)
+    K = len(rows)
+    assert K == fx[case + '_events'].shape[1] == ev.shape[1] == mag.shape[0]
+    # the product's own song-level normalisers against the oracle's own, every window, every grid the case uses
+    want_refs = fx[case + '_refs']
+    for j, k in enumerate(REF_KEYS):
+        if k in refs:
+            got = refs[k]
+            rel = np.abs(got - want_refs[:, j]) / want_refs[:, j]
+            assert rel.max() < 1e-4, (case, k, rel)
+        else:
+            assert np.all(np.isnan(want_refs[:, j])), k
+    want_ev = fx[case + '_events'].copy()
+    want_ev[:, :, 0] = rows[None, :]
+    assert np.array_equal(ev, want_ev), (case, np.argwhere(ev != want_ev))
+    bands = bands_for(p)
+    worst = {}
+    for it in range(iters):
+        for name, g in trace[it].items():
+            want = fx[case + '_float_' + name][it]
+            d = np.abs(g.reshape(K, -1).astype(np.float64) - want.reshape(K, -1)).max()
+            worst[name] = max(worst.get(name, 0.0), float(d))
+            assert d <= bands[name], (case, name, it, d, bands[name])
+    F = p.N // 2 + 1
+    for i in range(K):
+        m = mag[i][:, :F].T                                   # [T, ldf] frame-major -> [F, T]
+        scale = float(fx[case + '_fmax'][i].max())
+        assert np.abs(m.max(axis=0) - fx[case + '_fmax'][i]).max() <= 1e-4 * scale, ('frame maxima', case, i)
+        assert abs(float(rmax[i]) - scale) <= 1e-4 * scale, ('ref_max', case, i)
+        band = oa.AudioCompleteOracle.compress_bands(m, bands=p.timing_bands)
+        assert np.abs(band - fx[case + '_band'][i]).max() <= 1e-4 * float(fx[case + '_band'][i].max()), ('bands', case, i)
+    for i, s in enumerate(fx[case + '_resid_scale']):
+        want = fx[case + '_resid_q'][i].astype(np.float64) * s
+        m = mag[i][:, :F].T
+        assert np.abs(m - want).max() <= (1e-4 + 1.0 / 65535) * want.max(), ('residual', case, i)
+    return worst
+
+
+@pytest.mark.parametrize('case,streams', [('c3', 1), ('c5', 1), ('c3', 2), ('c5', 2), ('c4', 1)])
 def test_fullsize_loop_vs_oracle_fixture(case, streams, fx):
     import torch
     from amt_saga.loop import TranscriptionLoop
-    from oracle import audio as oa
-    from oracle.compare import bands_for
     c = fw.CASES[case]
     p = fw.params_for(case)
     wave_h = _waves(case, fx)
@@ -51,39 +98,8 @@ def test_fullsize_loop_vs_oracle_fixture(case, streams, fx):
     events, b = lp.run(torch.from_numpy(wave_h).cuda())
     torch.cuda.synchronize()
     trace, lp.trace = [{k: v.cpu().numpy() for k, v in t.items()} for t in lp.trace], None
-    # the product's own song-level normalisers against the oracle's own, every window, every grid the case uses
-    want_refs = fx[case + '_refs']
-    for j, k in enumerate(REF_KEYS):
-        if k in lp.refs:
-            got = lp.refs[k].cpu().numpy()
-            rel = np.abs(got - want_refs[:, j]) / want_refs[:, j]
-            assert rel.max() < 1e-4, (case, k, rel)
-        else:
-            assert np.all(np.isnan(want_refs[:, j])), k
-    ev = events.cpu().numpy()
-    assert np.array_equal(ev, fx[case + '_events']), (case, np.argwhere(ev != fx[case + '_events']))
-    bands = bands_for(p)
-    worst = {}
-    for it in range(c['iters']):
-        for name, g in trace[it].items():
-            want = fx[case + '_float_' + name][it]
-            d = np.abs(g.reshape(B, -1).astype(np.float64) - want.reshape(B, -1)).max()
-            worst[name] = max(worst.get(name, 0.0), float(d))
-            assert d <= bands[name], (case, name, it, d, bands[name])
-    mag = b.mag.cpu().numpy()                                 # [B, T, ldf] frame-major
-    F = p.N // 2 + 1
-    rmax = b.ref_max.cpu().numpy()
-    for i in range(B):
-        m = mag[i][:, :F].T
-        scale = float(fx[case + '_fmax'][i].max())
-        assert np.abs(m.max(axis=0) - fx[case + '_fmax'][i]).max() <= 1e-4 * scale, ('frame maxima', case, i)
-        assert abs(float(rmax[i]) - scale) <= 1e-4 * scale, ('ref_max', case, i)
-        band = oa.AudioCompleteOracle.compress_bands(m, bands=p.timing_bands)
-        assert np.abs(band - fx[case + '_band'][i]).max() <= 1e-4 * float(fx[case + '_band'][i].max()), ('bands', case, i)
-    for i, s in enumerate(fx[case + '_resid_scale']):
-        want = fx[case + '_resid_q'][i].astype(np.float64) * s
-        m = mag[i][:, :F].T
-        assert np.abs(m - want).max() <= (1e-4 + 1.0 / 65535) * want.max(), ('residual', case, i)
+    worst = compare_with_fixture(case, fx, p, c['iters'], np.arange(B), {k: v.cpu().numpy() for k, v in lp.refs.items()},
+                                 events.cpu().numpy(), trace, b.mag.cpu().numpy(), b.ref_max.cpu().numpy())
     print('%s (%d timing stream%s): %d windows of %d frames x %d iterations against the oracle fixture: events bit-exact, '
           'worst float distances %s' % (case, streams, 's' * (streams > 1), B, p.timing_frames, c['iters'],
                                         {k: '%.2g' % v for k, v in worst.items()}))
