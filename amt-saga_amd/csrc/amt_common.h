@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 #include "amt_saga.h"
 
 #define AMT_WAVE 64
@@ -84,3 +85,23 @@ __device__ __forceinline__ float block_max(float v, float *lds_scratch /* >= 16 
 }
 
 static inline int amt_is_pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
+
+// ---- run-time values as compile-time constants ------------------------------------------------
+// A compile-time list of supported values (amt_values) or of supported PAIRS (amt_cases: the pairs listed, not the
+// product of their members).  amt_dispatch calls f with the first entry that equals the run-time value(s), as
+// std::integral_constant(s), and returns f's status; AMT_E_UNSUPPORTED if no entry does.
+template <int... Vs> struct amt_values {};
+template <int A, int B> struct amt_case {};
+template <class... Cases> struct amt_cases {};
+template <int... Vs, class F>
+static int amt_dispatch(amt_values<Vs...>, int v, F f) {
+    int rc = AMT_E_UNSUPPORTED;
+    (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return rc;
+}
+template <int... As, int... Bs, class F>
+static int amt_dispatch(amt_cases<amt_case<As, Bs>...>, int a, int b, F f) {
+    int rc = AMT_E_UNSUPPORTED;
+    (void)((a == As && b == Bs && ((rc = f(std::integral_constant<int, As>{}, std::integral_constant<int, Bs>{})), true)) || ...);
+    return rc;
+}

@@ -75,6 +75,24 @@ __host__ __device__ __forceinline__ void amt_split_f16(float xs, unsigned short 
     lb = amt_f16_bits(l);
 }
 
+// The packed weights, as the kernels below read them and both packers (pack_f16x3 on the host, convh_pack_kernel on
+// the device: amt_rdcnn.hip) write them: [slice][chunk16][tap pair][plane][N-subtile][lane][8] f16 over 32-wide
+// output slices and 16-channel chunks (nch16 of them; ntp tap pairs).  Lane col + 16 g of N-subtile ns holds output
+// column 16 ns + col of its slice and k-group g = (tap 2 tp + g % 2, channels 8 (g / 2) .. + 7 of the chunk).
+struct HxWeightAt { size_t idx; int tap, cin, cout; };      // f16 index in the packed array <- element of the kernel
+__host__ __device__ __forceinline__ HxWeightAt hx_weight_at(int nch16, int ntp, int sl, int ch, int tp, int pl, int ns,
+                                                            int ln, int jj) {
+    const int col = ln & 15, kg = ln >> 4;
+    return {((((((size_t)sl * nch16 + ch) * ntp + tp) * 2 + pl) * 2 + ns) * 64 + ln) * 8 + jj,
+            2 * tp + (kg & 1), ch * BX_CC + 8 * (kg >> 1) + jj, sl * 32 + ns * 16 + col};
+}
+// The weights' exponent sw: max |w| 2^sw in [8, 16).  wmax is positive and finite (the callers' guards).
+__host__ __device__ __forceinline__ int hx_weight_shift(float wmax) {
+    int ew = 0;
+    (void)frexpf(wmax, &ew);                                 // wmax < 2^ew
+    return 4 - ew;
+}
+
 struct HxScale {
     const float *amax_in;     // device [B]: max |input| of every window of this launch
     float *amax_out;          // device [B] or null: max |output| per window (atomicMax, zeroed by the caller)

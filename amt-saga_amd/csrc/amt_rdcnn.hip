@@ -174,50 +174,62 @@ static void choose_tile16(ConvOp &c) {
     choose_tile_split(c, c.bf16, 256, [&](size_t npos) { return npos * BX_PSTRIDE + 3 * slab + (size_t)256 * 8; });
 }
 
-// the plan's workgroup tile into the launch parameters; returns the number of position tiles (gridDim.x)
-static unsigned apply_plan(ConvParams &p, const ConvPlan &pl) {
-    p.TH = pl.TH; p.TW = pl.TW; p.NWIN = pl.NWIN;
-    p.tiles_h = (p.H + p.TH - 1) / p.TH; p.tiles_w = (p.W + p.TW - 1) / p.TW;
-    const int groups = (p.B + p.NWIN - 1) / p.NWIN;
-    return (unsigned)((size_t)groups * p.tiles_h * p.tiles_w);
-}
-
-template <int KH, int KW, int CIN, int COUT, bool MASKED>
-static int launch_conv16_t(const ConvOp &c, ConvParams p, hipStream_t st) {
-    auto kern = conv_bf16x6_kernel<KH, KW, CIN, COUT, MASKED>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        AMT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)(80 * 1024)));
-        attr_set = true;
-    }
-    const unsigned grid = apply_plan(p, c.bf16);
-    kern<<<dim3(grid, c.bf16.nslice), 512, c.bf16.lds, st>>>(p, static_cast<const uint4 *>(c.bf16.w));
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
-}
-template <int KH, int KW>
-static int launch_conv16_k(const ConvOp &c, const ConvParams &p, hipStream_t st) {
-#define BX_CASE(CI, CO)                                                              \
-    if (c.cin == CI && c.bf16.cw == CO)                                              \
-        return c.bf16.masked ? launch_conv16_t<KH, KW, CI, CO, true>(c, p, st)          \
-                          : launch_conv16_t<KH, KW, CI, CO, false>(c, p, st);
-    BX_CASE(32, 32) BX_CASE(32, 64) BX_CASE(64, 64) BX_CASE(128, 64)
-#undef BX_CASE
-    return AMT_E_UNSUPPORTED;
-}
-// channel pairs of the matrix-pipe convolutions (all three arithmetics)
+// ---- the supported shapes, each stated once: what the kernels are instantiated for (amt_dispatch, amt_common.h) ------
+// kernel sizes (kh, kw), every family
+using ConvKernelSizes = amt_cases<amt_case<4, 16>, amt_case<4, 2>, amt_case<2, 2>>;
+// f32 MFMA (cin, slice width)
+using F32Shapes = amt_cases<amt_case<32, 32>, amt_case<32, 64>, amt_case<64, 64>, amt_case<64, 128>, amt_case<128, 128>,
+                            amt_case<64, 32>, amt_case<128, 32>>;
+// split-bf16 (cin, slice width)
+using Bf16Shapes = amt_cases<amt_case<32, 32>, amt_case<32, 64>, amt_case<64, 64>, amt_case<128, 64>>;
+// split-fp16 cin (32-wide slices), inference and trainer forms
+using F16Cins = amt_values<32, 64, 128>;
+// split-fp16 window-major (cin, positions per wave), 4 x 16 kernels only
+using WmajorShapes = amt_cases<amt_case<32, 3>, amt_case<32, 5>, amt_case<32, 8>, amt_case<64, 3>, amt_case<64, 5>,
+                               amt_case<64, 8>, amt_case<128, 3>, amt_case<128, 5>, amt_case<128, 8>>;
+using Flag = amt_values<0, 1>;      // a bool template argument
+template <class List, class... V>
+static bool in_list(List l, V... v) { return amt_dispatch(l, v..., [](auto...) { return (int)AMT_OK; }) == AMT_OK; }
+static bool conv_supported(int kh, int kw) { return in_list(ConvKernelSizes{}, kh, kw); }
+// channel pairs (cin, cout) of the LAYERS the matrix-pipe convolutions run (all three arithmetics, in the slices above)
 static bool conv_channels_supported(int cin, int cout) {
     return (cin == 32 && cout == 32) || (cin == 32 && cout == 64) || (cin == 64 && cout == 64) ||
            (cin == 64 && cout == 128) || (cin == 128 && cout == 128);
 }
-static int launch_conv16(const ConvOp &c, const ConvParams &p, hipStream_t st) {
-    if (c.kh == 4 && c.kw == 16) return launch_conv16_k<4, 16>(c, p, st);
-    if (c.kh == 4 && c.kw == 2) return launch_conv16_k<4, 2>(c, p, st);
-    if (c.kh == 2 && c.kw == 2) return launch_conv16_k<2, 2>(c, p, st);
-    return AMT_E_UNSUPPORTED;
+
+// ---- THE launch of a tiled kernel --------------------------------------------------------------------------------------
+// the workgroup tile into the launch parameters; returns the number of position tiles (gridDim.x)
+static unsigned apply_tile(ConvParams &p, int TH, int TW, int NWIN) {
+    p.TH = TH; p.TW = TW; p.NWIN = NWIN;
+    p.tiles_h = (p.H + p.TH - 1) / p.TH; p.tiles_w = (p.W + p.TW - 1) / p.TW;
+    const int groups = (p.B + p.NWIN - 1) / p.NWIN;
+    return (unsigned)((size_t)groups * p.tiles_h * p.tiles_w);
+}
+static unsigned apply_plan(ConvParams &p, const ConvPlan &pl) { return apply_tile(p, pl.TH, pl.TW, pl.NWIN); }
+// Kern's first launch in the process raises its dynamic-LDS limit to lds_cap bytes (0: it stays within the default)
+template <auto Kern, class... Args>
+static int launch_tiled(int lds_cap, dim3 grid, unsigned block, size_t lds, hipStream_t st, Args... args) {
+    static bool attr_set = false;
+    if (lds_cap && !attr_set) {
+        AMT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_cap));
+        attr_set = true;
+    }
+    Kern<<<grid, block, lds, st>>>(args...);
+    AMT_LAUNCH_CHECK();
+    return AMT_OK;
 }
 
+static int launch_conv16(const ConvOp &c, ConvParams p, hipStream_t st) {
+    const dim3 grid(apply_plan(p, c.bf16), c.bf16.nslice);
+    return amt_dispatch(ConvKernelSizes{}, c.kh, c.kw, [&](auto KH, auto KW) {
+        return amt_dispatch(Bf16Shapes{}, c.cin, c.bf16.cw, [&](auto CI, auto CW) {
+            return amt_dispatch(Flag{}, c.bf16.masked, [&](auto MASKED) {
+                return launch_tiled<conv_bf16x6_kernel<KH(), KW(), CI(), CW(), MASKED() != 0>>(
+                    80 * 1024, grid, 512, c.bf16.lds, st, p, static_cast<const uint4 *>(c.bf16.w));
+            });
+        });
+    });
+}
 
 // ---- split-fp16 variant: tile choice and launch ---------------------------------------------
 #define HX_SLAB_BYTES 4096
@@ -275,112 +287,56 @@ static void choose_tile_w(ConvOp &c) {
     p.wm_ms = 0;
     const char *e = getenv("AMT_CONV_WMAJOR");
     if (e && e[0] == '0') return;
-    if (!p.masked || c.kh != 4 || c.kw != 16 || !(c.cin == 32 || c.cin == 64 || c.cin == 128)) return;
+    if (!p.masked || c.kh != 4 || c.kw != 16 || !in_list(F16Cins{}, c.cin)) return;
     const int npos = c.H * c.W, ms = (npos + HXW_NWAVE - 1) / HXW_NWAVE;
     p.wm_ms = ms <= 3 ? 3 : ms <= 5 ? 5 : 8;
     p.wm_lds = hxw_lds_bytes<16>(npos);
 }
 
-template <int KH, int KW, int CIN, bool MASKED>
-static int launch_convs_t(const ConvOp &c, ConvParams p, const float *amax_in, float *amax_out, hipStream_t st) {
-    auto kern = conv_f16x3s_kernel<KH, KW, CIN, MASKED>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        AMT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)(80 * 1024)));
-        attr_set = true;
-    }
-    const unsigned grid = apply_plan(p, c.f16);
-    HxScale hs{amax_in, amax_out, c.sw, nullptr};
-    const size_t nwg = (size_t)grid * c.f16.nslice;
-    if (conv_ts_wanted()) { const int rc = conv_ts_buffer(nwg, &hs.ts); if (rc != AMT_OK) return rc; }
-    kern<<<dim3(grid, c.f16.nslice), 512, c.f16.lds, st>>>(p, static_cast<const uint4 *>(c.f16.w), hs);
-    AMT_LAUNCH_CHECK();
-    if (hs.ts) return conv_ts_report(c, MASKED ? "masked1" : "masked0", hs.ts, nwg, 512, st);
-    return AMT_OK;
+// split-fp16 single-tile kernel on the plan's tile: 32-wide N-slices in blockIdx.y, small images its masked form;
+// TRAIN: the trainer's form (amt_convh_run)
+template <bool TRAIN>
+static int launch_convs(int kh, int kw, int cin, bool masked, dim3 grid, size_t lds, const ConvParams &p, const void *w,
+                        const HxScale &hs, hipStream_t st) {
+    return amt_dispatch(ConvKernelSizes{}, kh, kw, [&](auto KH, auto KW) {
+        return amt_dispatch(F16Cins{}, cin, [&](auto CI) {
+            return amt_dispatch(Flag{}, masked, [&](auto MASKED) {
+                return launch_tiled<conv_f16x3s_kernel<KH(), KW(), CI(), MASKED() != 0, 2, TRAIN>>(
+                    80 * 1024, grid, 512, lds, st, p, static_cast<const uint4 *>(w), hs);
+            });
+        });
+    });
 }
-// window-major small-image form: 16 windows x all positions x 32 output channels per workgroup, the N-slice in the low
-// bits of the 1-D workgroup id; one workgroup per CU
-template <int KH, int KW, int CIN, int MS>
-static int launch_convw_t(const ConvOp &c, ConvParams p, const float *amax_in, float *amax_out, hipStream_t st) {
-    auto kern = conv_f16x3w_kernel<KH, KW, CIN, MS>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        AMT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-        attr_set = true;
-    }
-    p.TH = p.H; p.TW = p.W; p.NWIN = HXW_WIN; p.tiles_h = p.tiles_w = 1;
-    const size_t nwg = (size_t)((p.B + HXW_WIN - 1) / HXW_WIN) * c.f16.nslice;
+// The inference forms.  Window-major (wm_ms > 0): 16 windows x all positions x 32 output channels per workgroup, the
+// N-slice in the low bits of the 1-D workgroup id; one workgroup per CU
+static int launch_convh(const ConvOp &c, ConvParams p, const float *amax_in, float *amax_out, hipStream_t st) {
+    const ConvPlan &pl = c.f16;
+    const bool wmajor = pl.wm_ms > 0;
+    if (!pl.w || pl.cw != 32) return AMT_E_UNSUPPORTED;
+    if (wmajor && (c.kh != 4 || c.kw != 16 || c.H * c.W > 8 * pl.wm_ms)) return AMT_E_UNSUPPORTED;
+    const unsigned grid = wmajor ? apply_tile(p, p.H, p.W, HXW_WIN) : apply_plan(p, pl);
+    const size_t nwg = (size_t)grid * pl.nslice;
     HxScale hs{amax_in, amax_out, c.sw, nullptr};
     if (conv_ts_wanted()) { const int rc = conv_ts_buffer(nwg, &hs.ts); if (rc != AMT_OK) return rc; }
-    kern<<<dim3((unsigned)nwg), 64 * HXW_NWAVE, c.f16.wm_lds, st>>>(p, static_cast<const uint4 *>(c.f16.w), hs, c.f16.nslice);
-    AMT_LAUNCH_CHECK();
-    if (hs.ts) return conv_ts_report(c, "wmajor", hs.ts, nwg, 256, st);
-    return AMT_OK;
-}
-static int launch_convw(const ConvOp &c, const ConvParams &p, const float *amax_in, float *amax_out, hipStream_t st) {
-    if (!c.f16.w || c.f16.cw != 32 || c.kh != 4 || c.kw != 16 || c.H * c.W > 8 * c.f16.wm_ms) return AMT_E_UNSUPPORTED;
-#define HXW_CASE(CI, MS)                                                                   \
-    if (c.cin == CI && c.f16.wm_ms == MS) return launch_convw_t<4, 16, CI, MS>(c, p, amax_in, amax_out, st);
-    HXW_CASE(32, 3) HXW_CASE(32, 5) HXW_CASE(32, 8)
-    HXW_CASE(64, 3) HXW_CASE(64, 5) HXW_CASE(64, 8)
-    HXW_CASE(128, 3) HXW_CASE(128, 5) HXW_CASE(128, 8)
-#undef HXW_CASE
-    return AMT_E_UNSUPPORTED;
-}
-template <int KH, int KW>
-static int launch_convh_k(const ConvOp &c, const ConvParams &p, const float *amax_in, float *amax_out, hipStream_t st) {
-    // every layer runs 32-wide N-slices (blockIdx.y) of the single-tile kernel; small images its masked form
-    if (!c.f16.w || c.f16.cw != 32) return AMT_E_UNSUPPORTED;
-#define HXS_CASE(CI)                                                                       \
-    if (c.cin == CI)                                                                       \
-        return c.f16.masked ? launch_convs_t<KH, KW, CI, true>(c, p, amax_in, amax_out, st)               \
-                            : launch_convs_t<KH, KW, CI, false>(c, p, amax_in, amax_out, st);
-    HXS_CASE(32) HXS_CASE(64) HXS_CASE(128)
-#undef HXS_CASE
-    return AMT_E_UNSUPPORTED;
-}
-static int launch_convh(const ConvOp &c, const ConvParams &p, const float *amax_in, float *amax_out, hipStream_t st) {
-    if (c.f16.wm_ms > 0) return launch_convw(c, p, amax_in, amax_out, st);
-    if (c.kh == 4 && c.kw == 16) return launch_convh_k<4, 16>(c, p, amax_in, amax_out, st);
-    if (c.kh == 4 && c.kw == 2) return launch_convh_k<4, 2>(c, p, amax_in, amax_out, st);
-    if (c.kh == 2 && c.kw == 2) return launch_convh_k<2, 2>(c, p, amax_in, amax_out, st);
-    return AMT_E_UNSUPPORTED;
+    const int rc = !wmajor ? launch_convs<false>(c.kh, c.kw, c.cin, pl.masked, dim3(grid, pl.nslice), pl.lds, p, pl.w, hs, st)
+                           : amt_dispatch(WmajorShapes{}, c.cin, pl.wm_ms, [&](auto CI, auto MS) {
+                                 return launch_tiled<conv_f16x3w_kernel<4, 16, CI(), MS()>>(
+                                     160 * 1024, dim3((unsigned)nwg), 64 * HXW_NWAVE, pl.wm_lds, st, p,
+                                     static_cast<const uint4 *>(pl.w), hs, pl.nslice);
+                             });
+    if (rc != AMT_OK || !hs.ts) return rc;
+    return conv_ts_report(c, wmajor ? "wmajor" : pl.masked ? "masked1" : "masked0", hs.ts, nwg, wmajor ? 256 : 512, st);
 }
 
-template <int KH, int KW, int CIN, int COUT, int MT>
-static int launch_conv_t(const ConvOp &c, ConvParams p, hipStream_t st) {
-    auto kern = conv_mfma_kernel<KH, KW, CIN, COUT, MT>;
-    static size_t attr_set = 0;
-    if (c.f32.lds > attr_set) {
-        AMT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)(152 * 1024)));
-        attr_set = 152 * 1024;
-    }
-    const unsigned grid = apply_plan(p, c.f32);
-    kern<<<dim3(grid, c.f32.nslice), 256, c.f32.lds, st>>>(p);
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
-}
-
-template <int KH, int KW>
-static int launch_conv_k(const ConvOp &c, const ConvParams &p, hipStream_t st) {
-#define RD_CASE(CI, CO)                                                         \
-    if (c.cin == CI && c.f32.cw == CO)                                          \
-        return c.MT == 2 ? launch_conv_t<KH, KW, CI, CO, 2>(c, p, st)           \
-                         : launch_conv_t<KH, KW, CI, CO, 1>(c, p, st);
-    RD_CASE(32, 32) RD_CASE(32, 64) RD_CASE(64, 64) RD_CASE(64, 128) RD_CASE(128, 128)
-    RD_CASE(64, 32) RD_CASE(128, 32)
-#undef RD_CASE
-    return AMT_E_UNSUPPORTED;
-}
-
-static int launch_conv(const ConvOp &c, const ConvParams &p, hipStream_t st) {
-    if (c.kh == 4 && c.kw == 16) return launch_conv_k<4, 16>(c, p, st);
-    if (c.kh == 4 && c.kw == 2) return launch_conv_k<4, 2>(c, p, st);
-    if (c.kh == 2 && c.kw == 2) return launch_conv_k<2, 2>(c, p, st);
-    return AMT_E_UNSUPPORTED;
+static int launch_conv(const ConvOp &c, ConvParams p, hipStream_t st) {
+    const dim3 grid(apply_plan(p, c.f32), c.f32.nslice);
+    return amt_dispatch(ConvKernelSizes{}, c.kh, c.kw, [&](auto KH, auto KW) {
+        return amt_dispatch(F32Shapes{}, c.cin, c.f32.cw, [&](auto CI, auto CW) {
+            return amt_dispatch(amt_values<2, 1>{}, c.MT, [&](auto MT) {
+                return launch_tiled<conv_mfma_kernel<KH(), KW(), CI(), CW(), MT()>>(152 * 1024, grid, 256, c.f32.lds, st, p);
+            });
+        });
+    });
 }
 
 static void choose_tile1(int H, int W, int *TH_, int *TW_) {
@@ -395,10 +351,6 @@ static void choose_tile1(int H, int W, int *TH_, int *TW_) {
     }
 }
 
-static bool conv_supported(int kh, int kw) {
-    return (kh == 4 && kw == 16) || (kh == 4 && kw == 2) || (kh == 2 && kw == 2);
-}
-
 static int launch_conv1_mfma(const ConvOp &c, const Conv1Params &cp, hipStream_t st) {
     int TH1 = 1, TW1 = 1;
     choose_tile1(cp.H, cp.W, &TH1, &TW1);
@@ -406,11 +358,9 @@ static int launch_conv1_mfma(const ConvOp &c, const Conv1Params &cp, hipStream_t
     const size_t lds = (size_t)2 * C1M_PCAP * 4 + (size_t)4 * 32 * HX_TPITCH * 4 +
                        (size_t)(TH1 + c.kh - 1) * (TW1 + c.kw - 1) * 4;
     const unsigned grid = (unsigned)std::min<size_t>((size_t)cp.B * th * twn, 256 * 8);
-    if (c.kh == 4 && c.kw == 16) conv1_mfma_kernel<4, 16><<<grid, 256, lds, st>>>(cp, TH1, TW1, th, twn);
-    else if (c.kh == 4 && c.kw == 2) conv1_mfma_kernel<4, 2><<<grid, 256, lds, st>>>(cp, TH1, TW1, th, twn);
-    else conv1_mfma_kernel<2, 2><<<grid, 256, lds, st>>>(cp, TH1, TW1, th, twn);
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
+    return amt_dispatch(ConvKernelSizes{}, c.kh, c.kw, [&](auto KH, auto KW) {
+        return launch_tiled<conv1_mfma_kernel<KH(), KW()>>(0, grid, 256, lds, st, cp, TH1, TW1, th, twn);
+    });
 }
 static int launch_conv1(const ConvOp &c, const Conv1Params &cp, hipStream_t st) {
     const int groups = 256 / c.cout;
@@ -500,30 +450,20 @@ static std::vector<unsigned short> pack_bf16x6(const float *kern, int ntap, int 
                                 }
     return w16;
 }
-// split-fp16, weights scaled by wscale: [slice][chunk16][tap pair][plane][N-subtile][lane = col + 16 kgroup][8] f16,
-// kgroup g = (tap 2 tp + g % 2, channels 8 (g / 2) .. + 7); 32-wide slices
+// split-fp16, weights scaled by wscale: the layout of hx_weight_at (amt_conv_f16x3.h)
 static std::vector<unsigned short> pack_f16x3(const float *kern, int ntap, int C, int fo, float wscale) {
-    const int NT = fo / 32, nsliceh = fo / 32;
-    const int nch16 = C / BX_CC;
-    std::vector<unsigned short> ws((size_t)nch16 * ntap * 2 * NT * 2 * 32 * 8);
-    const int ntp = ntap / 2;
+    const int nsliceh = fo / 32, nch16 = C / BX_CC, ntp = ntap / 2;
+    std::vector<unsigned short> ws((size_t)ntap * C * fo * 2);
     for (int sl = 0; sl < nsliceh; ++sl)
         for (int ch = 0; ch < nch16; ++ch)
             for (int tp = 0; tp < ntp; ++tp)
                 for (int ns = 0; ns < 2; ++ns)
                     for (int ln = 0; ln < 64; ++ln)
                         for (int jj = 0; jj < 8; ++jj) {
-                            const int col = ln & 15, kg = ln >> 4;
-                            const int tap = 2 * tp + (kg & 1);
-                            const int cin_i = ch * BX_CC + 8 * (kg >> 1) + jj;
-                            const float wv = kern[((size_t)tap * C + cin_i) * fo + sl * 32 + ns * 16 + col];
+                            const HxWeightAt at = hx_weight_at(nch16, ntp, sl, ch, tp, 0, ns, ln, jj);
                             unsigned short hh[2];
-                            amt_split_f16<true>(wv * wscale, hh[0], hh[1]);
-                            for (int pl = 0; pl < 2; ++pl) {
-                                const size_t idx =
-                                    ((((((size_t)sl * nch16 + ch) * ntp + tp) * 2 + pl) * 2 + ns) * 64 + ln) * 8 + jj;
-                                ws[idx] = hh[pl];
-                            }
+                            amt_split_f16<true>(kern[((size_t)at.tap * C + at.cin) * fo + at.cout] * wscale, hh[0], hh[1]);
+                            for (int pl = 0; pl < 2; ++pl) ws[hx_weight_at(nch16, ntp, sl, ch, tp, pl, ns, ln, jj).idx] = hh[pl];
                         }
     return ws;
 }
@@ -565,9 +505,7 @@ static int build_conv_variants(amt_rdcnn *n, ConvOp &c, const float *kern) {
         wmax = std::max(wmax, fabsf(kern[q]));
     }
     if (c.f16.TH > 0 && finite && wmax > 0.f) {
-        int ew = 0;
-        (void)frexpf(wmax, &ew);                          // wmax < 2^ew
-        c.sw = 4 - ew;                                     // max |w| 2^sw in [8, 16)
+        c.sw = hx_weight_shift(wmax);
         const std::vector<unsigned short> ws = pack_f16x3(kern, ntap, C, fo, ldexpf(1.0f, c.sw));
         if ((rc = upload(n, ws.data(), ws.size() * 2, &c.f16.w)) != AMT_OK) return rc;
     }
@@ -985,7 +923,7 @@ int amt_rdcnn_forward(const amt_rdcnn *net, const float *const *x, int B, float 
 // ---- trainer form of the split-fp16 kernels (amt_convh.h) --------------------------------------------------------
 int amt_convh_plan_init(amt_convh_plan *pl, int kh, int kw, int cin, int cout, int H, int W) {
     if (!pl || !conv_supported(kh, kw)) return AMT_E_UNSUPPORTED;
-    if (!(cin == 32 || cin == 64 || cin == 128) || cout < 32 || cout % 32 != 0 || H < 1 || W < 1) return AMT_E_UNSUPPORTED;
+    if (!in_list(F16Cins{}, cin) || cout < 32 || cout % 32 != 0 || H < 1 || W < 1) return AMT_E_UNSUPPORTED;
     ConvOp c;
     c.cin = cin; c.cout = cout; c.H = H; c.W = W; c.kh = kh; c.kw = kw;
     c.f16.cw = 32; c.f16.nslice = cout / 32;
@@ -1008,17 +946,14 @@ __global__ __launch_bounds__(256) void convh_wmax_kernel(const amt_convh_pack_jo
     m = block_max(m, red);
     if (threadIdx.x == 0) atomicMax(reinterpret_cast<int *>(j.wmax), __float_as_int(m));
 }
-// one thread per (slice, chunk, tap pair, N-subtile, lane): eight channels x two planes = two 16-byte stores.
-// Layout (the host loop of amt_rdcnn_create, "split-fp16 weights"): [slice][chunk16][tap pair][plane][N-subtile][lane][8]
+// one thread per (slice, chunk, tap pair, N-subtile, lane): eight channels x two planes = two 16-byte stores.  The
+// layout is hx_weight_at's (amt_conv_f16x3.h; pack_f16x3 is the host's packer), spelled out here in 16-byte units:
+// going through that function costs this kernel a register and two instructions
 __global__ __launch_bounds__(256) void convh_pack_kernel(const amt_convh_pack_job *jobs) {
     const amt_convh_pack_job j = jobs[blockIdx.y];
     const float wmax = *j.wmax;
     int sw = 0;
-    if (wmax > 0.f && wmax < 3.0e38f) {
-        int ew = 0;
-        (void)frexpf(wmax, &ew);
-        sw = 4 - ew;
-    }
+    if (wmax > 0.f && wmax < 3.0e38f) sw = hx_weight_shift(wmax);
     if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == 0) *j.sw = sw;
     const float wscale = ldexpf(1.0f, sw);
     const bool bwd = blockIdx.z == 1;
@@ -1067,43 +1002,15 @@ int amt_convh_pack_all(const amt_convh_pack_job *jobs_dev, int n, int max_elems,
 int amt_convh_absmax(const float *x, size_t n, int B, float *amax, hipStream_t st) {
     return launch_absmax(x, n, n, B, amax, st);
 }
-template <int KH, int KW, int CIN, bool MASKED>
-static int launch_convtr_t(const amt_convh_plan &pl, const ConvParams &p, const void *packed, const HxScale &hs, hipStream_t st) {
-    auto kern = conv_f16x3s_kernel<KH, KW, CIN, MASKED, 2, true>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        AMT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)(80 * 1024)));
-        attr_set = true;
-    }
-    const int groups = (p.B + p.NWIN - 1) / p.NWIN;
-    const unsigned grid = (unsigned)((size_t)groups * p.tiles_h * p.tiles_w);
-    kern<<<dim3(grid, pl.cout / 32), 512, pl.lds, st>>>(p, static_cast<const uint4 *>(packed), hs);
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
-}
-template <int KH, int KW>
-static int launch_convtr_k(const amt_convh_plan &pl, const ConvParams &p, const void *packed, const HxScale &hs, hipStream_t st) {
-#define HXT_CASE(CI)                                                                            \
-    if (pl.cin == CI)                                                                           \
-        return pl.masked ? launch_convtr_t<KH, KW, CI, true>(pl, p, packed, hs, st)             \
-                         : launch_convtr_t<KH, KW, CI, false>(pl, p, packed, hs, st);
-    HXT_CASE(32) HXT_CASE(64) HXT_CASE(128)
-#undef HXT_CASE
-    return AMT_E_UNSUPPORTED;
-}
 int amt_convh_run(const amt_convh_plan *pl, const float *in, float *out, const float *acc, int B, const void *packed,
                   const int *sw_dev, const float *bias, const float *amax_in, int pad_t, int pad_l, hipStream_t st) {
     if (!pl || !in || !out || !packed || !sw_dev || !amax_in || B <= 0) return AMT_E_INVALID;
     if (pad_t < 0 || pad_t >= pl->kh || pad_l < 0 || pad_l >= pl->kw) return AMT_E_INVALID;
     const size_t istr = (size_t)pl->H * pl->W * pl->cin, ostr = (size_t)pl->H * pl->W * pl->cout;
-    ConvParams p{in, istr, out, ostr, acc, ostr, nullptr, nullptr, bias, nullptr, nullptr,
-                 B, pl->H, pl->W, pl->TH, pl->TW, pl->NWIN, (pl->H + pl->TH - 1) / pl->TH, (pl->W + pl->TW - 1) / pl->TW, pl->cout};
+    ConvParams p{in, istr, out, ostr, acc, ostr, nullptr, nullptr, bias, nullptr, nullptr, B, pl->H, pl->W, 0, 0, 1, 0, 0, pl->cout};
     p.pad_t = pad_t; p.pad_l = pad_l;
+    const dim3 grid(apply_tile(p, pl->TH, pl->TW, pl->NWIN), pl->cout / 32);
     HxScale hs{amax_in, nullptr, 0, nullptr};
     hs.sw_dev = sw_dev;
-    if (pl->kh == 4 && pl->kw == 16) return launch_convtr_k<4, 16>(*pl, p, packed, hs, st);
-    if (pl->kh == 4 && pl->kw == 2) return launch_convtr_k<4, 2>(*pl, p, packed, hs, st);
-    if (pl->kh == 2 && pl->kw == 2) return launch_convtr_k<2, 2>(*pl, p, packed, hs, st);
-    return AMT_E_UNSUPPORTED;
+    return launch_convs<true>(pl->kh, pl->kw, pl->cin, pl->masked != 0, grid, pl->lds, p, packed, hs, st);
 }

@@ -608,14 +608,10 @@ static int launch_istft_ragged(const amt_stft_plan *plan, const float *mag, cons
     return AMT_E_UNSUPPORTED;
 }
 
-// the transform size of a plan as a compile-time constant: f(std::integral_constant<int, N>) for the first N of the list
-// that equals n_fft, AMT_E_UNSUPPORTED if none does
-template <int N0, int... Ns, class F>
-static int with_n_fft(int n_fft, F f) {
-    if (n_fft == N0) return f(std::integral_constant<int, N0>{});
-    if constexpr (sizeof...(Ns) > 0) return with_n_fft<Ns...>(n_fft, f);
-    else return AMT_E_UNSUPPORTED;
-}
+// the transform sizes the kernels are built for; amt_dispatch (amt_common.h) hands a plan's n_fft to a launcher as a
+// compile-time constant
+using StftSizes = amt_values<256, 512, 1024, 2048, 4096>;
+using IstftRaggedSizes = amt_values<1024, 2048, 4096>;
 
 // ---------------------------------------------------------------------------------
 // C ABI
@@ -700,7 +696,7 @@ int amt_stft_mag(const amt_stft_plan *plan, const float *wave, int B, int L, siz
     if (plan->center && L <= plan->n_fft / 2) return AMT_E_SHAPE;   // reflect pad needs L > n_fft/2
     hipStream_t st = (hipStream_t)stream;
     if (ref_max) AMT_HIP_CHECK(hipMemsetAsync(ref_max, 0, sizeof(float) * B, st));
-    return with_n_fft<256, 512, 1024, 2048, 4096>(plan->n_fft, [&](auto N) {
+    return amt_dispatch(StftSizes{}, plan->n_fft, [&](auto N) {
         return launch_stft<N()>(plan, wave, B, L, wave_stride, mag, phase_ri, ref_max, T, ldf, spec_stride, st);
     });
 }
@@ -717,7 +713,7 @@ int amt_stft_mag_ragged(const amt_stft_plan *plan, const float *samples, const i
     if (plan->center ? max_len <= plan->n_fft / 2 : max_len < plan->n_fft) return AMT_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     if (ref_max) AMT_HIP_CHECK(hipMemsetAsync(ref_max, 0, sizeof(float) * n, st));
-    return with_n_fft<256, 512, 1024, 2048, 4096>(plan->n_fft, [&](auto N) {
+    return amt_dispatch(StftSizes{}, plan->n_fft, [&](auto N) {
         return launch_stft_ragged<N()>(plan, samples, sample_base, length, n, max_len, n_samples, total_len, mag, phase_ri,
                                        ref_max, frame_base, pool_frames, ldf, st);
     });
@@ -733,7 +729,7 @@ int amt_istft(const amt_stft_plan *plan, const float *mag, const float *phase_ri
     // spec_stride: bins with a phase array; floats of the interleaved complex array without one (a float2 per bin)
     if (spec_stride < (size_t)T * ldf * (phase_ri ? 1 : 2) || (!phase_ri && (spec_stride & 1))) return AMT_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
-    return with_n_fft<256, 512, 1024, 2048, 4096>(plan->n_fft, [&](auto N) {
+    return amt_dispatch(StftSizes{}, plan->n_fft, [&](auto N) {
         return launch_istft<N()>(plan, mag, phase_ri, B, T, ldf, spec_stride, wave_out, wave_stride, Lout, st);
     });
 }
@@ -748,7 +744,7 @@ int amt_istft_ragged(const amt_stft_plan *plan, const float *mag, const float *p
     if (ldf < F || max_frames <= 0 || pool_frames <= 0 || n_out < 0) return AMT_E_SHAPE;
     if (max_frames < 2) return AMT_OK;                              // no signal has a sample
     hipStream_t st = (hipStream_t)stream;
-    return with_n_fft<1024, 2048, 4096>(plan->n_fft, [&](auto N) {
+    return amt_dispatch(IstftRaggedSizes{}, plan->n_fft, [&](auto N) {
         return launch_istft_ragged<N()>(plan, mag, phase_ri, frame_base, t_frames, n, max_frames, pool_frames, ldf, out,
                                         out_base, n_out, st);
     });

@@ -522,6 +522,14 @@ def test_cqt_window_max_full_window(env):
     dict(shape=(16, 8), k=(2, 2), pool=(2, 2), L=6, pf=3, ef=3, r=2, K=1),
     dict(shape=(20, 70), k=(4, 16), pool=(2, 8), L=3, pf=0, ef=0, r=0, K=3),
     dict(shape=(11, 9), k=(4, 2), pool=(2, 2), L=4, pf=4, ef=2, r=1, K=1),
+    # every supported channel pair (32 -> 32, 32 -> 64, 64 -> 64, 64 -> 128, 128 -> 128) at every kernel size: pooled
+    # (288, 72 and 18 positions: halo tiles, then the masked and window-major forms and the f32 kernel's 32-wide
+    # slices) and unpooled (every pair on 400 positions)
+    dict(shape=(12, 24), k=(4, 16), pool=(2, 2), L=6, pf=2, ef=2, r=2, K=3),
+    dict(shape=(12, 24), k=(4, 2), pool=(2, 2), L=6, pf=2, ef=2, r=2, K=1),
+    dict(shape=(12, 24), k=(2, 2), pool=(2, 2), L=6, pf=2, ef=2, r=2, K=3),
+    dict(shape=(10, 40), k=(4, 16), pool=(2, 2), L=6, pf=0, ef=2, r=3, K=1),
+    dict(shape=(10, 40), k=(2, 2), pool=(2, 2), L=6, pf=0, ef=2, r=3, K=1),
 ])
 def test_small_topologies(env, case):
     """Shallow nets: every layer kind (Cin=1 conv, 32/64/128-channel MFMA convs,
