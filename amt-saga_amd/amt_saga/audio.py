@@ -899,9 +899,11 @@ class audio_complete:
         return float(np.mean(out.cpu().numpy().astype(np.float64)))
 
     def save(self, filename, flac=True):
-        """util_audio.py:520-527: the waveform as PCM-24 FLAC (the WAV branch is not provided)."""
+        """util_audio.py:520-527: the waveform as PCM-24 FLAC, or with flac=False as a float32 WAV normalised to its
+        peak -- what librosa.output.write_wav(filename, self.wf, self.sr, norm=True) writes for a float waveform."""
         if not flac:
-            raise NotImplementedError('only FLAC output is provided')
+            return save_wav(to_dev(np.asarray(self.wf, dtype=np.float32).reshape(-1)), filename, self.sr,
+                            fmt='float32', norm=True)
         from . import flac as _flac
         _flac.save_float(np.asarray(self.wf), filename, sr=self.sr, bps=24)
 
@@ -1262,3 +1264,147 @@ def load_flac(paths, verify=True, pcm=False):
             datas.append(f.read())
     res = flac_decode(datas, verify=verify, pcm=pcm)
     return res[0] if single else res
+
+
+# ======================================================================================
+# WAV files on the device (librosa.load for a WAV file, util_audio.py:962-964; write_wav, util_audio.py:526-527)
+# ======================================================================================
+PCM_TILE = 1024                    # values one workgroup of the unpack / pack kernels takes at a time (AMT_PCM_TILE)
+PCM_KINDS = {'int': 0, 'float': 1}
+PCM_FORMATS = {'pcm16': 0, 'pcm24': 1, 'float32': 2}
+
+
+def _wav_tables(datas):
+    """The host's O(chunks) share of wav_decode, no GPU involved: argument checks and the header of every file.
+    Returns (infos [(sr, channels, kind, bits, frames)], stream_meta int64 [n, 8], out_values).  Every file's output
+    begins on a 16-byte boundary."""
+    from . import wav as _wav
+    if isinstance(datas, (bytes, bytearray, memoryview)) or not isinstance(datas, (list, tuple)):
+        raise ValueError('Invalid Input shape. Expected: a list of bytes . Got: %s' % type(datas).__name__)
+    if not datas:
+        raise ValueError('Invalid Input shape. Expected: at least one file . Got: an empty list')
+    if len(datas) > Resampler.MAX_SIGNALS:
+        raise ValueError('Invalid Input shape. Expected: at most %d files a call . Got: %d'
+                         % (Resampler.MAX_SIGNALS, len(datas)))
+    infos, sm = [], []
+    off = out = 0
+    for d in datas:
+        if not isinstance(d, (bytes, bytearray)):
+            raise ValueError('Invalid Input shape. Expected: a list of bytes . Got: %s in it' % type(d).__name__)
+        sr, ch, kind, bits, c, first, frames = _wav.read_header(d)
+        sm.append([off + first, frames, ch, PCM_KINDS[kind], c, bits, out, 0])
+        infos.append((sr, ch, kind, bits, frames))
+        off += len(d)
+        out += -(-frames * ch // 4) * 4
+    return infos, np.asarray(sm, np.int64).reshape(-1, 8), out
+
+
+def wav_decode(datas, pcm=False):
+    """audio_from_file (util_audio.py:962-964) for WAV files without the host reader: the files `datas` (a list of
+    bytes) unpacked on the device -- one upload of the concatenated bytes, one small table, ONE launch
+    (amt_pcm_unpack_ragged).  Returns a list of (wave, sr, bits) -- wave a float32 device tensor by amt_saga.wav's value
+    rule, [n] for mono and [n, channels] otherwise, views of one buffer -- or (wave, sr, bits, pcm int32) with pcm=True
+    (integer files only: ValueError for a float file in the call).  Every refusal is a ValueError raised by the header
+    walk, before the GPU is touched."""
+    infos, sm, out_values = _wav_tables(datas)
+    if pcm and any(kind == 'float' for _, _, kind, _, _ in infos):
+        _lib.check(_lib.AMT_E_INVALID)
+    lib = _lib.load()
+    dev = torch.device('cuda', torch.cuda.current_device())
+    data = torch.frombuffer(bytearray(b''.join(datas)), dtype=torch.uint8).to(dev)
+    sm_d = torch.from_numpy(sm).to(dev)
+    out = torch.empty((out_values,), dtype=torch.float32, device=dev)
+    out_i = torch.empty((out_values,), dtype=torch.int32, device=dev) if pcm else None
+    _lib.check(lib.amt_pcm_unpack_ragged(ptr(data), data.numel(), ptr(sm_d), len(infos),
+                                         max(f for _, _, _, _, f in infos), ptr(out), ptr(out_i) if pcm else None,
+                                         out_values, stream_ptr()))
+    res = []
+    for (sr, ch, kind, bits, frames), row in zip(infos, sm.tolist()):
+        def view(t, base=row[6], frames=frames, ch=ch):
+            v = t[base:base + frames * ch]
+            return v if ch == 1 else v.view(frames, ch)
+        res.append((view(out), sr, bits) + ((view(out_i),) if pcm else ()))
+    return res
+
+
+def _read_files(paths):
+    single = isinstance(paths, (str, bytes, os.PathLike))
+    datas = []
+    for p in ([paths] if single else list(paths)):
+        with open(p, 'rb') as f:
+            datas.append(f.read())
+    return single, datas
+
+
+def load_wav(paths, pcm=False):
+    """wav_decode of the files at `paths` (one path or a list), read whole and unpacked in one call."""
+    single, datas = _read_files(paths)
+    res = wav_decode(datas, pcm=pcm)
+    return res[0] if single else res
+
+
+def load_audio(paths, verify=True):
+    """The files at `paths` (one path or a list), each taken by its first four bytes: the FLAC files of the call go
+    through ONE flac_decode (with `verify`), the WAV files (RIFF) through ONE wav_decode.  Returns (wave, sr, bits) per
+    file in input order; a file that is neither raises flac_decode's 'not a FLAC file'."""
+    single, datas = _read_files(paths)
+    is_wav = [bytes(d[:4]) == b'RIFF' for d in datas]
+    res = [None] * len(datas)
+    for want, decode in ((False, lambda ds: flac_decode(ds, verify=verify)), (True, wav_decode)):
+        idx = [i for i, w in enumerate(is_wav) if w == want]
+        if idx:
+            for i, r in zip(idx, decode([datas[i] for i in idx])):
+                res[i] = r
+    return res[0] if single else res
+
+
+def wav_encode(waves, sr, fmt='pcm24', norm=False):
+    """librosa.output.write_wav (util_audio.py:526-527) without the file: every signal of `waves` (the conventions of
+    flac_encode: 1-d float32 device tensors, a [G, n] tensor counts as G signals) as the bytes of a complete mono WAV
+    file of `fmt` ('pcm16', 'pcm24' or 'float32'), identical to amt_saga.wav.encode on the same float32 samples.
+    norm=True divides every signal by its own peak first (amt_pcm_peak_ragged; write_wav's norm=True).  One pack call
+    for the whole list on the current stream, one device-to-host copy."""
+    from . import wav as _wav
+    if fmt not in PCM_FORMATS:
+        raise ValueError('Requested attribute does not exist: fmt must be one of %s' % (_wav.FORMATS,))
+    sigs = _flac_signals(waves)
+    if len(sigs) > Resampler.MAX_SIGNALS:
+        raise ValueError('Invalid Input shape. Expected: at most %d signals a call . Got: %d'
+                         % (Resampler.MAX_SIGNALS, len(sigs)))
+    lens = [int(s.numel()) for s in sigs]
+    heads = [_wav.header(l, sr, fmt) for l in lens]                  # (refuses a bad rate or an oversized signal)
+    lib = _lib.load()
+    c = _wav.FORMAT_BYTES[fmt]
+    live = [s.data_ptr() for s, l in zip(sigs, lens) if l]
+    if not live:
+        return heads
+    anchor = min(live)
+    base = [(s.data_ptr() - anchor) // 4 if l else 0 for s, l in zip(sigs, lens)]
+    out_base, total = [], 0
+    for l in lens:
+        out_base.append(total)
+        total += -(-l * c // 4) * 4                                  # every signal's bytes begin on a word
+    dev = sigs[0].device
+    meta = torch.tensor([base, lens, out_base], dtype=torch.int64).to(dev)
+    out = torch.empty((total,), dtype=torch.uint8, device=dev)
+    peaks = None
+    if norm:
+        peaks = torch.empty((len(sigs),), dtype=torch.float32, device=dev)
+        _lib.check(lib.amt_pcm_peak_ragged(C.c_void_p(anchor), ptr(meta[0]), ptr(meta[1]), len(sigs), max(lens),
+                                           ptr(peaks), stream_ptr()))
+    _lib.check(lib.amt_pcm_pack_ragged(C.c_void_p(anchor), ptr(meta[0]), ptr(meta[1]), len(sigs), max(lens),
+                                       PCM_FORMATS[fmt], ptr(peaks) if norm else None, ptr(out), ptr(meta[2]), total,
+                                       stream_ptr()))
+    data = out.cpu().numpy().tobytes()
+    return [h + data[b:b + l * c] + (b'\0' if (l * c) & 1 else b'') for h, b, l in zip(heads, out_base, lens)]
+
+
+def save_wav(waves, paths, sr, fmt='pcm24', norm=False):
+    """wav_encode(waves, sr, fmt, norm) written to `paths`, one file per signal, one write per file."""
+    files = wav_encode(waves, sr, fmt=fmt, norm=norm)
+    paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
+    if len(paths) != len(files):
+        raise ValueError('Invalid Input shape. Expected: one path per signal (%d) . Got: %d' % (len(files), len(paths)))
+    for data, path in zip(files, paths):
+        with open(path, 'wb') as f:
+            f.write(data)

@@ -23,6 +23,10 @@ provide for the inference direction:
     encoder (audio.save_flac), a song's residual and stems in one call, compressed.
     --decode {host,device}: the reader of the input files -- host (default): amt_saga.flac's reader; device: the HIP
     decoder (audio.load_flac), --slots files per decode call with --songs, the samples never on the host.
+    A file that begins with RIFF is read as WAV, by amt_saga.wav's reader (host) or audio.load_audio (device: the FLAC and
+    the WAV files of a group in one decode call each); every other file is read as FLAC.
+    --format {flac,wav} (both modes): the container of --residual / --residual-dir / --stems-dir -- flac (default), or
+    wav: PCM-24 WAV through audio.save_wav, a song's residual and stems in one call, named .residual.wav / .group<g>.wav.
 
 Weights: a directory with {timing_start,timing_end,pitch,instrument,velocity}.npz in the
 naming of amt_saga/rdcnn.py; without it the heads carry their seeded synthetic weights (the
@@ -170,7 +174,14 @@ CLI_GROUPS = (0, 1, 2)                                             # the command
 
 FLAC_WRITERS = ('host', 'device')
 _FLAC_HELP = ("writer of --residual / --residual-dir / --stems-dir: 'host' = the VERBATIM writer (uncompressed FLAC, the "
-              "default), 'device' = the HIP encoder (fixed predictors + Rice coding, one call per song)")
+              "default), 'device' = the HIP encoder (fixed predictors + Rice coding, one call per song); no effect with "
+              "--format wav")
+
+
+FORMATS = ('flac', 'wav')
+_FORMAT_HELP = ("container of --residual / --residual-dir / --stems-dir: 'flac' (the default) or 'wav' = PCM-24 WAV packed "
+                "on the device (audio.save_wav), a song's residual and stems in one call, the generated names ending in "
+                ".residual.wav and .group<g>.wav; with 'wav', --flac has no effect")
 
 
 DECODERS = ('host', 'device')
@@ -181,13 +192,33 @@ _DECODE_HELP = ("reader of the input files: 'host' = the pure-Python reader (the
                 "down in float32 on the device and in float64 on the host, so its samples may differ in the last bit")
 
 
-def write_song_audio(rate, residual=None, residual_path=None, stems=None, stems_dir=None, name=None, flac='host'):
+def _is_wav(path):
+    """True for a file that begins with RIFF; every other file, and a missing one, is left to the FLAC path."""
+    from . import wav
+    try:
+        return wav.is_wav(path)
+    except OSError:
+        return False
+
+
+def _load_float(path, flac):
+    """(float64 waveform, rate) of one file on the host: amt_saga.wav's reader for a RIFF file, else the FLAC reader."""
+    if _is_wav(path):
+        from . import wav
+        return wav.load_float(path)
+    return flac.load_float(path)
+
+
+def write_song_audio(rate, residual=None, residual_path=None, stems=None, stems_dir=None, name=None, flac='host',
+                     format='flac'):
     """What a song walk kept, as 24-bit FLAC at `rate`: `residual` (1-d device tensor) to residual_path, and / or the rows
     of `stems` [G, samples] to <stems_dir>/<name>.group<g>.flac, g the reference group id of the row (CLI_GROUPS).
     flac='host': the VERBATIM writer of amt_saga.flac, file by file (the default: the bytes every earlier call wrote);
     flac='device': audio.save_flac -- the residual and all stems of the song in ONE encode call on the device,
-    compressed, and no sample crosses to the host before it is coded."""
-    if flac not in FLAC_WRITERS:
+    compressed, and no sample crosses to the host before it is coded.
+    format='wav': PCM-24 WAV instead, <name>.group<g>.wav, through audio.save_wav -- one pack call and one copy for the
+    residual and all stems of the song; `flac` then has no effect."""
+    if flac not in FLAC_WRITERS or format not in FORMATS:
         raise ValueError('Requested attribute does not exist')
     waves, paths, notes = [], [], []
     if residual is not None:
@@ -197,11 +228,14 @@ def write_song_audio(rate, residual=None, residual_path=None, stems=None, stems_
     if stems is not None:
         for row, g in zip(stems, CLI_GROUPS):
             waves.append(row)
-            paths.append(os.path.join(stems_dir, '%s.group%d.flac' % (name, g)))
+            paths.append(os.path.join(stems_dir, '%s.group%d.%s' % (name, g, format)))
             notes.append('stem of group %d -> %s' % (g, paths[-1]))
     if not waves:
         return
-    if flac == 'device':
+    if format == 'wav':
+        from . import audio
+        audio.save_wav(waves, paths, rate, fmt='pcm24')
+    elif flac == 'device':
         from . import audio
         audio.save_flac(waves, paths, rate)
     else:
@@ -234,6 +268,7 @@ def main_songs(argv):
                          'took out of the song, 24-bit FLAC at the rate the model runs at')
     ap.add_argument('--flac', default='host', choices=FLAC_WRITERS, help=_FLAC_HELP)
     ap.add_argument('--decode', default='host', choices=DECODERS, help=_DECODE_HELP)
+    ap.add_argument('--format', default='flac', choices=FORMATS, help=_FORMAT_HELP)
     a = ap.parse_args(argv)
     os.makedirs(a.out_dir, exist_ok=True)
     keep, keep_stems = a.residual_dir is not None, a.stems_dir is not None
@@ -258,8 +293,9 @@ def main_songs(argv):
         ev.write_midi(notes, out)
         print('%d notes -> %s' % (len(notes), out))
         write_song_audio(rate, residual=item[3] if keep else None,
-                         residual_path=os.path.join(a.residual_dir, stems[i] + '.residual.flac') if keep else None,
-                         stems=item[-1] if keep_stems else None, stems_dir=a.stems_dir, name=stems[i], flac=a.flac)
+                         residual_path=os.path.join(a.residual_dir, stems[i] + '.residual.' + a.format) if keep else None,
+                         stems=item[-1] if keep_stems else None, stems_dir=a.stems_dir, name=stems[i], flac=a.flac,
+                         format=a.format)
 
 
 def _load_songs(a, flac):
@@ -270,11 +306,14 @@ def _load_songs(a, flac):
         from . import audio
         step = max(1, a.slots)
         for k in range(0, len(a.songs), step):
-            for wf, sr, _ in audio.load_flac(list(a.songs[k:k + step])):
+            group = list(a.songs[k:k + step])
+            # (a group without a RIFF file keeps the FLAC call it always made)
+            load = audio.load_audio if any(_is_wav(f) for f in group) else audio.load_flac
+            for wf, sr, _ in load(group):
                 yield wf, sr
     else:
         for f in a.songs:
-            yield flac.load_float(f)
+            yield _load_float(f, flac)
 
 
 def _same_rate_queue(a, flac, residual=False, stems=False):
@@ -282,7 +321,12 @@ def _same_rate_queue(a, flac, residual=False, stems=False):
     Returns (the queue, that rate)."""
     if a.decode == 'device':
         with open(a.songs[0], 'rb') as f0:
-            sr0 = flac.read_streaminfo(f0.read())[0]                # the first file's header, on the host
+            head = f0.read()
+        if head[:4] == b'RIFF':
+            from . import wav
+            sr0 = wav.read_header(head)[0]
+        else:
+            sr0 = flac.read_streaminfo(head)[0]                     # the first file's header, on the host
 
         def load():
             for f, (wf, sr) in zip(a.songs, _load_songs(a, flac)):
@@ -292,12 +336,12 @@ def _same_rate_queue(a, flac, residual=False, stems=False):
                 yield wf, sr                        # a pair: audio.resample at equal rates, the downmix alone
         return iter_transcribe_songs(load(), Hyperparams(N=2048, sr=sr0), iters=a.iters, weights_dir=a.weights,
                                      guess=a.guess, slots=a.slots, residual=residual, stems=stems, groups=CLI_GROUPS), sr0
-    first = flac.load_float(a.songs[0])
+    first = _load_float(a.songs[0], flac)
     sr0 = first[1]
 
     def load():
         for k, f in enumerate(a.songs):
-            wf, sr = first if k == 0 else flac.load_float(f)
+            wf, sr = first if k == 0 else _load_float(f, flac)
             if sr != sr0:
                 raise SystemExit('%s: sample rate %d differs from the first file\'s %d; one queue runs at one rate'
                                  % (f, sr, sr0))
@@ -330,6 +374,7 @@ def main(argv=None):
                          'subtractions took out of the song, 24-bit FLAC at the rate the model runs at')
     ap.add_argument('--flac', default='host', choices=FLAC_WRITERS, help=_FLAC_HELP)
     ap.add_argument('--decode', default='host', choices=DECODERS, help=_DECODE_HELP)
+    ap.add_argument('--format', default='flac', choices=FORMATS, help=_FORMAT_HELP)
     a = ap.parse_args(argv)
     if a.residual is not None and a.traversal != 'song':
         raise SystemExit('--residual needs --traversal song (independent windows have no song-level residual)')
@@ -337,9 +382,9 @@ def main(argv=None):
         raise SystemExit('--stems-dir needs --traversal song (independent windows have no song-level stems)')
     if a.decode == 'device':
         from . import audio
-        wf, sr, _ = audio.load_flac(a.infile)
+        wf, sr, _ = (audio.load_audio if _is_wav(a.infile) else audio.load_flac)(a.infile)
     else:
-        wf, sr = flac.load_float(a.infile)
+        wf, sr = _load_float(a.infile, flac)
     if a.sr is None:                             # the model at the file's rate
         if a.decode == 'device':
             wf = audio.resample(wf, sr, sr)      # [n, channels] -> mono on the device; mono passes through
@@ -364,7 +409,7 @@ def main(argv=None):
         os.makedirs(a.stems_dir, exist_ok=True)
     write_song_audio(model_sr, residual=got[2] if a.residual is not None else None, residual_path=a.residual,
                      stems=got[-1] if a.stems_dir is not None else None, stems_dir=a.stems_dir,
-                     name=os.path.splitext(os.path.basename(a.infile))[0], flac=a.flac)
+                     name=os.path.splitext(os.path.basename(a.infile))[0], flac=a.flac, format=a.format)
 
 
 if __name__ == '__main__':

@@ -218,7 +218,45 @@ int amt_flac_decode_ragged(const unsigned char *data, long long data_bytes, cons
                            unsigned char *md5, void *stream);
 
 /* ------------------------------------------------------------------------ *
- * Spectral subtraction  (replaces audio_complete.subtract, util_audio.py:221-259)
+ * WAV sample data  (replaces, for WAV files, the librosa.load of audio_from_file, util_audio.py:962-964, and the
+ * librosa.output.write_wav of audio_complete.save(flac=False), util_audio.py:526-527)
+ *
+ * The host walks the RIFF chunks and writes the file headers (amt_saga/wav.py); the device turns the data chunk into
+ * floats and floats into a data chunk.  Reading -- integer PCM, container c = 1 .. 4 bytes little-endian (c = 1
+ * unsigned, u - 128), valid bits b = 1 .. 8 c, MSB-justified: q = container >> (8 c - b), wave = float32(q) 2^-(b-1)
+ * (nearest even), pcm = q; float32: the bits as they are; float64: rounded to float32, nearest even.  Writing -- mono,
+ * fmt 0 = PCM-16, 1 = PCM-24: q = clip(rint(y 2^(b-1)), -2^(b-1), 2^(b-1) - 1) on the float32 product, NaN -> 0 (the
+ * FLAC encoder's rule); 2 = float32, the bits as they are.  DESIGN.md 18.
+ * ------------------------------------------------------------------------ */
+/* audio_from_file (util_audio.py:962-964) for the data chunks of n WAV files in ONE launch.  data [data_bytes]: the
+ * files' bytes.  stream_meta int64 [n][8]: byte offset in data of the first sample (any value modulo 4), frames,
+ * channels (1 .. 8), kind (0 integer, 1 float), container bytes, valid bits, first output value, reserved.  max_frames
+ * (host) sizes the grid.  out [out_values] float32, file i at its first output value, interleaved [frames][channels];
+ * out_pcm: the int32 q in the same layout, or NULL (rows of float kind write none).  Tables and buffers: device.
+ * No byte at or past data_bytes is read and nothing at or past out_values is written, whatever the table holds: a row
+ * whose geometry is none of the above, or whose bytes or values would leave either buffer, is left unwritten -- a bad
+ * table costs output, never a fault.  AMT_E_INVALID: a NULL pointer (out_pcm excepted), n outside 1 .. 65535, a
+ * negative size.  All checks return before any HIP call.  Integer code without packed-FP32 instructions: any stream. */
+int amt_pcm_unpack_ragged(const unsigned char *data, long long data_bytes, const long long *stream_meta, int n,
+                          long long max_frames, float *out, int *out_pcm, long long out_values, void *stream);
+/* librosa.output.write_wav(norm=True) (util_audio.py:526-527), its inf-norm: peak_out[i] = max |y| over signal i =
+ * wave[base[i] .. + len[i]) (conventions of amt_flac_encode_ragged), NaNs skipped; 0 for an empty or all-NaN signal.
+ * A maximum: exact in any order.  peak_out float32 [n], device; zeroed by the call on `stream`.  AMT_E_INVALID: a NULL
+ * pointer, n outside 1 .. 65535, max_len < 0. */
+int amt_pcm_peak_ragged(const float *wave, const long long *base, const long long *len, int n, long long max_len,
+                        float *peak_out, void *stream);
+/* librosa.output.write_wav (util_audio.py:526-527) without the header, for n signals in ONE launch: signal i =
+ * wave[base[i] .. + len[i]) (floats; base any offset the caller owns, a len above max_len is cut to max_len) becomes
+ * the data bytes of `fmt` (0 PCM-16, 1 PCM-24, 2 float32) at out[out_base[i] ..).  peak: NULL, or float32 [n] -- each
+ * sample is first y / peak[i], an IEEE float32 division; a peak of 0 or a non-finite one leaves the signal as it is.
+ * base, len, peak, out_base: device.  A signal whose bytes would leave out[0 .. out_bytes) is left unwritten.
+ * AMT_E_INVALID: a NULL pointer (peak excepted), n outside 1 .. 65535, a negative size, fmt outside 0 .. 2. */
+int amt_pcm_pack_ragged(const float *wave, const long long *base, const long long *len, int n, long long max_len,
+                        int fmt, const float *peak, unsigned char *out, const long long *out_base, long long out_bytes,
+                        void *stream);
+
+/* ------------------------------------------------------------------------ *
+ * Spectral subtraction (replaces audio_complete.subtract, util_audio.py:221-259)
  * ------------------------------------------------------------------------ */
 typedef struct amt_subtract_args {
     float       *resid;          /* [B][T][ldf] in place (self.mag)                          */
