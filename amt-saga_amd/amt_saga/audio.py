@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, flac as _flac, wav as _wav
 from .device import empty, ptr, require_gpu, stream_ptr, to_dev, zeros
 
 _PLANS = {}
@@ -904,13 +904,15 @@ class audio_complete:
         if not flac:
             return save_wav(to_dev(np.asarray(self.wf, dtype=np.float32).reshape(-1)), filename, self.sr,
                             fmt='float32', norm=True)
-        from . import flac as _flac
         _flac.save_float(np.asarray(self.wf), filename, sr=self.sr, bps=24)
 
 
 # ======================================================================================
 # Sample-rate conversion (the `sr=` of librosa.load, util_audio.py:962-964)
 # ======================================================================================
+MAX_SIGNALS = 65535                # signals (or files) one ragged call takes: the launchers' grid limit
+
+
 def _check_rates(sr_in, sr_out):
     if int(sr_in) != sr_in or int(sr_out) != sr_out or int(sr_in) <= 0 or int(sr_out) <= 0:
         raise ValueError('resample: sample rates must be positive integers. Got: %r -> %r' % (sr_in, sr_out))
@@ -937,7 +939,7 @@ class Resampler:
     R = max(L, M).  Channels ([n, channels], interleaved) are averaged by the kernel, as librosa.load's mono=True does.
     Every argument error is a ValueError raised before the library or the GPU is touched; the coefficient table is
     built (amt_resampler_create) at the first call."""
-    Z, R_MAX, MAX_CHANNELS, MAX_SIGNALS = 32, 2048, 8, 65535
+    Z, R_MAX, MAX_CHANNELS, MAX_SIGNALS = 32, 2048, 8, MAX_SIGNALS
 
     def __init__(self, sr_in, sr_out):
         self.sr_in, self.sr_out = _check_rates(sr_in, sr_out)
@@ -1030,11 +1032,67 @@ def resample(wf, sr_in, sr_out):
 
 
 # ======================================================================================
-# FLAC encoding on the device (the soundfile.write of audio_to_flac, util_audio.py:966-968)
+# File codecs: the steps the FLAC and the WAV paths share
 # ======================================================================================
-def _flac_signals(waves):
-    """The 1-d float32 device signals of `waves`: a tensor [n] or [G, n], or a list of those.  Rows of a 2-d tensor are
-    taken as views; only a signal whose samples are not adjacent in memory is copied."""
+def _read_files(paths):
+    """(single, datas): the files at `paths` (one path or a list) read whole, and whether it was one path."""
+    single = isinstance(paths, (str, bytes, os.PathLike))
+    datas = []
+    for p in ([paths] if single else list(paths)):
+        with open(p, 'rb') as f:
+            datas.append(f.read())
+    return single, datas
+
+
+def _write_files(files, paths):
+    """files[i] written to paths[i] (one path or a list), one write per file."""
+    paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
+    if len(paths) != len(files):
+        raise ValueError('Invalid Input shape. Expected: one path per signal (%d) . Got: %d' % (len(files), len(paths)))
+    for data, path in zip(files, paths):
+        with open(path, 'wb') as f:
+            f.write(data)
+
+
+def _check_files(datas, limit=None):
+    """The argument check of both decoders: `datas` is a non-empty list of bytes, of at most `limit` files."""
+    if isinstance(datas, (bytes, bytearray, memoryview)) or not isinstance(datas, (list, tuple)):
+        raise ValueError('Invalid Input shape. Expected: a list of bytes . Got: %s' % type(datas).__name__)
+    if not datas:
+        raise ValueError('Invalid Input shape. Expected: at least one file . Got: an empty list')
+    if limit is not None and len(datas) > limit:
+        raise ValueError('Invalid Input shape. Expected: at most %d files a call . Got: %d' % (limit, len(datas)))
+    for d in datas:
+        if not isinstance(d, (bytes, bytearray)):
+            raise ValueError('Invalid Input shape. Expected: a list of bytes . Got: %s in it' % type(d).__name__)
+
+
+def _upload_files(datas):
+    """The files' bytes back to back in one uint8 tensor on the current device: one upload."""
+    return torch.frombuffer(bytearray(b''.join(datas)), dtype=torch.uint8).to(
+        torch.device('cuda', torch.cuda.current_device()))
+
+
+def _file_view(buf, base, frames, channels):
+    """One decoded file in the packed output `buf`: [frames] for mono, else [frames, channels]."""
+    v = buf[base:base + frames * channels]
+    return v if channels == 1 else v.view(frames, channels)
+
+
+def _ragged_layout(sigs):
+    """The input layout of amt_flac_encode_ragged, amt_pcm_peak_ragged and amt_pcm_pack_ragged: 1-d float32 signals
+    that lie anywhere in one address space, named by one pointer and two tables.  Returns (anchor, base, lens):
+    anchor = the lowest data_ptr of the signals that have samples, base[i] = signal i's offset from it in floats (0 for
+    an empty signal, whose pointer means nothing), lens[i] = its length.  No signal has samples: anchor is None."""
+    lens = [int(s.numel()) for s in sigs]
+    live = [s.data_ptr() for s, l in zip(sigs, lens) if l]
+    anchor = min(live) if live else None
+    return anchor, [(s.data_ptr() - anchor) // 4 if l else 0 for s, l in zip(sigs, lens)], lens
+
+
+def _device_signals(waves):
+    """The signal check of both encoders: the 1-d float32 device signals of `waves`, a tensor [n] or [G, n] or a list of
+    those.  Rows of a 2-d tensor are taken as views; only a signal whose samples are not adjacent in memory is copied."""
     items = [waves] if isinstance(waves, torch.Tensor) else list(waves)
     sigs = []
     for w in items:
@@ -1050,23 +1108,23 @@ def _flac_signals(waves):
     return sigs
 
 
+# ======================================================================================
+# FLAC encoding on the device (the soundfile.write of audio_to_flac, util_audio.py:966-968)
+# ======================================================================================
 def flac_encode_streams(waves, bps=24, blocksize=4096, first_frame=0):
-    """amt_flac_encode_ragged for the signals of `waves` (see _flac_signals), one call on the current stream: returns
+    """amt_flac_encode_ragged for the signals of `waves` (see _device_signals), one call on the current stream: returns
     (out, stream_off, frame_minmax, md5, frame_bytes) -- out a uint8 device buffer in which signal i's frames lie back
     to back at [stream_off[i], stream_off[i + 1]); stream_off int64 [n + 1], frame_minmax int32 [n, 2], md5 uint8
     [n, 16], frame_bytes int64 [n, frames of the longest]: all device tensors, nothing is synchronised."""
     lib = _lib.load()
-    sigs = _flac_signals(waves)
+    sigs = _device_signals(waves)
     bound = int(lib.amt_flac_frame_bound(int(blocksize), int(bps)))
     if bound < 0 or int(first_frame) < 0:
         _lib.check(_lib.AMT_E_INVALID)
     n = len(sigs)
-    lens = [int(s.numel()) for s in sigs]
+    anchor, base, lens = _ragged_layout(sigs)
     max_len = max(lens)
     frames = [-(-l // int(blocksize)) for l in lens]
-    live = [s.data_ptr() for s, l in zip(sigs, lens) if l]
-    anchor = min(live) if live else 0
-    base = [(s.data_ptr() - anchor) // 4 if l else 0 for s, l in zip(sigs, lens)]
     dev = sigs[0].device
     meta = torch.tensor([base, lens], dtype=torch.int64).to(dev)
     scratch = torch.empty((max(int(lib.amt_flac_scratch_bytes(n, max_len, int(blocksize), int(bps))), 8),),
@@ -1076,12 +1134,12 @@ def flac_encode_streams(waves, bps=24, blocksize=4096, first_frame=0):
     stream_off = torch.empty((n + 1,), dtype=torch.int64, device=dev)
     minmax = torch.empty((n, 2), dtype=torch.int32, device=dev)
     md5 = torch.empty((n, 16), dtype=torch.uint8, device=dev)
-    # (a host-side 8 stands where a buffer would be empty: the ABI refuses NULL)
+    # (a host-side 8 stands where a buffer would be empty, the scratch where no signal has samples: the ABI refuses NULL)
     fb = frame_bytes if frame_bytes.numel() else torch.empty((1,), dtype=torch.int64, device=dev)
     _lib.check(lib.amt_flac_encode_ragged(
-        C.c_void_p(anchor if live else scratch.data_ptr()), ptr(meta[0]), ptr(meta[1]), n, max_len, int(blocksize),
-        int(bps), int(first_frame), ptr(scratch), scratch.numel(), ptr(out), out.numel(), ptr(fb), ptr(stream_off),
-        ptr(minmax), ptr(md5), stream_ptr()))
+        C.c_void_p(scratch.data_ptr() if anchor is None else anchor), ptr(meta[0]), ptr(meta[1]), n, max_len,
+        int(blocksize), int(bps), int(first_frame), ptr(scratch), scratch.numel(), ptr(out), out.numel(), ptr(fb),
+        ptr(stream_off), ptr(minmax), ptr(md5), stream_ptr()))
     # the signals and the scratch stay referenced until the call is enqueued; torch's allocator keeps a freed block
     # for the stream that used it, so work enqueued later on this stream cannot overtake the encoder
     return out, stream_off, minmax, md5, frame_bytes
@@ -1099,7 +1157,7 @@ def flac_encode(waves, sr, bps=24, blocksize=4096):
     tensors; a [G, n] tensor counts as G signals, its rows are not copied -- as the bytes of a complete mono FLAC file
     (fLaC, STREAMINFO, frames).  One encode call for the whole list, on the current stream, so it is ordered after
     whatever produced the tensors; the frames come back in one device-to-host copy."""
-    sigs = _flac_signals(waves)
+    sigs = _device_signals(waves)
     out, stream_off, minmax, md5, _ = flac_encode_streams(sigs, bps=bps, blocksize=blocksize)
     off = stream_off.cpu().tolist()
     minmax, md5 = minmax.cpu().tolist(), md5.cpu().numpy()
@@ -1112,13 +1170,7 @@ def flac_encode(waves, sr, bps=24, blocksize=4096):
 
 def save_flac(waves, paths, sr, bps=24):
     """flac_encode(waves, sr, bps) written to `paths`, one file per signal, one write per file."""
-    files = flac_encode(waves, sr, bps=bps)
-    paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
-    if len(paths) != len(files):
-        raise ValueError('Invalid Input shape. Expected: one path per signal (%d) . Got: %d' % (len(files), len(paths)))
-    for data, path in zip(files, paths):
-        with open(path, 'wb') as f:
-            f.write(data)
+    _write_files(flac_encode(waves, sr, bps=bps), paths)
 
 
 # ======================================================================================
@@ -1137,18 +1189,12 @@ def _flac_tables(datas, verify):
     """The host's O(frames) share of flac_decode, no GPU involved: argument checks, STREAMINFO and the candidate
     headers of every file.  Returns (infos, stream_meta int64 [n, 9], cand_meta int64 [n_cand, 7], md5 uint8 [n, 16],
     slot_ints, out_values)."""
-    from . import flac as _flac
     if not isinstance(verify, (bool, str)) or verify not in FLAC_VERIFY:
         raise ValueError("Requested attribute does not exist: verify must be True, 'crc' or False")
-    if isinstance(datas, (bytes, bytearray, memoryview)) or not isinstance(datas, (list, tuple)):
-        raise ValueError('Invalid Input shape. Expected: a list of bytes . Got: %s' % type(datas).__name__)
-    if not datas:
-        raise ValueError('Invalid Input shape. Expected: at least one file . Got: an empty list')
+    _check_files(datas)                                             # (amt_flac_decode_ragged has its own limit on files)
     infos, sm, cm, md5s = [], [], [], []
     off = slot = out = 0
     for i, d in enumerate(datas):
-        if not isinstance(d, (bytes, bytearray)):
-            raise ValueError('Invalid Input shape. Expected: a list of bytes . Got: %s in it' % type(d).__name__)
         sr, ch, bps, total, md5, first = _flac.read_streaminfo(d)
         if bps > 24:
             raise ValueError('FLAC file %d: %d bits per sample; above 24 is not supported (float32 is exact to 24)'
@@ -1183,8 +1229,8 @@ def flac_decode_streams(datas, verify=True, pcm=False):
     infos, sm, cm, md5, slot_ints, out_values = _flac_tables(datas, verify)
     lib = _lib.load()
     n, n_cand = len(infos), len(cm)
-    dev = torch.device('cuda', torch.cuda.current_device())
-    data = torch.frombuffer(bytearray(b''.join(datas)), dtype=torch.uint8).to(dev)
+    data = _upload_files(datas)
+    dev = data.device
     tab = torch.from_numpy(np.concatenate([sm.reshape(-1), cm.reshape(-1)])).to(dev)
     sm_d, cm_d = tab[:sm.size], tab[sm.size:]
     md5_in = torch.from_numpy(md5.copy()).to(dev)
@@ -1246,22 +1292,14 @@ def flac_decode(datas, verify=True, pcm=False):
                     e = int(r['cand_out'][int(hit[0]), 1].item())
                     msg += ' (%s)' % _FLAC_FRAME_ERRORS.get(e, 'error %d' % e)
             raise ValueError(msg + (' (file %d of the call)' % i if len(status) > 1 else ''))
-        base = m[6]
-
-        def view(t):
-            v = t[base:base + total * ch]
-            return v if ch == 1 else v.view(total, ch)
-        res.append((view(r['out']), sr, bps) + ((view(r['pcm']),) if pcm else ()))
+        res.append((_file_view(r['out'], m[6], total, ch), sr, bps)
+                   + ((_file_view(r['pcm'], m[6], total, ch),) if pcm else ()))
     return res
 
 
 def load_flac(paths, verify=True, pcm=False):
     """flac_decode of the files at `paths` (one path or a list), read whole and decoded in one call."""
-    single = isinstance(paths, (str, bytes, os.PathLike))
-    datas = []
-    for p in ([paths] if single else list(paths)):
-        with open(p, 'rb') as f:
-            datas.append(f.read())
+    single, datas = _read_files(paths)
     res = flac_decode(datas, verify=verify, pcm=pcm)
     return res[0] if single else res
 
@@ -1278,19 +1316,10 @@ def _wav_tables(datas):
     """The host's O(chunks) share of wav_decode, no GPU involved: argument checks and the header of every file.
     Returns (infos [(sr, channels, kind, bits, frames)], stream_meta int64 [n, 8], out_values).  Every file's output
     begins on a 16-byte boundary."""
-    from . import wav as _wav
-    if isinstance(datas, (bytes, bytearray, memoryview)) or not isinstance(datas, (list, tuple)):
-        raise ValueError('Invalid Input shape. Expected: a list of bytes . Got: %s' % type(datas).__name__)
-    if not datas:
-        raise ValueError('Invalid Input shape. Expected: at least one file . Got: an empty list')
-    if len(datas) > Resampler.MAX_SIGNALS:
-        raise ValueError('Invalid Input shape. Expected: at most %d files a call . Got: %d'
-                         % (Resampler.MAX_SIGNALS, len(datas)))
+    _check_files(datas, MAX_SIGNALS)
     infos, sm = [], []
     off = out = 0
     for d in datas:
-        if not isinstance(d, (bytes, bytearray)):
-            raise ValueError('Invalid Input shape. Expected: a list of bytes . Got: %s in it' % type(d).__name__)
         sr, ch, kind, bits, c, first, frames = _wav.read_header(d)
         sm.append([off + first, frames, ch, PCM_KINDS[kind], c, bits, out, 0])
         infos.append((sr, ch, kind, bits, frames))
@@ -1310,8 +1339,8 @@ def wav_decode(datas, pcm=False):
     if pcm and any(kind == 'float' for _, _, kind, _, _ in infos):
         _lib.check(_lib.AMT_E_INVALID)
     lib = _lib.load()
-    dev = torch.device('cuda', torch.cuda.current_device())
-    data = torch.frombuffer(bytearray(b''.join(datas)), dtype=torch.uint8).to(dev)
+    data = _upload_files(datas)
+    dev = data.device
     sm_d = torch.from_numpy(sm).to(dev)
     out = torch.empty((out_values,), dtype=torch.float32, device=dev)
     out_i = torch.empty((out_values,), dtype=torch.int32, device=dev) if pcm else None
@@ -1320,20 +1349,9 @@ def wav_decode(datas, pcm=False):
                                          out_values, stream_ptr()))
     res = []
     for (sr, ch, kind, bits, frames), row in zip(infos, sm.tolist()):
-        def view(t, base=row[6], frames=frames, ch=ch):
-            v = t[base:base + frames * ch]
-            return v if ch == 1 else v.view(frames, ch)
-        res.append((view(out), sr, bits) + ((view(out_i),) if pcm else ()))
+        res.append((_file_view(out, row[6], frames, ch), sr, bits)
+                   + ((_file_view(out_i, row[6], frames, ch),) if pcm else ()))
     return res
-
-
-def _read_files(paths):
-    single = isinstance(paths, (str, bytes, os.PathLike))
-    datas = []
-    for p in ([paths] if single else list(paths)):
-        with open(p, 'rb') as f:
-            datas.append(f.read())
-    return single, datas
 
 
 def load_wav(paths, pcm=False):
@@ -1364,22 +1382,17 @@ def wav_encode(waves, sr, fmt='pcm24', norm=False):
     file of `fmt` ('pcm16', 'pcm24' or 'float32'), identical to amt_saga.wav.encode on the same float32 samples.
     norm=True divides every signal by its own peak first (amt_pcm_peak_ragged; write_wav's norm=True).  One pack call
     for the whole list on the current stream, one device-to-host copy."""
-    from . import wav as _wav
     if fmt not in PCM_FORMATS:
         raise ValueError('Requested attribute does not exist: fmt must be one of %s' % (_wav.FORMATS,))
-    sigs = _flac_signals(waves)
-    if len(sigs) > Resampler.MAX_SIGNALS:
-        raise ValueError('Invalid Input shape. Expected: at most %d signals a call . Got: %d'
-                         % (Resampler.MAX_SIGNALS, len(sigs)))
-    lens = [int(s.numel()) for s in sigs]
+    sigs = _device_signals(waves)
+    if len(sigs) > MAX_SIGNALS:
+        raise ValueError('Invalid Input shape. Expected: at most %d signals a call . Got: %d' % (MAX_SIGNALS, len(sigs)))
+    anchor, base, lens = _ragged_layout(sigs)
     heads = [_wav.header(l, sr, fmt) for l in lens]                  # (refuses a bad rate or an oversized signal)
     lib = _lib.load()
     c = _wav.FORMAT_BYTES[fmt]
-    live = [s.data_ptr() for s, l in zip(sigs, lens) if l]
-    if not live:
+    if anchor is None:                                               # nothing to pack: every file is its header
         return heads
-    anchor = min(live)
-    base = [(s.data_ptr() - anchor) // 4 if l else 0 for s, l in zip(sigs, lens)]
     out_base, total = [], 0
     for l in lens:
         out_base.append(total)
@@ -1401,10 +1414,4 @@ def wav_encode(waves, sr, fmt='pcm24', norm=False):
 
 def save_wav(waves, paths, sr, fmt='pcm24', norm=False):
     """wav_encode(waves, sr, fmt, norm) written to `paths`, one file per signal, one write per file."""
-    files = wav_encode(waves, sr, fmt=fmt, norm=norm)
-    paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
-    if len(paths) != len(files):
-        raise ValueError('Invalid Input shape. Expected: one path per signal (%d) . Got: %d' % (len(files), len(paths)))
-    for data, path in zip(files, paths):
-        with open(path, 'wb') as f:
-            f.write(data)
+    _write_files(wav_encode(waves, sr, fmt=fmt, norm=norm), paths)

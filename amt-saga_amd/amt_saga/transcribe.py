@@ -22,9 +22,9 @@ provide for the inference direction:
     --flac {host,device}: the writer of those files -- host (default): amt_saga.flac's VERBATIM writer; device: the HIP
     encoder (audio.save_flac), a song's residual and stems in one call, compressed.
     --decode {host,device}: the reader of the input files -- host (default): amt_saga.flac's reader; device: the HIP
-    decoder (audio.load_flac), --slots files per decode call with --songs, the samples never on the host.
-    A file that begins with RIFF is read as WAV, by amt_saga.wav's reader (host) or audio.load_audio (device: the FLAC and
-    the WAV files of a group in one decode call each); every other file is read as FLAC.
+    decoder (audio.load_audio), --slots files per decode call with --songs, the samples never on the host.
+    A file that begins with RIFF is read as WAV, by amt_saga.wav's reader (host) or by audio.load_audio (device: the FLAC
+    and the WAV files of a group in one decode call each); every other file is read as FLAC.
     --format {flac,wav} (both modes): the container of --residual / --residual-dir / --stems-dir -- flac (default), or
     wav: PCM-24 WAV through audio.save_wav, a song's residual and stems in one call, named .residual.wav / .group<g>.wav.
 
@@ -32,13 +32,15 @@ Weights: a directory with {timing_start,timing_end,pitch,instrument,velocity}.np
 naming of amt_saga/rdcnn.py; without it the heads carry their seeded synthetic weights (the
 reference ships no checkpoint), which exercises the whole path but transcribes nothing.
 """
+import argparse
+import itertools
 import os
 import sys
 
 import numpy as np
 import torch
 
-from . import events as ev
+from . import audio, events as ev, flac as host_flac, wav as host_wav
 from .hyperparams import Hyperparams
 from .loop import TranscriptionLoop
 
@@ -99,8 +101,7 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
     if loop is None:
         loop = _make_loop(p, iters, heads, groups, weights_dir, guess)
     if sr is not None:
-        from .audio import resample
-        wf = resample(wf, sr, p.sr)                                # 1-d float32, on the device; sr == p.sr: a downmix
+        wf = audio.resample(wf, sr, p.sr)                              # 1-d float32, on the device; sr == p.sr: a downmix
     on_dev = isinstance(wf, torch.Tensor) and wf.is_cuda
     if traversal == 'song':
         wf32 = wf if on_dev else np.ascontiguousarray(wf, dtype=np.float32)      # (run_songs takes either)
@@ -142,8 +143,7 @@ def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', '
     def feed():
         for i, wf in enumerate(wfs):
             if isinstance(wf, tuple):
-                from .audio import resample
-                w = resample(wf[0], wf[1], p.sr)
+                w = audio.resample(wf[0], wf[1], p.sr)
             else:
                 w = np.ascontiguousarray(wf, dtype=np.float32).reshape(-1)
             lens[i] = len(w)
@@ -192,21 +192,52 @@ _DECODE_HELP = ("reader of the input files: 'host' = the pure-Python reader (the
                 "down in float32 on the device and in float64 on the host, so its samples may differ in the last bit")
 
 
+def _shared_options(ap, sr_help, **stems_dir):
+    """The options both command-line modes have; the help of --sr and --stems-dir is the mode's own."""
+    ap.add_argument('--weights', default=None)
+    ap.add_argument('--iters', type=int, default=5)
+    ap.add_argument('--guess', default='bank', choices=('bank', 'render'))
+    ap.add_argument('--sr', type=int, default=None, help=sr_help)
+    ap.add_argument('--stems-dir', default=None, **stems_dir)
+    ap.add_argument('--flac', default='host', choices=FLAC_WRITERS, help=_FLAC_HELP)
+    ap.add_argument('--decode', default='host', choices=DECODERS, help=_DECODE_HELP)
+    ap.add_argument('--format', default='flac', choices=FORMATS, help=_FORMAT_HELP)
+
+
 def _is_wav(path):
     """True for a file that begins with RIFF; every other file, and a missing one, is left to the FLAC path."""
-    from . import wav
     try:
-        return wav.is_wav(path)
+        return host_wav.is_wav(path)
     except OSError:
         return False
 
 
-def _load_float(path, flac):
+def _load_float(path):
     """(float64 waveform, rate) of one file on the host: amt_saga.wav's reader for a RIFF file, else the FLAC reader."""
-    if _is_wav(path):
-        from . import wav
-        return wav.load_float(path)
-    return flac.load_float(path)
+    return (host_wav if _is_wav(path) else host_flac).load_float(path)
+
+
+def _read_inputs(paths, decode, group=1):
+    """(waveform, rate) of every file of `paths` in order, lazily.  decode='host': read one by one, float64 arrays.
+    decode='device': audio.load_audio calls of `group` files each, made as the consumer pulls them, the waveforms device
+    tensors -- the bytes, the scratch and the samples on the device are those of one such group and of the songs in
+    flight, not of the collection."""
+    if decode == 'device':
+        step = max(1, group)
+        for k in range(0, len(paths), step):
+            for wf, sr, _ in audio.load_audio(list(paths[k:k + step])):
+                yield wf, sr
+    else:
+        for f in paths:
+            yield _load_float(f)
+
+
+def _mono(wf, sr, decode):
+    """A file's waveform [n] or [n, channels] as one channel at its own rate `sr`: the float64 mean of the channels on
+    the host, audio.resample at equal rates (a float32 mean) on the device; a mono waveform passes through."""
+    if decode == 'device':
+        return audio.resample(wf, sr, sr)
+    return wf.mean(axis=1) if wf.ndim > 1 else wf
 
 
 def write_song_audio(rate, residual=None, residual_path=None, stems=None, stems_dir=None, name=None, flac='host',
@@ -233,42 +264,40 @@ def write_song_audio(rate, residual=None, residual_path=None, stems=None, stems_
     if not waves:
         return
     if format == 'wav':
-        from . import audio
         audio.save_wav(waves, paths, rate, fmt='pcm24')
     elif flac == 'device':
-        from . import audio
         audio.save_flac(waves, paths, rate)
     else:
-        from . import flac as host
         for w, path in zip(waves, paths):
-            host.save_float(np.ascontiguousarray(w.cpu().numpy()), path, sr=rate)
+            host_flac.save_float(np.ascontiguousarray(w.cpu().numpy()), path, sr=rate)
     for line in notes:
         print(line)
+
+
+def _same_rate(paths, pairs, rate, decode):
+    """The queue's input without --sr: every (waveform, rate) of `pairs` as one channel, a file of another rate than
+    `rate` refused."""
+    for f, (wf, sr) in zip(paths, pairs):
+        if sr != rate:
+            raise SystemExit('%s: sample rate %d differs from the first file\'s %d; one queue runs at one rate'
+                             % (f, sr, rate))
+        wf = _mono(wf, sr, decode)
+        yield (wf, sr) if decode == 'device' else wf        # (the queue takes a device tensor as a pair; equal rates pass)
 
 
 def main_songs(argv):
     """The many-files mode: --songs a.flac b.flac ... --out-dir DIR [--slots N]; one .mid per input, written as its song
     finishes."""
-    import argparse
-    from . import flac
     ap = argparse.ArgumentParser(description='song queue: one MIDI file per input file')
     ap.add_argument('--songs', nargs='+', required=True)
     ap.add_argument('--out-dir', required=True)
     ap.add_argument('--slots', type=int, default=8)
-    ap.add_argument('--weights', default=None)
-    ap.add_argument('--iters', type=int, default=5)
-    ap.add_argument('--guess', default='bank', choices=('bank', 'render'))
-    ap.add_argument('--sr', type=int, default=None,
-                    help='rate the model runs at; every file is resampled to it from its own rate (mixed rates allowed)')
     ap.add_argument('--residual-dir', default=None,
                     help='write <stem>.residual.flac per song as it finishes: what the walk left after every subtraction, '
                          '24-bit FLAC at the rate the model runs at (with --sr, the resampled rate)')
-    ap.add_argument('--stems-dir', default=None,
+    _shared_options(ap, 'rate the model runs at; every file is resampled to it from its own rate (mixed rates allowed)',
                     help='write <stem>.group<g>.flac per song and instrument group as it finishes: what the subtractions '
                          'took out of the song, 24-bit FLAC at the rate the model runs at')
-    ap.add_argument('--flac', default='host', choices=FLAC_WRITERS, help=_FLAC_HELP)
-    ap.add_argument('--decode', default='host', choices=DECODERS, help=_DECODE_HELP)
-    ap.add_argument('--format', default='flac', choices=FORMATS, help=_FORMAT_HELP)
     a = ap.parse_args(argv)
     os.makedirs(a.out_dir, exist_ok=True)
     keep, keep_stems = a.residual_dir is not None, a.stems_dir is not None
@@ -278,15 +307,22 @@ def main_songs(argv):
     stems = [os.path.splitext(os.path.basename(f))[0] for f in a.songs]
     if len(set(stems)) != len(stems):
         raise SystemExit('--songs: two inputs would write the same .mid (equal file names)')
-    if a.sr is not None:
+    wfs = _read_inputs(a.songs, a.decode, a.slots)
+    if a.sr is not None:                         # every file resampled to the model's rate as the queue pulls it
         if a.sr <= 0:
             raise SystemExit('--sr: the rate must be positive')
-        queue = iter_transcribe_songs(_load_songs(a, flac), Hyperparams(N=2048, sr=a.sr), iters=a.iters,
-                                      weights_dir=a.weights, guess=a.guess, slots=a.slots, residual=keep,
-                                      stems=keep_stems, groups=CLI_GROUPS)
         rate = a.sr
-    else:
-        queue, rate = _same_rate_queue(a, flac, keep, keep_stems)
+    else:                                        # the model at the first file's rate, every other file held to it
+        if a.decode == 'device':                 # the first file's header, on the host
+            with open(a.songs[0], 'rb') as f0:
+                head = f0.read()
+            rate = (host_wav.read_header(head) if head[:4] == b'RIFF' else host_flac.read_streaminfo(head))[0]
+        else:                                    # the first file itself, loaded once
+            first = next(wfs)
+            rate, wfs = first[1], itertools.chain([first], wfs)
+        wfs = _same_rate(a.songs, wfs, rate, a.decode)
+    queue = iter_transcribe_songs(wfs, Hyperparams(N=2048, sr=rate), iters=a.iters, weights_dir=a.weights, guess=a.guess,
+                                  slots=a.slots, residual=keep, stems=keep_stems, groups=CLI_GROUPS)
     for item in queue:
         i, notes = item[0], item[1]
         out = os.path.join(a.out_dir, stems[i] + '.mid')
@@ -298,99 +334,29 @@ def main_songs(argv):
                          format=a.format)
 
 
-def _load_songs(a, flac):
-    """(waveform, rate) of every --songs file in order: read one by one on the host, or -- with --decode device -- in
-    decode calls of --slots files each, as the queue pulls them, the waveforms device tensors: the bytes, the scratch
-    and the samples on the device are those of one such group and of the songs in flight, not of the collection."""
-    if a.decode == 'device':
-        from . import audio
-        step = max(1, a.slots)
-        for k in range(0, len(a.songs), step):
-            group = list(a.songs[k:k + step])
-            # (a group without a RIFF file keeps the FLAC call it always made)
-            load = audio.load_audio if any(_is_wav(f) for f in group) else audio.load_flac
-            for wf, sr, _ in load(group):
-                yield wf, sr
-    else:
-        for f in a.songs:
-            yield _load_float(f, flac)
-
-
-def _same_rate_queue(a, flac, residual=False, stems=False):
-    """--songs without --sr: the model at the first file's rate, every other file refused unless it has that rate.
-    Returns (the queue, that rate)."""
-    if a.decode == 'device':
-        with open(a.songs[0], 'rb') as f0:
-            head = f0.read()
-        if head[:4] == b'RIFF':
-            from . import wav
-            sr0 = wav.read_header(head)[0]
-        else:
-            sr0 = flac.read_streaminfo(head)[0]                     # the first file's header, on the host
-
-        def load():
-            for f, (wf, sr) in zip(a.songs, _load_songs(a, flac)):
-                if sr != sr0:
-                    raise SystemExit('%s: sample rate %d differs from the first file\'s %d; one queue runs at one rate'
-                                     % (f, sr, sr0))
-                yield wf, sr                        # a pair: audio.resample at equal rates, the downmix alone
-        return iter_transcribe_songs(load(), Hyperparams(N=2048, sr=sr0), iters=a.iters, weights_dir=a.weights,
-                                     guess=a.guess, slots=a.slots, residual=residual, stems=stems, groups=CLI_GROUPS), sr0
-    first = _load_float(a.songs[0], flac)
-    sr0 = first[1]
-
-    def load():
-        for k, f in enumerate(a.songs):
-            wf, sr = first if k == 0 else _load_float(f, flac)
-            if sr != sr0:
-                raise SystemExit('%s: sample rate %d differs from the first file\'s %d; one queue runs at one rate'
-                                 % (f, sr, sr0))
-            yield wf.mean(axis=1) if wf.ndim > 1 else wf
-    return iter_transcribe_songs(load(), Hyperparams(N=2048, sr=sr0), iters=a.iters, weights_dir=a.weights,
-                                 guess=a.guess, slots=a.slots, residual=residual, stems=stems, groups=CLI_GROUPS), sr0
-
-
 def main(argv=None):
-    import argparse
-    from . import flac
     argv = sys.argv[1:] if argv is None else list(argv)
     if '--songs' in argv:
         return main_songs(argv)
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('infile')
     ap.add_argument('outfile')
-    ap.add_argument('--weights', default=None)
-    ap.add_argument('--iters', type=int, default=5)
-    ap.add_argument('--guess', default='bank', choices=('bank', 'render'))
     ap.add_argument('--traversal', default='windows', choices=('windows', 'song'),
                     help="'song': one sliding window per song with the residual kept (run_songs)")
-    ap.add_argument('--sr', type=int, default=None,
-                    help='rate the model runs at; the file is resampled to it from its own rate')
     ap.add_argument('--residual', default=None, metavar='OUT.flac',
                     help='with --traversal song: write what the walk left of the song after every subtraction, 24-bit FLAC '
                          'at the rate the model runs at (with --sr, the resampled rate)')
-    ap.add_argument('--stems-dir', default=None, metavar='DIR',
+    _shared_options(ap, 'rate the model runs at; the file is resampled to it from its own rate', metavar='DIR',
                     help='with --traversal song: write <input stem>.group<g>.flac per instrument group, what the '
                          'subtractions took out of the song, 24-bit FLAC at the rate the model runs at')
-    ap.add_argument('--flac', default='host', choices=FLAC_WRITERS, help=_FLAC_HELP)
-    ap.add_argument('--decode', default='host', choices=DECODERS, help=_DECODE_HELP)
-    ap.add_argument('--format', default='flac', choices=FORMATS, help=_FORMAT_HELP)
     a = ap.parse_args(argv)
     if a.residual is not None and a.traversal != 'song':
         raise SystemExit('--residual needs --traversal song (independent windows have no song-level residual)')
     if a.stems_dir is not None and a.traversal != 'song':
         raise SystemExit('--stems-dir needs --traversal song (independent windows have no song-level stems)')
-    if a.decode == 'device':
-        from . import audio
-        wf, sr, _ = (audio.load_audio if _is_wav(a.infile) else audio.load_flac)(a.infile)
-    else:
-        wf, sr = _load_float(a.infile, flac)
+    wf, sr = next(_read_inputs([a.infile], a.decode))
     if a.sr is None:                             # the model at the file's rate
-        if a.decode == 'device':
-            wf = audio.resample(wf, sr, sr)      # [n, channels] -> mono on the device; mono passes through
-        elif wf.ndim > 1:
-            wf = wf.mean(axis=1)                 # [n, channels] -> mono
-        model_sr, file_sr = sr, None
+        wf, model_sr, file_sr = _mono(wf, sr, a.decode), sr, None
     elif a.sr <= 0:
         raise SystemExit('--sr: the rate must be positive')
     else:                                        # the file at the model's rate: resampled and downmixed on the device

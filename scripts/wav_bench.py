@@ -74,13 +74,11 @@ def unpack_leg(datas):
 
 
 def pack_leg(sigs):
-    lens = [int(s.numel()) for s in sigs]
+    anchor, base, lens = audio._ragged_layout(sigs)
     res = {}
     for fmt in wav.FORMATS:
         c = wav.FORMAT_BYTES[fmt]
         ideal = (4 + c) * sum(lens)
-        anchor = min(s.data_ptr() for s in sigs)
-        base = [(s.data_ptr() - anchor) // 4 for s in sigs]
         ob = np.concatenate([[0], np.cumsum([-(-l * c // 4) * 4 for l in lens])])
         meta = torch.tensor([base, lens, ob[:-1].tolist()], dtype=torch.int64).cuda()
         o = torch.empty((int(ob[-1]),), dtype=torch.uint8, device='cuda')

@@ -191,7 +191,7 @@ def test_save_flac_through_the_reader(env, tmp_path):
             lim = float(1 << (bps - 1))
             want = np.clip(np.rint(y.astype(np.float64) * lim), -lim, lim - 1).astype(np.int64)
             assert (sr, b) == (44100, bps) and np.array_equal(pcm[:, 0] if len(y) else pcm.reshape(-1), want), path
-    sigs = audio._flac_signals(rows)
+    sigs = audio._device_signals(rows)
     assert [s.data_ptr() for s in sigs] == [rows[g].data_ptr() for g in range(3)]
     files = audio.flac_encode(rows, 44100)
     assert len(files) == 3 and files[0] == open(str(tmp_path / 'f24_2.flac'), 'rb').read()

@@ -427,7 +427,46 @@ def test_format_option_parses_and_riff_files_reach_the_wav_reader(tmp_path, caps
     monkeypatch.setattr(audio, 'load_audio', load_audio)
     with pytest.raises(Reached):
         tr.main([song, str(tmp_path / 'o.mid'), '--decode', 'device'])
-    import argparse
-    from amt_saga import flac
     with pytest.raises(Reached):
-        list(tr._load_songs(argparse.Namespace(decode='device', slots=2, songs=[song]), flac))
+        list(tr._read_inputs([song], 'device', 2))
+
+
+def test_device_reader_pulls_groups_lazily_and_opens_no_file(tmp_path, monkeypatch):
+    """--decode device reads every group through audio.load_audio, whatever the files are: no probe opens them, and a
+    group is requested only when the queue pulls past the one before."""
+    from amt_saga import audio, transcribe as tr
+    paths = [str(tmp_path / ('missing_%d.flac' % k)) for k in range(5)]
+    groups = []
+
+    def load_audio(group, verify=True):
+        groups.append(list(group))
+        return [('wave of ' + f, 44100 + paths.index(f), 24) for f in group]
+    monkeypatch.setattr(audio, 'load_audio', load_audio)
+    reader = tr._read_inputs(paths, 'device', 2)
+    assert groups == []                                                            # nothing before the first pull
+    want = [paths[0:2], paths[2:4], paths[4:5]]
+    for k, f in enumerate(paths):
+        assert next(reader) == ('wave of ' + f, 44100 + k)
+        assert groups == want[:k // 2 + 1]                                         # the next group: not before its turn
+    with pytest.raises(StopIteration):
+        next(reader)
+    assert groups == want
+
+
+def test_ragged_layout_of_host_tensors():
+    """The input layout of the three ragged encoder calls, stated once (audio._ragged_layout), on host tensors: base is
+    every pointer minus the lowest in floats, an empty signal gets 0, lens are the lengths; no signal with samples gives
+    no anchor."""
+    import torch
+    from amt_saga import audio
+    (r0, r1, r2), lone, none = torch.zeros((3, 7)).unbind(0), torch.zeros(5), torch.zeros(0)
+    for sigs in ([r0, r1, none, r2, lone], [lone, r2, none, r0, r1]):
+        anchor, base, lens = audio._ragged_layout(sigs)
+        assert anchor == min(s.data_ptr() for s in sigs if s.numel())
+        assert lens == [int(s.numel()) for s in sigs] and sorted(lens) == [0, 5, 7, 7, 7]
+        for s, b in zip(sigs, base):
+            assert b == ((s.data_ptr() - anchor) // 4 if s.numel() else 0) and b >= 0
+        assert base[2] == 0 and min(base) == 0
+        at = dict(zip(map(id, sigs), base))
+        assert at[id(r1)] - at[id(r0)] == 7 and at[id(r2)] - at[id(r0)] == 14
+    assert audio._ragged_layout([none, torch.zeros(0)]) == (None, [0, 0], [0, 0])
