@@ -111,6 +111,8 @@ PROTOTYPES = {
     'amt_flac_scratch_bytes': (C.c_longlong, [C.c_int, C.c_longlong, C.c_int, C.c_int]),
     'amt_flac_encode_ragged': (C.c_int, [vp, vp, vp, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_longlong, vp,
                                          C.c_longlong, vp, C.c_longlong, vp, vp, vp, vp, vp]),
+    'amt_flac_encode_lpc_ragged': (C.c_int, [vp, vp, vp, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_longlong, C.c_int,
+                                             vp, C.c_longlong, vp, C.c_longlong, vp, vp, vp, vp, vp]),
     'amt_flac_decode_scratch_bytes': (C.c_longlong, [C.c_longlong, C.c_longlong]),
     'amt_flac_decode_ragged': (C.c_int, [vp, C.c_longlong, vp, C.c_int, vp, C.c_longlong, vp, C.c_int, vp, C.c_longlong,
                                          C.c_longlong, vp, vp, C.c_longlong, vp, vp, vp, vp]),

@@ -1111,11 +1111,29 @@ def _device_signals(waves):
 # ======================================================================================
 # FLAC encoding on the device (the soundfile.write of audio_to_flac, util_audio.py:966-968)
 # ======================================================================================
-def flac_encode_streams(waves, bps=24, blocksize=4096, first_frame=0):
+FLAC_PREDICTORS = ('fixed', 'lpc')
+FLAC_LPC_MAX_ORDER = 12
+
+
+def _flac_predictor(predictor, lpc_order):
+    """The check of predictor / lpc_order, before any device work: the order amt_flac_encode_lpc_ragged gets, 0 for
+    'fixed' (amt_flac_encode_ragged; lpc_order is then only checked)."""
+    if not isinstance(predictor, str) or predictor not in FLAC_PREDICTORS:
+        raise ValueError('Requested attribute does not exist: predictor %r (one of %s)' % (predictor, FLAC_PREDICTORS))
+    if isinstance(lpc_order, bool) or not isinstance(lpc_order, (int, np.integer)) \
+            or not 1 <= lpc_order <= FLAC_LPC_MAX_ORDER:
+        raise ValueError('Invalid Input shape. Expected: lpc_order in 1 .. %d . Got: %r' % (FLAC_LPC_MAX_ORDER, lpc_order))
+    return int(lpc_order) if predictor == 'lpc' else 0
+
+
+def flac_encode_streams(waves, bps=24, blocksize=4096, first_frame=0, predictor='fixed', lpc_order=12):
     """amt_flac_encode_ragged for the signals of `waves` (see _device_signals), one call on the current stream: returns
     (out, stream_off, frame_minmax, md5, frame_bytes) -- out a uint8 device buffer in which signal i's frames lie back
     to back at [stream_off[i], stream_off[i + 1]); stream_off int64 [n + 1], frame_minmax int32 [n, 2], md5 uint8
-    [n, 16], frame_bytes int64 [n, frames of the longest]: all device tensors, nothing is synchronised."""
+    [n, 16], frame_bytes int64 [n, frames of the longest]: all device tensors, nothing is synchronised.
+    predictor='lpc': amt_flac_encode_lpc_ragged, LPC subframes of order 1 .. lpc_order beside the fixed predictors
+    (DESIGN 20); the buffers are the same, no frame is larger."""
+    order = _flac_predictor(predictor, lpc_order)
     lib = _lib.load()
     sigs = _device_signals(waves)
     bound = int(lib.amt_flac_frame_bound(int(blocksize), int(bps)))
@@ -1136,10 +1154,11 @@ def flac_encode_streams(waves, bps=24, blocksize=4096, first_frame=0):
     md5 = torch.empty((n, 16), dtype=torch.uint8, device=dev)
     # (a host-side 8 stands where a buffer would be empty, the scratch where no signal has samples: the ABI refuses NULL)
     fb = frame_bytes if frame_bytes.numel() else torch.empty((1,), dtype=torch.int64, device=dev)
-    _lib.check(lib.amt_flac_encode_ragged(
-        C.c_void_p(scratch.data_ptr() if anchor is None else anchor), ptr(meta[0]), ptr(meta[1]), n, max_len,
-        int(blocksize), int(bps), int(first_frame), ptr(scratch), scratch.numel(), ptr(out), out.numel(), ptr(fb),
-        ptr(stream_off), ptr(minmax), ptr(md5), stream_ptr()))
+    head = (C.c_void_p(scratch.data_ptr() if anchor is None else anchor), ptr(meta[0]), ptr(meta[1]), n, max_len,
+            int(blocksize), int(bps), int(first_frame))
+    tail = (ptr(scratch), scratch.numel(), ptr(out), out.numel(), ptr(fb), ptr(stream_off), ptr(minmax), ptr(md5),
+            stream_ptr())
+    _lib.check(lib.amt_flac_encode_lpc_ragged(*head, order, *tail) if order else lib.amt_flac_encode_ragged(*head, *tail))
     # the signals and the scratch stay referenced until the call is enqueued; torch's allocator keeps a freed block
     # for the stream that used it, so work enqueued later on this stream cannot overtake the encoder
     return out, stream_off, minmax, md5, frame_bytes
@@ -1152,13 +1171,16 @@ def flac_stream_header(n_samples, sr, bps, blocksize, min_frame, max_frame, md5)
     return b'fLaC' + bytes([0x80]) + len(si).to_bytes(3, 'big') + si
 
 
-def flac_encode(waves, sr, bps=24, blocksize=4096):
+def flac_encode(waves, sr, bps=24, blocksize=4096, predictor='fixed', lpc_order=12):
     """audio_to_flac (util_audio.py:966-968) without the file: every signal of `waves` -- a list of 1-d float32 device
     tensors; a [G, n] tensor counts as G signals, its rows are not copied -- as the bytes of a complete mono FLAC file
     (fLaC, STREAMINFO, frames).  One encode call for the whole list, on the current stream, so it is ordered after
-    whatever produced the tensors; the frames come back in one device-to-host copy."""
+    whatever produced the tensors; the frames come back in one device-to-host copy.  predictor='fixed' (the default)
+    or 'lpc' with lpc_order in 1 .. 12: see flac_encode_streams."""
+    _flac_predictor(predictor, lpc_order)
     sigs = _device_signals(waves)
-    out, stream_off, minmax, md5, _ = flac_encode_streams(sigs, bps=bps, blocksize=blocksize)
+    out, stream_off, minmax, md5, _ = flac_encode_streams(sigs, bps=bps, blocksize=blocksize, predictor=predictor,
+                                                          lpc_order=lpc_order)
     off = stream_off.cpu().tolist()
     minmax, md5 = minmax.cpu().tolist(), md5.cpu().numpy()
     if off[-1] > out.numel():
@@ -1168,9 +1190,10 @@ def flac_encode(waves, sr, bps=24, blocksize=4096):
             + data[off[i]:off[i + 1]] for i, s in enumerate(sigs)]
 
 
-def save_flac(waves, paths, sr, bps=24):
-    """flac_encode(waves, sr, bps) written to `paths`, one file per signal, one write per file."""
-    _write_files(flac_encode(waves, sr, bps=bps), paths)
+def save_flac(waves, paths, sr, bps=24, predictor='fixed', lpc_order=12):
+    """flac_encode(waves, sr, bps, predictor=..., lpc_order=...) written to `paths`, one file per signal, one write per
+    file."""
+    _write_files(flac_encode(waves, sr, bps=bps, predictor=predictor, lpc_order=lpc_order), paths)
 
 
 # ======================================================================================

@@ -21,6 +21,8 @@ provide for the inference direction:
     group, <input stem>.group<g>.flac (the reference's _guessed.flac, training.py:426-447, at song length).
     --flac {host,device}: the writer of those files -- host (default): amt_saga.flac's VERBATIM writer; device: the HIP
     encoder (audio.save_flac), a song's residual and stems in one call, compressed.
+    --flac-predictor {fixed,lpc}: the predictors of --flac device -- fixed (default): orders 0..4; lpc: linear prediction
+    of order 1..12 beside them.  Refused with --flac host.
     --decode {host,device}: the reader of the input files -- host (default): amt_saga.flac's reader; device: the HIP
     decoder (audio.load_audio), --slots files per decode call with --songs, the samples never on the host.
     A file that begins with RIFF is read as WAV, by amt_saga.wav's reader (host) or by audio.load_audio (device: the FLAC
@@ -178,6 +180,12 @@ _FLAC_HELP = ("writer of --residual / --residual-dir / --stems-dir: 'host' = the
               "--format wav")
 
 
+FLAC_PREDICTORS = audio.FLAC_PREDICTORS
+_FLAC_PREDICTOR_HELP = ("predictors of --flac device: 'fixed' (the default) = the fixed orders 0..4, 'lpc' = linear "
+                        "prediction of order 1..12 beside them (smaller files for tonal audio, more encoding time); the "
+                        "host writer has no predictors, so 'lpc' with --flac host is refused; no effect with --format wav")
+
+
 FORMATS = ('flac', 'wav')
 _FORMAT_HELP = ("container of --residual / --residual-dir / --stems-dir: 'flac' (the default) or 'wav' = PCM-24 WAV packed "
                 "on the device (audio.save_wav), a song's residual and stems in one call, the generated names ending in "
@@ -200,8 +208,15 @@ def _shared_options(ap, sr_help, **stems_dir):
     ap.add_argument('--sr', type=int, default=None, help=sr_help)
     ap.add_argument('--stems-dir', default=None, **stems_dir)
     ap.add_argument('--flac', default='host', choices=FLAC_WRITERS, help=_FLAC_HELP)
+    ap.add_argument('--flac-predictor', default='fixed', choices=FLAC_PREDICTORS, help=_FLAC_PREDICTOR_HELP)
     ap.add_argument('--decode', default='host', choices=DECODERS, help=_DECODE_HELP)
     ap.add_argument('--format', default='flac', choices=FORMATS, help=_FORMAT_HELP)
+
+
+def _check_writer(a):
+    """--flac-predictor lpc asks for the device encoder: refused with the host writer, before any work."""
+    if a.flac_predictor == 'lpc' and a.flac == 'host' and a.format == 'flac':
+        raise SystemExit('--flac-predictor lpc needs --flac device (the host writer has no predictors)')
 
 
 def _is_wav(path):
@@ -241,16 +256,20 @@ def _mono(wf, sr, decode):
 
 
 def write_song_audio(rate, residual=None, residual_path=None, stems=None, stems_dir=None, name=None, flac='host',
-                     format='flac'):
+                     format='flac', predictor='fixed'):
     """What a song walk kept, as 24-bit FLAC at `rate`: `residual` (1-d device tensor) to residual_path, and / or the rows
     of `stems` [G, samples] to <stems_dir>/<name>.group<g>.flac, g the reference group id of the row (CLI_GROUPS).
     flac='host': the VERBATIM writer of amt_saga.flac, file by file (the default: the bytes every earlier call wrote);
     flac='device': audio.save_flac -- the residual and all stems of the song in ONE encode call on the device,
     compressed, and no sample crosses to the host before it is coded.
     format='wav': PCM-24 WAV instead, <name>.group<g>.wav, through audio.save_wav -- one pack call and one copy for the
-    residual and all stems of the song; `flac` then has no effect."""
-    if flac not in FLAC_WRITERS or format not in FORMATS:
+    residual and all stems of the song; `flac` then has no effect.
+    predictor='lpc' (with flac='device'): save_flac's LPC subframes beside the fixed predictors; the host writer has no
+    predictors and refuses it."""
+    if flac not in FLAC_WRITERS or format not in FORMATS or predictor not in FLAC_PREDICTORS:
         raise ValueError('Requested attribute does not exist')
+    if predictor == 'lpc' and flac == 'host' and format == 'flac':
+        raise ValueError("predictor='lpc' needs flac='device': the host writer has no predictors")
     waves, paths, notes = [], [], []
     if residual is not None:
         waves.append(residual)
@@ -266,7 +285,7 @@ def write_song_audio(rate, residual=None, residual_path=None, stems=None, stems_
     if format == 'wav':
         audio.save_wav(waves, paths, rate, fmt='pcm24')
     elif flac == 'device':
-        audio.save_flac(waves, paths, rate)
+        audio.save_flac(waves, paths, rate, predictor=predictor)
     else:
         for w, path in zip(waves, paths):
             host_flac.save_float(np.ascontiguousarray(w.cpu().numpy()), path, sr=rate)
@@ -299,6 +318,7 @@ def main_songs(argv):
                     help='write <stem>.group<g>.flac per song and instrument group as it finishes: what the subtractions '
                          'took out of the song, 24-bit FLAC at the rate the model runs at')
     a = ap.parse_args(argv)
+    _check_writer(a)
     os.makedirs(a.out_dir, exist_ok=True)
     keep, keep_stems = a.residual_dir is not None, a.stems_dir is not None
     for d in (a.residual_dir, a.stems_dir):
@@ -331,7 +351,7 @@ def main_songs(argv):
         write_song_audio(rate, residual=item[3] if keep else None,
                          residual_path=os.path.join(a.residual_dir, stems[i] + '.residual.' + a.format) if keep else None,
                          stems=item[-1] if keep_stems else None, stems_dir=a.stems_dir, name=stems[i], flac=a.flac,
-                         format=a.format)
+                         format=a.format, predictor=a.flac_predictor)
 
 
 def main(argv=None):
@@ -350,6 +370,7 @@ def main(argv=None):
                     help='with --traversal song: write <input stem>.group<g>.flac per instrument group, what the '
                          'subtractions took out of the song, 24-bit FLAC at the rate the model runs at')
     a = ap.parse_args(argv)
+    _check_writer(a)
     if a.residual is not None and a.traversal != 'song':
         raise SystemExit('--residual needs --traversal song (independent windows have no song-level residual)')
     if a.stems_dir is not None and a.traversal != 'song':
@@ -375,7 +396,8 @@ def main(argv=None):
         os.makedirs(a.stems_dir, exist_ok=True)
     write_song_audio(model_sr, residual=got[2] if a.residual is not None else None, residual_path=a.residual,
                      stems=got[-1] if a.stems_dir is not None else None, stems_dir=a.stems_dir,
-                     name=os.path.splitext(os.path.basename(a.infile))[0], flac=a.flac, format=a.format)
+                     name=os.path.splitext(os.path.basename(a.infile))[0], flac=a.flac, format=a.format,
+                     predictor=a.flac_predictor)
 
 
 if __name__ == '__main__':

@@ -13,6 +13,11 @@
 //     bits(o, p) = 8 + o bps + 6 + sum_j cost_j; smallest bits, smallest p, then smallest o on ties; VERBATIM unless
 //     that is strictly below 8 + bs bps.
 //   zero bits to the byte boundary, CRC-16 (0x8005) of the whole frame.
+//   With linear prediction (amt_flac_encode_lpc_ragged; DESIGN 20, tests/flac_lpc_reference.py): after the FIXED orders
+//   the LPC orders m = 1..L (bs > m) of amt_flac_lpc_core.h join the same choice -- type byte (32 + m - 1) << 1, m
+//   warm-up samples, 4 bits P - 1, 5 bits shift, m coefficients of P bits, the same residual coding;
+//     bits(m, p) = 8 + m bps + 4 + 5 + m P + 6 + sum_j cost_j.  A candidate replaces the best so far only if strictly
+//   smaller, so FIXED wins a tie against LPC and the smaller order wins; |r| >= 2^27 disqualifies an LPC order.
 //
 // Design:
 //  * frame kernel: one 256-thread workgroup per frame, grid (frames of the longest signal, signals).  Thread t owns at
@@ -33,15 +38,21 @@
 //  * offsets: one workgroup per signal scans its frame sizes; one workgroup scans the signals' totals.
 //  * compaction: one workgroup per frame copies slot -> byte offset, byte-granular.
 //  * MD5: one wave per signal; the lanes build the message words from the same quantiser, the rounds run on LDS words.
+//  * LPC (the kernel's second instantiation): the windowed block goes to LDS, every thread sums its samples' products
+//    for the 13 lags in int64, the sums are added over the wave and the four waves (exact: any order), thread 0 runs the
+//    float64 recurrence and the quantiser of amt_flac_lpc_core.h for all orders into LDS, and every order then goes
+//    through the cost search of the fixed orders with its residuals computed from q and its coefficients in LDS.
 //  * no workgroup waits for another; the kernels are ordered by the stream alone.  No global atomics.
 #include <math.h>
 
 #include "amt_common.h"
 #include "amt_flac_common.h"
+#include "amt_flac_lpc_core.h"
 
 #define AMT_FL_THREADS 256
 #define AMT_FL_MAXBS 4096
 #define AMT_FL_KN 29                                            /* k = 0 .. 28 */
+#define AMT_FL_CAND (5 + FLL_MAX_ORDER)                           /* FIXED 0 .. 4, then LPC 1 .. 12 */
 #define AMT_FL_WORDS ((13 + (8 + AMT_FL_MAXBS * 24 + 7) / 8 + 2 + 3) / 4 + 2)
 
 typedef unsigned long long fl_u64;
@@ -75,6 +86,24 @@ __device__ __forceinline__ int fl_resid(const int *q, int i, int o) {
 }
 
 __device__ __forceinline__ unsigned fl_zig(int r) { return ((unsigned)r << 1) ^ (unsigned)(r >> 31); }
+
+// The residual of sample i under one predictor, as the cost search and the emit phase take it.  `bad` is raised where
+// the candidate is disqualified (LPC: |r| >= 2^27); the fixed predictors never raise it.
+struct fl_fixed_resid {
+    const int *q;
+    int o;
+    __device__ __forceinline__ int operator()(int i, int &bad) const { return fl_resid(q, i, o); }
+};
+
+struct fl_lpc_resid {
+    const int *q, *c;
+    int m, shift;
+    __device__ __forceinline__ int operator()(int i, int &bad) const {
+        const fll_i64 r = fll_resid(q, i, c, m, shift);
+        bad |= !fll_resid_ok(r);
+        return (int)r;
+    }
+};
 
 // n bits (1 .. 32) of v (< 2^n) at bit `pos` of the zeroed big-endian word buffer of AMT_FL_WORDS words
 __device__ __forceinline__ void fl_put(unsigned *buf, unsigned pos, int n, unsigned v) {
@@ -115,18 +144,126 @@ __device__ __forceinline__ fl_u64 fl_block_scan(fl_u64 v, fl_u64 *lds, fl_u64 *t
     return before + incl - v;
 }
 
+// The cost search of one predictor of order o over the block: the thread's sums of u >> k over its samples [i0, i1),
+// the butterflies, the best k of every partition of every level into kbest_o, the level totals.  Returns the smallest
+// head_bits + sum of the partition costs over the partition orders, *best_p its p (the smallest of a tie); *bad is
+// raised in the threads whose residuals disqualify the predictor.  Ends with a barrier: wsum and red are free again.
+template <class Resid>
+__device__ __forceinline__ fl_u64 fl_cost_search(const Resid &resid, int o, fl_u64 head_bits, int bs, int pmax, int i0,
+                                                 int i1, fl_u64 (*wsum)[AMT_FL_KN], fl_u64 (*red)[9],
+                                                 unsigned char *kbest_o, int *best_p, int *bad) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    unsigned s32[AMT_FL_KN];
+#pragma unroll
+    for (int k = 0; k < AMT_FL_KN; ++k) s32[k] = 0u;
+    for (int i = max(i0, o); i < i1; ++i) {
+        const unsigned u = fl_zig(resid(i, *bad));
+#pragma unroll
+        for (int k = 0; k < AMT_FL_KN; ++k) s32[k] += u >> k;
+    }
+    fl_u64 s[AMT_FL_KN];
+#pragma unroll
+    for (int k = 0; k < AMT_FL_KN; ++k) s[k] = s32[k];
+    fl_u64 c[9];
+#pragma unroll
+    for (int lg = 0; lg <= 8; ++lg) {
+        const int p = 8 - lg;
+        if (lg >= 1 && lg <= 6) {
+#pragma unroll
+            for (int k = 0; k < AMT_FL_KN; ++k) s[k] += __shfl_xor(s[k], 1 << (lg - 1), 64);
+        } else if (lg == 7) {
+            if (lane == 0) {
+#pragma unroll
+                for (int k = 0; k < AMT_FL_KN; ++k) wsum[w][k] = s[k];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < AMT_FL_KN; ++k) s[k] += wsum[w ^ 1][k];
+        } else if (lg == 8) {
+#pragma unroll
+            for (int k = 0; k < AMT_FL_KN; ++k) s[k] += wsum[w ^ 2][k] + wsum[w ^ 3][k];
+        }
+        c[lg] = 0;
+        if (p <= pmax && (bs >> p) > o) {                         // block-uniform
+            const fl_u64 n = (fl_u64)((bs >> p) - (tid < (1 << lg) ? o : 0));
+            fl_u64 bc = 5 + n + s[0];
+            int bk = 0;
+#pragma unroll
+            for (int k = 1; k < AMT_FL_KN; ++k) {
+                const fl_u64 v = 5 + n * (fl_u64)(k + 1) + s[k];
+                if (v < bc) { bc = v; bk = k; }
+            }
+            if ((tid & ((1 << lg) - 1)) == 0) {
+                kbest_o[(1 << p) - 1 + (tid >> lg)] = (unsigned char)bk;
+                c[lg] = bc;
+            }
+        }
+    }
+    // totals of the nine levels over the block
+#pragma unroll
+    for (int lg = 0; lg <= 8; ++lg) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) c[lg] += __shfl_xor(c[lg], off, 64);
+        if (lane == 0) red[w][lg] = c[lg];
+    }
+    __syncthreads();
+    fl_u64 ob = ~0ull;
+    int op = 0;
+#pragma unroll
+    for (int lg = 0; lg <= 8; ++lg) {                             // p descending: <= keeps the smallest p of a tie
+        const int p = 8 - lg;
+        if (p <= pmax && (bs >> p) > o) {
+            const fl_u64 t = head_bits + red[0][lg] + red[1][lg] + red[2][lg] + red[3][lg];
+            if (t <= ob) { ob = t; op = p; }
+        }
+    }
+    *best_p = op;
+    __syncthreads();                                              // wsum / red are free for the next predictor
+    return ob;
+}
+
+// The residual codes of the chosen predictor of order o, partition order 8 - lg, from bit `at` of the frame: per
+// partition the 5-bit parameter (its leader thread), per sample the unary zeros, the stop bit and the k low bits.
+template <class Resid>
+__device__ __forceinline__ void fl_emit_codes(const Resid &resid, int o, int i0, int i1, int lg, int k, unsigned at,
+                                              unsigned *bits, fl_u64 *scan_lds) {
+    const int tid = threadIdx.x;
+    const bool leader = (tid & ((1 << lg) - 1)) == 0;
+    int bad = 0;
+    unsigned mine = leader ? 5u : 0u;
+    for (int i = max(i0, o); i < i1; ++i) mine += (fl_zig(resid(i, bad)) >> k) + 1u + k;
+    fl_u64 total;
+    unsigned pos = at + (unsigned)fl_block_scan(mine, scan_lds, &total);
+    if (leader) { fl_put(bits, pos, 5, (unsigned)k); pos += 5; }
+    for (int i = max(i0, o); i < i1; ++i) {
+        const unsigned u = fl_zig(resid(i, bad));
+        pos += u >> k;
+        fl_put(bits, pos, 1 + k, (1u << k) | (u & ((1u << k) - 1u)));
+        pos += 1 + k;
+    }
+}
+
+// LPC = false: the fixed predictors alone (amt_flac_encode_ragged; lpc_order is not read).  LPC = true: the LPC orders
+// 1 .. lpc_order as well.
+template <bool LPC>
 __global__ __launch_bounds__(AMT_FL_THREADS) void flac_frame_kernel(
     const float *__restrict__ wave, const long long *__restrict__ base, const long long *__restrict__ len,
     long long max_len, int blocksize, int bps, long long first_frame, long long frames_max,
-    unsigned char *__restrict__ scratch, long long bound, long long *__restrict__ frame_bytes) {
+    unsigned char *__restrict__ scratch, long long bound, long long *__restrict__ frame_bytes, int lpc_order) {
     __shared__ int q[AMT_FL_MAXBS];
     __shared__ unsigned bits[AMT_FL_WORDS];
     __shared__ fl_u64 wsum[4][AMT_FL_KN];
     __shared__ fl_u64 red[4][9];
     __shared__ fl_u64 scan_lds[4];
-    __shared__ unsigned char kbest[5][512];
+    __shared__ unsigned char kbest[LPC ? AMT_FL_CAND : 5][512];
     __shared__ unsigned crc_s[AMT_FL_THREADS];
     __shared__ unsigned short crctab[256];
+    // LPC only (never referenced, so not allocated, in the fixed instantiation)
+    __shared__ int xw[LPC ? AMT_FL_MAXBS : 1];                    // the windowed block
+    __shared__ fll_i64 acorr[4][FLL_LAGS];                        // per wave, then [0]: the block's autocorrelation
+    __shared__ double lpc_work[FLL_WORK];
+    __shared__ int lpc_coef[FLL_MAX_ORDER * FLL_MAX_ORDER];
+    __shared__ int lpc_shift[FLL_MAX_ORDER];
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int b = blockIdx.y;
@@ -164,72 +301,47 @@ __global__ __launch_bounds__(AMT_FL_THREADS) void flac_frame_kernel(
     int best_o = 0, best_p = 0;
     if (!constant) {
         for (int o = 0; o < 5 && bs > o; ++o) {
-            unsigned s32[AMT_FL_KN];
+            int op, bad = 0;
+            const fl_u64 ob = fl_cost_search(fl_fixed_resid{q, o}, o, 8 + (fl_u64)(o * bps) + 6, bs, pmax, i0, i1, wsum,
+                                             red, kbest[o], &op, &bad);
+            if (ob < best_bits) { best_bits = ob; best_o = o; best_p = op; }
+        }
+        if constexpr (LPC) {
+            // autocorrelation of the windowed block: exact int64 sums, so the order of the additions is free
+            for (int i = i0; i < i1; ++i) xw[i] = fll_windowed(q[i], i, bs);
+            __syncthreads();
+            fll_i64 acc[FLL_LAGS];
 #pragma unroll
-            for (int k = 0; k < AMT_FL_KN; ++k) s32[k] = 0u;
-            for (int i = max(i0, o); i < i1; ++i) {
-                const unsigned u = fl_zig(fl_resid(q, i, o));
+            for (int l = 0; l < FLL_LAGS; ++l) acc[l] = 0;
+            for (int i = i0; i < i1; ++i) {
+                const fll_i64 xi = xw[i];
 #pragma unroll
-                for (int k = 0; k < AMT_FL_KN; ++k) s32[k] += u >> k;
+                for (int l = 0; l < FLL_LAGS; ++l)
+                    if (i >= l) acc[l] += xi * xw[i - l];
             }
-            fl_u64 s[AMT_FL_KN];
 #pragma unroll
-            for (int k = 0; k < AMT_FL_KN; ++k) s[k] = s32[k];
-            fl_u64 c[9];
+            for (int l = 0; l < FLL_LAGS; ++l) {
 #pragma unroll
-            for (int lg = 0; lg <= 8; ++lg) {
-                const int p = 8 - lg;
-                if (lg >= 1 && lg <= 6) {
-#pragma unroll
-                    for (int k = 0; k < AMT_FL_KN; ++k) s[k] += __shfl_xor(s[k], 1 << (lg - 1), 64);
-                } else if (lg == 7) {
-                    if (lane == 0) {
-#pragma unroll
-                        for (int k = 0; k < AMT_FL_KN; ++k) wsum[w][k] = s[k];
-                    }
-                    __syncthreads();
-#pragma unroll
-                    for (int k = 0; k < AMT_FL_KN; ++k) s[k] += wsum[w ^ 1][k];
-                } else if (lg == 8) {
-#pragma unroll
-                    for (int k = 0; k < AMT_FL_KN; ++k) s[k] += wsum[w ^ 2][k] + wsum[w ^ 3][k];
-                }
-                c[lg] = 0;
-                if (p <= pmax && (bs >> p) > o) {                 // block-uniform
-                    const fl_u64 n = (fl_u64)((bs >> p) - (tid < (1 << lg) ? o : 0));
-                    fl_u64 bc = 5 + n + s[0];
-                    int bk = 0;
-#pragma unroll
-                    for (int k = 1; k < AMT_FL_KN; ++k) {
-                        const fl_u64 v = 5 + n * (fl_u64)(k + 1) + s[k];
-                        if (v < bc) { bc = v; bk = k; }
-                    }
-                    if ((tid & ((1 << lg) - 1)) == 0) {
-                        kbest[o][(1 << p) - 1 + (tid >> lg)] = (unsigned char)bk;
-                        c[lg] = bc;
-                    }
-                }
-            }
-            // totals of the nine levels over the block
-#pragma unroll
-            for (int lg = 0; lg <= 8; ++lg) {
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) c[lg] += __shfl_xor(c[lg], off, 64);
-                if (lane == 0) red[w][lg] = c[lg];
+                for (int off = 32; off > 0; off >>= 1) acc[l] += __shfl_xor(acc[l], off, 64);
+                if (lane == 0) acorr[w][l] = acc[l];
             }
             __syncthreads();
-            fl_u64 ob = ~0ull;
-            int op = 0;
-#pragma unroll
-            for (int lg = 0; lg <= 8; ++lg) {                     // p descending: <= keeps the smallest p of a tie
-                const int p = 8 - lg;
-                if (p <= pmax && (bs >> p) > o) {
-                    const fl_u64 t = 8 + (fl_u64)(o * bps) + 6 + red[0][lg] + red[1][lg] + red[2][lg] + red[3][lg];
-                    if (t <= ob) { ob = t; op = p; }
-                }
+            const int orders = min(lpc_order, bs - 1);
+            if (tid == 0) {                                       // one lane: the recurrence is sequential
+                for (int l = 0; l < FLL_LAGS; ++l) acorr[0][l] += acorr[1][l] + acorr[2][l] + acorr[3][l];
+                fll_analyse(acorr[0], orders, fll_precision(bps), lpc_work, lpc_coef, lpc_shift);
             }
-            if (ob < best_bits) { best_bits = ob; best_o = o; best_p = op; }
-            __syncthreads();                                      // wsum / red are free for the next order
+            __syncthreads();
+            for (int m = 1; m <= orders; ++m) {
+                const int sh = lpc_shift[m - 1];                  // block-uniform
+                if (sh < 0) continue;
+                int op, bad = 0;
+                const fl_lpc_resid rs{q, lpc_coef + (m - 1) * FLL_MAX_ORDER, m, sh};
+                const fl_u64 head = 8 + (fl_u64)(m * bps) + 4 + 5 + (fl_u64)(m * fll_precision(bps)) + 6;
+                const fl_u64 ob = fl_cost_search(rs, m, head, bs, pmax, i0, i1, wsum, red, kbest[4 + m], &op, &bad);
+                if (__syncthreads_or(bad)) continue;              // some |r| >= 2^27: no candidate
+                if (ob < best_bits) { best_bits = ob; best_o = 4 + m; best_p = op; }
+            }
         }
     }
 
@@ -266,24 +378,29 @@ __global__ __launch_bounds__(AMT_FL_THREADS) void flac_frame_kernel(
         if (tid == 0) fl_put(bits, sp + 8, bps, (unsigned)q[0] & mask);
     } else if (best_bits < verbatim_bits) {
         body_bits = best_bits;
-        const int o = best_o, p = best_p, lg = 8 - p;
-        if (tid == 0) {
-            fl_put(bits, sp, 8, (unsigned)(8 + o) << 1);
-            for (int i = 0; i < o; ++i) fl_put(bits, sp + 8 + i * bps, bps, (unsigned)q[i] & mask);
-            fl_put(bits, sp + 8 + o * bps, 6, 0x10u | (unsigned)p);
-        }
-        const int k = kbest[o][(1 << p) - 1 + (tid >> lg)];
-        const bool leader = (tid & ((1 << lg) - 1)) == 0;
-        unsigned mine = leader ? 5u : 0u;
-        for (int i = max(i0, o); i < i1; ++i) mine += (fl_zig(fl_resid(q, i, o)) >> k) + 1u + k;
-        fl_u64 total;
-        unsigned pos = sp + 8 + o * bps + 6 + (unsigned)fl_block_scan(mine, scan_lds, &total);
-        if (leader) { fl_put(bits, pos, 5, (unsigned)k); pos += 5; }
-        for (int i = max(i0, o); i < i1; ++i) {
-            const unsigned u = fl_zig(fl_resid(q, i, o));
-            pos += u >> k;
-            fl_put(bits, pos, 1 + k, (1u << k) | (u & ((1u << k) - 1u)));
-            pos += 1 + k;
+        const int p = best_p, lg = 8 - p;
+        const int k = kbest[best_o][(1 << p) - 1 + (tid >> lg)];
+        if (!LPC || best_o < 5) {
+            const int o = best_o;
+            if (tid == 0) {
+                fl_put(bits, sp, 8, (unsigned)(8 + o) << 1);
+                for (int i = 0; i < o; ++i) fl_put(bits, sp + 8 + i * bps, bps, (unsigned)q[i] & mask);
+                fl_put(bits, sp + 8 + o * bps, 6, 0x10u | (unsigned)p);
+            }
+            fl_emit_codes(fl_fixed_resid{q, o}, o, i0, i1, lg, k, sp + 8 + o * bps + 6, bits, scan_lds);
+        } else if constexpr (LPC) {
+            const int m = best_o - 4, prec = fll_precision(bps), sh = lpc_shift[m - 1];
+            const int *cf = lpc_coef + (m - 1) * FLL_MAX_ORDER;
+            const unsigned at = sp + 8 + m * bps + 4 + 5 + m * prec;
+            if (tid == 0) {
+                fl_put(bits, sp, 8, (unsigned)(32 + m - 1) << 1);
+                for (int i = 0; i < m; ++i) fl_put(bits, sp + 8 + i * bps, bps, (unsigned)q[i] & mask);
+                fl_put(bits, sp + 8 + m * bps, 4, (unsigned)(prec - 1));
+                fl_put(bits, sp + 8 + m * bps + 4, 5, (unsigned)sh);
+                for (int j = 0; j < m; ++j) fl_put(bits, sp + 8 + m * bps + 9 + j * prec, prec, (unsigned)cf[j] & ((1u << prec) - 1u));
+                fl_put(bits, at, 6, 0x10u | (unsigned)p);
+            }
+            fl_emit_codes(fl_lpc_resid{q, cf, m, sh}, m, i0, i1, lg, k, at + 6, bits, scan_lds);
         }
     } else {
         body_bits = verbatim_bits;
@@ -464,10 +581,11 @@ long long amt_flac_scratch_bytes(int n, long long max_len, int blocksize, int bp
     return (slots * bound + 7) / 8 * 8 + 8 * slots;
 }
 
-int amt_flac_encode_ragged(const float *wave, const long long *base, const long long *len, int n, long long max_len,
-                           int blocksize, int bps, long long first_frame, unsigned char *scratch,
-                           long long scratch_bytes, unsigned char *out, long long out_bytes, long long *frame_bytes,
-                           long long *stream_off, int *frame_minmax, unsigned char *md5, void *stream_) {
+// both entries: lpc_order 0 = the fixed predictors alone
+static int fl_encode(const float *wave, const long long *base, const long long *len, int n, long long max_len,
+                     int blocksize, int bps, long long first_frame, unsigned char *scratch, long long scratch_bytes,
+                     unsigned char *out, long long out_bytes, long long *frame_bytes, long long *stream_off,
+                     int *frame_minmax, unsigned char *md5, void *stream_, int lpc_order) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!wave || !base || !len || !scratch || !out || !frame_bytes || !stream_off || !frame_minmax || !md5)
         return AMT_E_INVALID;
@@ -484,8 +602,14 @@ int amt_flac_encode_ragged(const float *wave, const long long *base, const long 
     long long *frame_off = (long long *)(scratch + (slots * bound + 7) / 8 * 8);
     if (frames > 0) {
         const dim3 grid((unsigned)frames, (unsigned)n);
-        flac_frame_kernel<<<grid, AMT_FL_THREADS, 0, stream>>>(wave, base, len, max_len, blocksize, bps, first_frame,
-                                                               frames, scratch, bound, frame_bytes);
+        if (lpc_order > 0)
+            flac_frame_kernel<true><<<grid, AMT_FL_THREADS, 0, stream>>>(wave, base, len, max_len, blocksize, bps,
+                                                                         first_frame, frames, scratch, bound,
+                                                                         frame_bytes, lpc_order);
+        else
+            flac_frame_kernel<false><<<grid, AMT_FL_THREADS, 0, stream>>>(wave, base, len, max_len, blocksize, bps,
+                                                                          first_frame, frames, scratch, bound,
+                                                                          frame_bytes, 0);
         AMT_LAUNCH_CHECK();
     }
     flac_frame_offsets_kernel<<<n, AMT_FL_THREADS, 0, stream>>>(len, max_len, blocksize, frames, frame_bytes, frame_off,
@@ -504,6 +628,23 @@ int amt_flac_encode_ragged(const float *wave, const long long *base, const long 
     flac_md5_kernel<<<n, AMT_FL_MD5_LANES, 0, stream>>>(wave, base, len, max_len, bps, md5, kc);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
+}
+
+int amt_flac_encode_ragged(const float *wave, const long long *base, const long long *len, int n, long long max_len,
+                           int blocksize, int bps, long long first_frame, unsigned char *scratch,
+                           long long scratch_bytes, unsigned char *out, long long out_bytes, long long *frame_bytes,
+                           long long *stream_off, int *frame_minmax, unsigned char *md5, void *stream) {
+    return fl_encode(wave, base, len, n, max_len, blocksize, bps, first_frame, scratch, scratch_bytes, out, out_bytes,
+                     frame_bytes, stream_off, frame_minmax, md5, stream, 0);
+}
+
+int amt_flac_encode_lpc_ragged(const float *wave, const long long *base, const long long *len, int n, long long max_len,
+                               int blocksize, int bps, long long first_frame, int lpc_order, unsigned char *scratch,
+                               long long scratch_bytes, unsigned char *out, long long out_bytes, long long *frame_bytes,
+                               long long *stream_off, int *frame_minmax, unsigned char *md5, void *stream) {
+    if (lpc_order < 1 || lpc_order > FLL_MAX_ORDER) return AMT_E_INVALID;
+    return fl_encode(wave, base, len, n, max_len, blocksize, bps, first_frame, scratch, scratch_bytes, out, out_bytes,
+                     frame_bytes, stream_off, frame_minmax, md5, stream, lpc_order);
 }
 
 }  // extern "C"

@@ -180,9 +180,23 @@ int amt_flac_encode_ragged(const float *wave, const long long *base, const long 
                            int blocksize, int bps, long long first_frame, unsigned char *scratch,
                            long long scratch_bytes, unsigned char *out, long long out_bytes, long long *frame_bytes,
                            long long *stream_off, int *frame_minmax, unsigned char *md5, void *stream);
+/* audio_to_flac (util_audio.py:966-968) as soundfile writes it, with linear prediction: amt_flac_encode_ragged with one
+ * more family of candidates per block, LPC subframes of order m = 1 .. lpc_order (blocksize > m) after the FIXED orders.
+ * Analysis (csrc/amt_flac_lpc_core.h): a Welch-like integer window, the exact int64 autocorrelation, a
+ * float64 Levinson-Durbin recurrence in one written-out operation order, coefficients of 14 (24 bit) or 12 (16 bit) bits
+ * with a shift in 0 .. 15; bits = 8 + m bps + 4 + 5 + m P + 6 + the residual coding of the fixed orders.  A candidate
+ * replaces the best so far only if strictly smaller (FIXED wins a tie, then the smaller order); an order with a residual
+ * |r| >= 2^27 is no candidate.  So no frame is larger than amt_flac_encode_ragged's for the same block: the frame bound,
+ * the scratch layout and every other argument are that entry's, and so are its errors; in addition AMT_E_INVALID for
+ * lpc_order outside 1 .. 12.  Every byte is defined (tests/flac_lpc_reference.py).  All checks return before any HIP
+ * call.  No packed-FP32 instructions: any stream. */
+int amt_flac_encode_lpc_ragged(const float *wave, const long long *base, const long long *len, int n, long long max_len,
+                               int blocksize, int bps, long long first_frame, int lpc_order, unsigned char *scratch,
+                               long long scratch_bytes, unsigned char *out, long long out_bytes, long long *frame_bytes,
+                               long long *stream_off, int *frame_minmax, unsigned char *md5, void *stream);
 
 /* ------------------------------------------------------------------------ *
- * FLAC decoder  (replaces the librosa.load of audio_from_file, util_audio.py:962-964, for files whose bytes are put
+ * FLAC decoder (replaces the librosa.load of audio_from_file, util_audio.py:962-964, for files whose bytes are put
  * on the device: the front of the song queue)
  *
  * The host parses STREAMINFO and lists the plausible frame headers (amt_saga/flac.py: read_streaminfo,

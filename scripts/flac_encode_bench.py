@@ -1,11 +1,13 @@
 """The device FLAC encoder, measured against the host writer, all from one process.
 
-    python scripts/flac_encode_bench.py [B] [result.json] [host_seconds]
+    python scripts/flac_encode_bench.py [B] [result.json] [host_seconds] [--predictor fixed|lpc|both]
 
 Legs, three repeats each, alternated:
   encode   audio.flac_encode_streams of B signals of 3 .. 6 half windows at N = 2048 (the shape of song_stems_bench.py):
            decaying tones plus noise.  Time per call (all five kernels, MD5 included), samples/s, GB/s on the bytes the
-           call has to move (4 B per sample in, the emitted bytes out).
+           call has to move (4 B per sample in, the emitted bytes out).  --predictor (default fixed) names the
+           predictors of this leg; `both` alternates fixed and lpc calls, the fixed figures under 'encode' as before,
+           the others under 'encode_lpc'.  The other legs use the fixed predictors.
   host     flac.save_float on a `host_seconds` excerpt of the same audio (default 10 s), scaled by length to the whole
            set: the writer is a per-sample loop, its time is proportional to the samples.
   ratio    emitted bytes over the VERBATIM size, per signal class of tests/flac_encode_reference.signals().
@@ -27,6 +29,14 @@ import flac_encode_reference as R
 from amt_saga import audio, flac
 from amt_saga.hyperparams import Hyperparams
 
+predictor = 'fixed'
+if '--predictor' in sys.argv:
+    at = sys.argv.index('--predictor')
+    predictor = sys.argv[at + 1]
+    del sys.argv[at:at + 2]
+if predictor not in ('fixed', 'lpc', 'both'):
+    sys.exit('--predictor: fixed, lpc or both')
+legs = ('fixed', 'lpc') if predictor == 'both' else (predictor,)
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 encode_only = len(sys.argv) > 3 and sys.argv[3] == 'encode_only'
 host_seconds = float(sys.argv[3]) if len(sys.argv) > 3 and not encode_only else 10.0
@@ -63,19 +73,25 @@ def host_time(y):
 lens = rng.integers(3, 7, B) * half * hop
 songs = [tone_noise(int(n), 110.0 * 2 ** (i % 36 / 12), 1e-3) for i, n in enumerate(lens)]
 samples = int(lens.sum())
-audio.flac_encode_streams(songs[:4]); torch.cuda.synchronize()
-enc, host = [], []
+for leg in legs:
+    audio.flac_encode_streams(songs[:4], predictor=leg); torch.cuda.synchronize()
+times, emitted, host = {leg: [] for leg in legs}, {}, []
 y0 = songs[0].cpu().numpy()
 for _ in range(3):
-    ms, res = timed(lambda: audio.flac_encode_streams(songs))
-    emitted = int(res[1][-1])
-    enc.append(ms)
-    del res
+    for leg in legs:
+        ms, res = timed(lambda: audio.flac_encode_streams(songs, predictor=leg))
+        emitted[leg] = int(res[1][-1])
+        times[leg].append(ms)
+        del res
     if not encode_only:
         host.append(host_time(y0))
-out['encode'] = dict(signals=B, samples=samples, seconds_of_audio=samples / sr, ms=enc, emitted_bytes=emitted,
-                     ratio_to_verbatim=emitted / (samples * 3), samples_per_s=samples / (min(enc) * 1e-3),
-                     GBps=(4 * samples + emitted) / (min(enc) * 1e-3) / 1e9)
+for leg in legs:
+    e = emitted[leg]
+    out['encode' if leg == legs[0] else 'encode_' + leg] = dict(
+        predictor=leg, signals=B, samples=samples, seconds_of_audio=samples / sr, ms=times[leg], emitted_bytes=e,
+        ratio_to_verbatim=e / (samples * 3), samples_per_s=samples / (min(times[leg]) * 1e-3),
+        GBps=(4 * samples + e) / (min(times[leg]) * 1e-3) / 1e9)
+enc = times[legs[0]]
 if encode_only:
     print(json.dumps(out))
     sys.exit(0)
@@ -89,6 +105,9 @@ dev = [torch.from_numpy(v).cuda() for v in sig.values()]
 _, off, _, _, _ = audio.flac_encode_streams(dev)
 off = off.cpu().numpy()
 out['ratio_by_class'] = {k: float((off[i + 1] - off[i]) / (len(v) * 3)) for i, (k, v) in enumerate(sig.items())}
+if 'lpc' in legs:
+    off = audio.flac_encode_streams(dev, predictor='lpc')[1].cpu().numpy()
+    out['ratio_by_class_lpc'] = {k: float((off[i + 1] - off[i]) / (len(v) * 3)) for i, (k, v) in enumerate(sig.items())}
 
 # ---- one 5-minute song, three stems -------------------------------------------------------------------------------------
 n = 300 * sr // hop * hop
