@@ -346,7 +346,7 @@ __global__ __launch_bounds__(256) void colreduce_final_kernel(const float *__res
 //   bnf_act_kernel          y = (z - mu) inv gamma + beta [-> sigmoid], plus max |output| per window for the next
 //                           convolution's operand scaling
 //   bnf_bwd_reduce_kernel   sum dy, sum dy zhat with dy = dA a (1 - a) formed on the fly (the sigmoid's gradient)
-//   bnf_bwd_apply_kernel    dz = gamma inv (dy - mean dy - zhat mean(dy zhat)) [+ what is already in the destination],
+//   bnf_bwd_apply_kernel    dz = gamma inv (dy - mean dy - zhat mean(dy zhat)),
 //                           plus per-workgroup column sums of dz (the bias gradient of the convolution in front) and
 //                           max |dz| per window (operand scaling of the data gradient)
 #define BNF_RPT 8
@@ -521,7 +521,7 @@ __global__ __launch_bounds__(256) void bnf_bwd_apply_kernel(const float *__restr
                                                              const float *__restrict__ z, const float *__restrict__ mu,
                                                              const float *__restrict__ inv, const float *__restrict__ gamma,
                                                              const float *__restrict__ sdy, const float *__restrict__ sdyz,
-                                                             float invM, size_t M, int C, int HW, const float *acc, float *dst,
+                                                             float invM, size_t M, int C, int HW, float *dst,
                                                              float *__restrict__ part2, float *__restrict__ gamax) {
     __shared__ float4 red[256];
     __shared__ float lds16[16];
@@ -548,7 +548,6 @@ __global__ __launch_bounds__(256) void bnf_bwd_apply_kernel(const float *__restr
         d.w = g4.w * iv4.w * (dy.w - a4.w * invM - ((v.w - mu4.w) * iv4.w) * (b4.w * invM));
         cs = f4_add(cs, d);
         m[i] = f4_amax(d);
-        if (acc) d = f4_add(d, *reinterpret_cast<const float4 *>(acc + off));
         *reinterpret_cast<float4 *>(dst + off) = d;
     }
     if (part2) {
@@ -1246,14 +1245,17 @@ int bwd_bn(amt_trainer *t, Op &o, const Step &s, const float *gout) {
         const float *a = o.sig_out >= 0 ? t->tensors[o.sig_out].v.p : nullptr;
         bnf_bwd_reduce_kernel<<<nwg, 256, 0, s.st>>>(gout, a, in.v, o.bmu, o.binv, M, o.Cout, t->red0, t->red1);
         colreduce_final_kernel<<<(o.Cout + 31) / 32, 256, 0, s.st>>>(t->red0, t->red1, o.Cout, 1.0f / (float)M, 2, nwg, dbeta, dgamma);
+        // A BatchNormalization's input feeds nothing else: build_tape puts one behind a convolution, behind a shortcut's
+        // Add, or behind the projection / average pool of a shortcut (which has a BatchNormalization of its own only when
+        // it has one of those).  So this is the first gradient to arrive there, and the kernel only writes.
         const float *acc = nullptr;
         float *dst = claim(t, o.in0, &acc);
+        if (acc) return AMT_E_UNSUPPORTED;
         bnf_bwd_apply_kernel<<<nwg, 256, 0, s.st>>>(gout, a, in.v, o.bmu, o.binv, gamma, dbeta, dgamma, 1.0f / (float)M, M, o.Cout,
-                                                    in.H * in.W, acc, dst, t->red2, in.gam_slot);
-        // red2 now holds THIS launch's column partials: valid as the bias gradient of the convolution in front only when
-        // dz was written, not accumulated; any partials another convolution was still waiting for are gone either way
-        if (!acc) { in.gam = in.gam_slot; t->colsum_of = o.in0; t->colsum_nwg = nwg; }
-        else t->colsum_of = -1;
+                                                    in.H * in.W, dst, t->red2, in.gam_slot);
+        // red2 now holds this launch's column partials: the bias gradient of the convolution in front, if there is one
+        // (any partials another convolution was still waiting for are gone)
+        in.gam = in.gam_slot; t->colsum_of = o.in0; t->colsum_nwg = nwg;
         return AMT_OK;
     }
     // generic path: dy -> scratch, two column sums, dz
