@@ -207,7 +207,7 @@ class SoundFont:
 
 def render_windows_device(notes, L, soundfont, sr=44100, out=None):
     """Sample-playback counterpart of synth.render_windows_device: notes rows {MIDI program, pitch, velocity, onset_s,
-    dur_s} (list of note lists or a device float32 [B, M, 5] tensor) -> device float32 [B, L]."""
+    dur_s} (list of note lists or a device float32 [B, M, 5] tensor) -> device float32 [B, L] (`out`, if given: synth.wave_out)."""
     from . import _lib, synth
     from .device import empty, ptr, stream_ptr, to_dev
     lib = _lib.load()
@@ -217,9 +217,9 @@ def render_windows_device(notes, L, soundfont, sr=44100, out=None):
     assert nt.dtype == torch.float32 and nt.shape[-1] == 5 and nt.is_contiguous()
     samples, zones, first = soundfont.device()
     B, M = nt.shape[0], nt.shape[1]
-    wave = out if out is not None else empty((B, int(L)))
+    wave, wave_ptr = synth.wave_out(out, B, L)
     peak = empty((B,))
     _lib.check(lib.amt_sf2_synth_windows(ptr(nt), M, B, int(L), float(sr), ptr(samples), int(samples.shape[0]),
                                          ptr(zones), int(zones.shape[0]), ptr(first), int(first.shape[0]) - 1,
-                                         ptr(wave), wave.stride(0), ptr(peak), stream_ptr()))
+                                         wave_ptr, max(wave.stride(0), int(L)), ptr(peak), stream_ptr()))
     return wave

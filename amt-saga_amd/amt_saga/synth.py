@@ -97,11 +97,42 @@ def notes_tensor(notes, max_notes=None):
 _TIMBRE_DEV = {}
 
 
+def check_host_timbres(timbres):
+    """A caller's host timbre table as contiguous float32 [n, 5]; ValueError for a shape other than [n, 5], a
+    non-finite entry, H < 1 or attack <= 0 (the kernel and oracle/synth.py disagree on such rows: min(t / 0, 1) is 1 on
+    one side and NaN on the other)."""
+    tb = np.ascontiguousarray(timbres, dtype=np.float32)
+    if tb.ndim != 2 or tb.shape[1] != 5:
+        raise ValueError('timbre table must be float32 [n, 5]')
+    if not np.isfinite(tb).all():
+        raise ValueError('timbre table has a non-finite entry')
+    if (tb[:, 0] < 1).any() or (tb[:, 3] <= 0).any():
+        raise ValueError('timbre table rows need H >= 1 and attack > 0')
+    return tb
+
+
+def wave_out(out, B, L):
+    """(wave, device pointer) of a render: a fresh [B, L] tensor, or the caller's `out` -- float32 [B, L] on the device
+    with unit sample stride; its rows may be L or more apart (a view of a wider buffer: the kernels take the row pitch
+    and write nothing beyond column L - 1)."""
+    import ctypes as C
+    from .device import empty
+    if out is None:
+        out = empty((B, int(L)))
+    elif (not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (B, int(L)) or out.stride(1) != 1
+          or (B > 1 and out.stride(0) < int(L))):
+        raise ValueError('out must be a float32 device tensor [%d, %d] with unit sample stride' % (B, int(L)))
+    return out, C.c_void_p(out.data_ptr())
+
+
 def render_windows_device(notes, L, sr=44100, out=None, timbres=None):
     """HIP synthesiser.  notes: list of note lists, or a device float32 [B, M, 5] tensor
     (rows {group, pitch, velocity, onset_s, dur_s}; pitch < 0 = unused).  Returns a device
-    float32 [B, L] tensor.  timbres: None = field 0 is one of the three groups; 'gm' = field 0 is a General MIDI
-    program rendered with gm_timbre_table(); or a float32 [n, 5] table of the caller's."""
+    float32 [B, L] tensor (`out`, if given: see wave_out).  timbres: None = field 0 is one of the three groups;
+    'gm' = field 0 is a General MIDI program rendered with gm_timbre_table(); or a float32 [n, 5] table of the caller's (a host table is checked by
+    check_host_timbres, a device tensor is trusted)."""
+    if timbres is not None and not isinstance(timbres, (str, torch.Tensor)):
+        timbres = check_host_timbres(timbres)
     from . import _lib
     from .device import empty, ptr, stream_ptr, to_dev
     lib = _lib.load()
@@ -110,10 +141,10 @@ def render_windows_device(notes, L, sr=44100, out=None, timbres=None):
         nt = nt[:, None, :]
     assert nt.dtype == torch.float32 and nt.shape[-1] == 5 and nt.is_contiguous()
     B, M = nt.shape[0], nt.shape[1]
-    wave = out if out is not None else empty((B, int(L)))
+    wave, wave_ptr = wave_out(out, B, L)
     peak = empty((B,))
     if timbres is None:
-        _lib.check(lib.amt_synth_windows(ptr(nt), M, B, int(L), float(sr), ptr(wave), wave.stride(0),
+        _lib.check(lib.amt_synth_windows(ptr(nt), M, B, int(L), float(sr), wave_ptr, max(wave.stride(0), int(L)),
                                          ptr(peak), stream_ptr()))
         return wave
     if isinstance(timbres, str):
@@ -126,8 +157,8 @@ def render_windows_device(notes, L, sr=44100, out=None, timbres=None):
         tb = timbres if isinstance(timbres, torch.Tensor) else to_dev(np.ascontiguousarray(timbres, dtype=np.float32))
     if tb.dim() != 2 or tb.shape[1] != 5 or tb.dtype != torch.float32 or not tb.is_contiguous():
         raise ValueError('timbre table must be float32 [n, 5]')
-    _lib.check(lib.amt_synth_windows_timbres(ptr(nt), M, B, int(L), float(sr), ptr(tb), int(tb.shape[0]), ptr(wave),
-                                             wave.stride(0), ptr(peak), stream_ptr()))
+    _lib.check(lib.amt_synth_windows_timbres(ptr(nt), M, B, int(L), float(sr), ptr(tb), int(tb.shape[0]), wave_ptr,
+                                             max(wave.stride(0), int(L)), ptr(peak), stream_ptr()))
     return wave
 
 

@@ -76,6 +76,8 @@ __global__ __launch_bounds__(256) void synth_kernel(const float *__restrict__ no
 // zones [nz][20] f32: key lo, hi, velocity lo, hi, start, end, loop start, loop end (frames in the pool), looped,
 // sample rate, root key, scaleTuning (cents / key), tuning (cents), gain, delay, attack, hold, decay (s), sustain (dB),
 // release (s).  first [n_prog + 1]: program p plays zones first[p] .. first[p + 1] - 1.  One thread per output sample.
+// A note whose program lies outside 0 .. n_prog - 1 plays nothing (as a program without a preset does, oracle/sf2.py);
+// it still counts as a note of its window in the scale law below.
 #define SF2_ZF 20
 __device__ __forceinline__ float sf2_held_amp(float t, const float *z) {       // envelope while the key is down
     const float ta = t - z[14];
@@ -102,7 +104,8 @@ __global__ __launch_bounds__(256) void sf2_synth_kernel(const float *__restrict_
         for (int n = 0; n < max_notes; ++n) {
             const float pitch = nt[n * 5 + 1];
             if (pitch < 0.f) continue;
-            const int prog = min(max((int)nt[n * 5 + 0], 0), n_prog - 1);
+            const int prog = (int)nt[n * 5 + 0];
+            if (prog < 0 || prog >= n_prog) continue;                   // no preset: silent, never a neighbour's zones
             const float vel = nt[n * 5 + 2], onset = nt[n * 5 + 3], dur = nt[n * 5 + 4];
             const double tt = t - (double)onset;
             if (tt < 0.0 || tt >= (double)dur + (double)SYN_TAIL) continue;

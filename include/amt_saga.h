@@ -589,6 +589,8 @@ int amt_synth_windows_timbres(const float *notes, int max_notes, int B, int L, f
  * samples [n_samples] f32 = the font's 16-bit pool / 32768; zones [n_zones][20] f32 and first [n_prog + 1] i32 as
  * amt_saga/sf2.py:SoundFont.tables() lays them out (flattened preset x instrument zones of bank 0: ranges, sample
  * and loop points, tuning, attenuation, volume envelope).  Same amplitude law and 1 s tail as amt_synth_windows.
+ * A note whose program is outside 0 .. n_prog - 1 plays nothing, like a program the font has no preset for (it is
+ * still one of the window's notes for the amplitude law).
  * The zone table is trusted (the host parser validates offsets against the pool). */
 int amt_sf2_synth_windows(const float *notes, int max_notes, int B, int L, float sample_rate, const float *samples,
                           int n_samples, const float *zones, int n_zones, const int32_t *first, int n_prog,

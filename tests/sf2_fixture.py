@@ -15,6 +15,18 @@ Content (what the tests assert the reader recovers):
             program 24 'Pluck'  -> PluckInst, preset-level attenuation +2 dB, fineTune -5
             program 40 'Layer'  global zone (coarseTune +12); SineInst limited to keys 40-80 + SquareInst (layered)
             bank 128 program 0 'Drums' -> PluckInst (ignored by the reader: bank != 0)
+
+build(extra=True) appends, leaving everything above as it is (build() itself stays byte-identical), what the synthesiser's
+envelope and loop edges need (tests/synth_reference.py):
+  samples   3 'sineloop' 32000 Hz, 925 frames of a sine of 100 frames per period, loop = frames 225 .. 925: the loop ends
+                         where the sample ends, so the frame after it is the zero padding, not a continuation of the loop
+                         (an interpolation that reads past the loop end instead of wrapping is audible), root 60
+  instruments 3 'DelayHoldInst' sineloop looped, delay 50 ms, attack 30 ms, hold 40 ms, decay 1 s, sustain 20 dB, release 0.1 s
+              4 'DecaySusInst'  square looped, root key 72, attack 10 ms, decay 0.5 s to sustain 10 dB (reached 50 ms
+                                into the decay), release 0.15 s
+              5 'LongRelInst'   sineloop looped, release 4 s (25 dB down, still audible, when the 1 s tail is cut)
+              6 'ShotInst'      square NOT looped (0.2 s at its root), root key 72, release 0.3 s
+  presets   program 8 'DelayHold', 16 'DecaySus', 32 'LongRel', 48 'Shot' -> those instruments
 """
 import struct
 
@@ -39,7 +51,7 @@ def _gen(name, amount):
         struct.pack('<HH', GEN[name], amount)
 
 
-def build():
+def build(extra=False):
     sr0, sr1, sr2 = 22050, 44100, 32000
     n0 = np.arange(sr0)
     s0 = 0.8 * np.sin(2 * np.pi * 441.0 * n0 / sr0)
@@ -48,9 +60,12 @@ def build():
     n2 = np.arange(6400)
     s2 = sum(np.sin(2 * np.pi * 500.0 * h * n2 / sr2) / h for h in (1, 3, 5, 7)) * 0.5
     pool, hdrs, off = [], [], 0
-    for name, s, rate, pitch, corr, loop in (('sine441', s0, sr0, 69, 0, (2000, 2000 + 50 * 300)),
-                                             ('pluck', s1, sr1, 57, 5, (0, 0)),
-                                             ('square', s2, sr2, 71, 0, (640, 640 + 64 * 50))):
+    sample_list = [('sine441', s0, sr0, 69, 0, (2000, 2000 + 50 * 300)),
+                   ('pluck', s1, sr1, 57, 5, (0, 0)),
+                   ('square', s2, sr2, 71, 0, (640, 640 + 64 * 50))]
+    if extra:
+        sample_list.append(('sineloop', 0.8 * np.sin(2 * np.pi * np.arange(925) / 100.0), 32000, 60, 0, (225, 925)))
+    for name, s, rate, pitch, corr, loop in sample_list:
         q = np.clip(np.round(s * 32767), -32768, 32767).astype('<i2')
         pool.append(q)
         pool.append(np.zeros(46, '<i2'))                       # the 46 zero frames the format asks for after a sample
@@ -76,6 +91,17 @@ def build():
         ('Layer', 40, 0, [[('coarseTune', 12)], [('keyRange', (40, 80)), ('instrument', 0)], [('instrument', 2)]]),
         ('Drums', 0, 128, [[('instrument', 1)]]),
     ]
+    if extra:
+        insts += [
+            ('DelayHoldInst', [[('delay', tc(0.05)), ('attack', tc(0.03)), ('hold', tc(0.04)), ('decay', tc(1.0)),
+                                ('sustain', 200), ('release', tc(0.1)), ('sampleModes', 1), ('sampleID', 3)]]),
+            ('DecaySusInst', [[('rootKey', 72), ('attack', tc(0.01)), ('decay', tc(0.5)), ('sustain', 100),
+                               ('release', tc(0.15)), ('sampleModes', 1), ('sampleID', 2)]]),
+            ('LongRelInst', [[('release', tc(4.0)), ('sampleModes', 1), ('sampleID', 3)]]),
+            ('ShotInst', [[('rootKey', 72), ('release', tc(0.3)), ('sampleID', 2)]]),
+        ]
+        presets += [('DelayHold', 8, 0, [[('instrument', 3)]]), ('DecaySus', 16, 0, [[('instrument', 4)]]),
+                    ('LongRel', 32, 0, [[('instrument', 5)]]), ('Shot', 48, 0, [[('instrument', 6)]])]
 
     def pack(groups, hdr_fmt, hdr_of):
         hdr, bag, gen = b'', b'', b''

@@ -12,16 +12,22 @@ REL = 1e-4
 RATIOS = []          # (head, mode, e_gpu, e_cpu): distance of the GPU / CPU float32 results from the float64 oracle
 
 
-@pytest.fixture(scope='module', autouse=True)
-def _dump_ratios():
-    yield
+def dump_records(name, records):
+    """Write a test module's measured errors as JSON into the run's output directory beside the tree (the figures
+    DESIGN.md quotes); best effort.  Shared with test_gpu_synth_geometry.py."""
     out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'gpurun_out')
     try:
         os.makedirs(out, exist_ok=True)
-        with open(os.path.join(out, 'rdcnn_error_vs_f64.json'), 'w') as f:
-            json.dump(RATIOS, f, indent=1)
+        with open(os.path.join(out, name), 'w') as f:
+            json.dump(records, f, indent=1)
     except OSError:
         pass
+
+
+@pytest.fixture(scope='module', autouse=True)
+def _dump_ratios():
+    yield
+    dump_records('rdcnn_error_vs_f64.json', RATIOS)
     for r in RATIOS:
         print('e_gpu/e_cpu  %-34s mode %d  gpu %.3g  cpu %.3g  ratio %.2f' %
               (r['head'], r['mode'], r['e_gpu'], r['e_cpu'], r['e_gpu'] / max(r['e_cpu'], 1e-30)))
