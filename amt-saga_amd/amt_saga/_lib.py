@@ -34,16 +34,27 @@ class StemArgs(C.Structure):
                 ('n_prog', C.c_int32), ('G', C.c_int32), ('pool_frames', C.c_int64)]
 
 
-def stem_args(**fields):
-    """StemArgs (amt_stem_args of amt_subtract_span_stems) from keyword arguments: a tensor gives its device pointer,
-    None a NULL, a number itself."""
-    a = StemArgs()
-    known = {name for name, _ in StemArgs._fields_}
+def args(struct_type, **fields):
+    """A struct_type filled from keyword arguments: a tensor gives its device pointer, None a NULL, a number itself; an
+    array field takes a sequence entry by entry (missing entries stay zero / NULL).  A name the struct does not have
+    raises ValueError."""
+    a = struct_type()
+    types = dict(struct_type._fields_)
     for k, v in fields.items():
-        if k not in known:
+        if k not in types:
             raise ValueError('Requested attribute does not exist')
-        setattr(a, k, v.data_ptr() if hasattr(v, 'data_ptr') else v)
+        if issubclass(types[k], C.Array):
+            arr = getattr(a, k)
+            for i, t in enumerate(v):
+                arr[i] = t.data_ptr() if hasattr(t, 'data_ptr') else t
+        else:
+            setattr(a, k, v.data_ptr() if hasattr(v, 'data_ptr') else v)
     return a
+
+
+def stem_args(**fields):
+    """StemArgs (amt_stem_args of amt_subtract_span_stems)."""
+    return args(StemArgs, **fields)
 
 
 class CqtArgs(C.Structure):
@@ -73,20 +84,8 @@ class SongAdmitArgs(C.Structure):
 
 
 def song_admit_args(**fields):
-    """SongAdmitArgs from keyword arguments: a tensor gives its device pointer, None a NULL, a number itself; new_ref /
-    ref take sequences of up to four tensors (missing entries are NULL)."""
-    a = SongAdmitArgs()
-    known = {name for name, _ in SongAdmitArgs._fields_}
-    for k, v in fields.items():
-        if k not in known:
-            raise ValueError('Requested attribute does not exist')
-        if k in ('new_ref', 'ref'):
-            arr = getattr(a, k)
-            for i, t in enumerate(v):
-                arr[i] = t.data_ptr() if t is not None else None
-        else:
-            setattr(a, k, v.data_ptr() if hasattr(v, 'data_ptr') else v)
-    return a
+    """SongAdmitArgs; new_ref / ref take sequences of up to four tensors."""
+    return args(SongAdmitArgs, **fields)
 
 
 # name -> (restype, argtypes); every symbol include/amt_saga.h declares

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib, flac as _flac, wav as _wav
-from .device import empty, ptr, require_gpu, stream_ptr, to_dev, zeros
+from .device import empty, per_device, ptr, require_gpu, stream_ptr, to_dev, zeros
 
 _PLANS = {}
 
@@ -27,14 +27,13 @@ def _stride0(t):
 
 
 def _plan(n_fft, hop, center):
-    key = (int(n_fft), int(hop), bool(center), torch.cuda.current_device())
-    if key not in _PLANS:
+    def build():
         lib = _lib.load()
         require_gpu()
         h = C.c_void_p()
         _lib.check(lib.amt_stft_plan_create(C.byref(h), int(n_fft), int(hop), int(bool(center))))
-        _PLANS[key] = h
-    return _PLANS[key]
+        return h
+    return per_device(_PLANS, (int(n_fft), int(hop), bool(center)), build)
 
 
 # Row pitch of the spectrograms in floats.  AMT_LDF_ALIGN=32 (128-byte rows) is a measured experiment, not a supported
@@ -94,10 +93,7 @@ _DEV_TABLES = {}
 def _dev_table(key, build):
     """Small constant index tables live on the device once: a pageable host-to-device copy
     inside the loop would drain the stream on every call."""
-    t = _DEV_TABLES.get(key)
-    if t is None:
-        t = _DEV_TABLES[key] = to_dev(build(), torch.int32)
-    return t
+    return per_device(_DEV_TABLES, key, lambda: to_dev(build(), torch.int32))
 
 
 class AudioBatch:
@@ -175,27 +171,15 @@ class AudioBatch:
         if stems is not None and not (span and relu):
             raise ValueError('subtract: stems need the span subtraction (span=True, relu=True)')
         B, T = self.mag.shape[0], self.mag.shape[1]
-        a = _lib.SubtractArgs()
         new_max = empty((B,))
-        a.resid = self.mag.data_ptr()
-        a.resid_max = self.ref_max.data_ptr() if normalize else None
-        a.guess = guess_mag.data_ptr()
-        a.guess_max = guess_max.data_ptr() if (normalize and guess_max is not None) else None
-        a.guess_index = guess_index.data_ptr() if guess_index is not None else None
-        if isinstance(guess_frames, torch.Tensor):
-            a.guess_frames = guess_frames.data_ptr()
-            a.guess_frames_all = 0
-        else:
-            a.guess_frames = None
-            a.guess_frames_all = int(guess_mag.shape[1] if guess_frames is None else guess_frames)
-        a.offset_frames = offset_frames.data_ptr() if offset_frames is not None else None
-        a.new_max = new_max.data_ptr()
-        a.resid_stride = T * self.ldf
-        a.guess_stride = _stride0(guess_mag)
-        a.B, a.T, a.ldf, a.F = B, T, self.ldf, self.F
-        a.normalize = int(bool(normalize))
-        a.relu = int(bool(relu))
-        a.overkill_factor = float(overkill_factor)
+        per_window = isinstance(guess_frames, torch.Tensor)         # else one frame count for every window
+        a = _lib.args(_lib.SubtractArgs, resid=self.mag, resid_max=self.ref_max if normalize else None, guess=guess_mag,
+                      guess_max=guess_max if normalize else None, guess_index=guess_index,
+                      guess_frames=guess_frames if per_window else None,
+                      guess_frames_all=0 if per_window else int(guess_mag.shape[1] if guess_frames is None else guess_frames),
+                      offset_frames=offset_frames, new_max=new_max, resid_stride=T * self.ldf,
+                      guess_stride=_stride0(guess_mag), B=B, T=T, ldf=self.ldf, F=self.F, normalize=int(bool(normalize)),
+                      relu=int(bool(relu)), overkill_factor=float(overkill_factor))
         fm = self._fmax
         # the cached maxima describe `mag` only while it is the same tensor AND unedited since (the key holds its address
         # and torch's in-place version counter; the kernels behind this class write through raw pointers, which the counter
@@ -305,18 +289,9 @@ def cqt_slices(wave, src_frame, table, n_bins, hop, bin0=None, ref=None, complex
     B, L = wave.shape
     frames = src_frame.shape[1]
     out = empty((B, n_bins, frames))
-    a = _lib.CqtArgs()
-    a.wave = wave.data_ptr()
-    a.src_frame = src_frame.data_ptr()
-    a.bin0 = bin0.data_ptr() if bin0 is not None else None
-    a.phase_inc = table[0].data_ptr()
-    a.length = table[1].data_ptr()
-    a.ref = ref.data_ptr() if ref is not None else None
-    a.coef = table[2].data_ptr()
-    a.out = out.data_ptr()
-    a.wave_stride = _stride0(wave)
-    a.B, a.L, a.hop, a.frames, a.n_bins, a.n_table = B, L, int(hop), frames, int(n_bins), \
-        int(table[0].shape[0])
+    a = _lib.args(_lib.CqtArgs, wave=wave, src_frame=src_frame, bin0=bin0, phase_inc=table[0], length=table[1], ref=ref,
+                  coef=table[2], out=out, wave_stride=_stride0(wave), B=B, L=L, hop=int(hop), frames=frames,
+                  n_bins=int(n_bins), n_table=int(table[0].shape[0]))
     if complex_out:
         out_im = empty((B, n_bins, frames))
         _lib.check(lib.amt_cqt_slices_complex(C.byref(a), ptr(out_im), stream_ptr()))
@@ -952,19 +927,18 @@ class Resampler:
             raise ValueError('Resampler: %d -> %d reduces to %d / %d; the larger side may be at most %d'
                              % (self.sr_in, self.sr_out, self.L, self.M, self.R_MAX))
         self.taps = 2 * self.Z * R // self.L + 1
-        self._handles = {}                                          # device index -> amt_resampler *
+        self._handles = {}                                          # (device index,) -> amt_resampler *
 
     def out_len(self, n_in):
         """ceil(n_in L / M) (amt_resample_length)."""
         return -((-int(n_in) * self.L) // self.M)
 
     def _handle(self):
-        dev = torch.cuda.current_device()
-        if dev not in self._handles:
+        def build():
             h = C.c_void_p()
             _lib.check(_lib.load().amt_resampler_create(C.byref(h), self.sr_in, self.sr_out))
-            self._handles[dev] = h
-        return self._handles[dev]
+            return h
+        return per_device(self._handles, (), build)
 
     def __del__(self):
         try:

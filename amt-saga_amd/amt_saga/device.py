@@ -12,6 +12,15 @@ def require_gpu():
     return torch.device('cuda', torch.cuda.current_device())
 
 
+def per_device(store, key, build):
+    """store[(current device index,) + key], built on a miss: what lives on a device (a plan, a table, a handle) is
+    cached per device."""
+    k = (torch.cuda.current_device(),) + tuple(key)
+    if k not in store:
+        store[k] = build()
+    return store[k]
+
+
 def stream_ptr():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 

@@ -12,6 +12,7 @@
 // H-sample blocks and every frame is a difference of two prefix sums of block sums plus one block head.
 // VALU / L1-bound; no MFMA.
 #include "amt_common.h"
+#include "amt_launch.h"
 #include <cstdlib>
 
 #define AMT_CQT_MAXF 8
@@ -798,15 +799,16 @@ __global__ __launch_bounds__(256) void cqt_slices_direct_kernel(amt_cqt_args a, 
     }
 }
 
-static int cqt_blocks_geometry(int L, int hop, int *hshift, int *blk_cap, size_t *lds) {
-    if (!amt_is_pow2(hop) || hop < 128 || hop > 2048) return AMT_E_UNSUPPORTED;
-    *hshift = 0;
-    while ((1 << *hshift) < hop) ++*hshift;
+// AMT_E_UNSUPPORTED: hop is no power of two in 128..2048.  Else AMT_OK, and *in_lds says whether the block sums of a
+// signal of L samples fit the LDS (*lds bytes) or go to an HBM workspace.
+static int cqt_blocks_geometry(int L, int hop, int *hshift, int *blk_cap, size_t *lds, bool *in_lds) {
+    if (!amt_hop_shift(hop, 128, 2048, hshift)) return AMT_E_UNSUPPORTED;
     *blk_cap = L / hop + 3;                          // blocks that can hold samples, whatever the filter length
     const size_t stage_floats = (size_t)4 * CM_STAGE > (size_t)(*blk_cap + 1) * 12 ? (size_t)4 * CM_STAGE
                                                                                     : (size_t)(*blk_cap + 1) * 12;
     *lds = (stage_floats + (size_t)*blk_cap * 12) * sizeof(float);
-    return *lds > 159 * 1024 ? AMT_E_UNSUPPORTED : AMT_OK;
+    *in_lds = *lds <= AMT_LDS_CQT;
+    return AMT_OK;
 }
 
 extern "C" int amt_cqt_coef(const uint32_t *phase_inc, const int32_t *length, int n_table, float *coef, void *stream) {
@@ -830,35 +832,27 @@ static int cqt_slices_impl(const amt_cqt_args *args, float *out_im, void *stream
     if (q.frames <= 0 || q.frames > AMT_CQT_MAXF) return AMT_E_UNSUPPORTED;
     if (q.wave_stride < (size_t)q.L) return AMT_E_SHAPE;
     CqtBlocksArgs a{};
-    size_t lds;
-    if (cqt_blocks_geometry(q.L, q.hop, &a.hshift, &a.blk_cap, &lds) != AMT_OK) {
+    size_t lds; bool in_lds;
+    if (cqt_blocks_geometry(q.L, q.hop, &a.hshift, &a.blk_cap, &lds, &in_lds) != AMT_OK || !in_lds) {
         // hop not a power of two in 128..2048, or more hop-blocks than the LDS holds: the direct form
         cqt_slices_direct_kernel<<<dim3(q.n_bins, q.B), 256, 0, (hipStream_t)stream>>>(q, out_im);
         AMT_LAUNCH_CHECK();
         return AMT_OK;
     }
     if (!q.coef) return AMT_E_INVALID;
-    static bool attr_set = false;
-    if (!attr_set) {
-        AMT_HIP_CHECK(hipFuncSetAttribute((const void *)cqt_blocks_kernel<true, false>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-        attr_set = true;
-    }
     a.wave_stride = q.wave_stride; a.L = q.L; a.H = q.hop; a.T = 1 + q.L / q.hop;
     a.src_frame = q.src_frame; a.bin0 = q.bin0; a.ref = q.ref; a.out = q.out; a.out_im = out_im;
     a.frames = q.frames; a.n_bins = q.n_bins; a.n_table = q.n_table;
-    cqt_blocks_kernel<true, false><<<dim3(q.n_bins, q.B), 256, lds, (hipStream_t)stream>>>(q.wave, q.phase_inc, q.length,
-                                                                                     q.coef, a);
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
+    return amt_launch<cqt_blocks_kernel<true, false>>(AMT_LDS_CQT, dim3(q.n_bins, q.B), 256, lds, (hipStream_t)stream, q.wave,
+                                                      q.phase_inc, q.length, q.coef, a);
 }
 
 // bytes of HBM workspace amt_cqt_window_max needs for (L, hop, n_bins, B): 0 while the block sums fit the LDS
 extern "C" size_t amt_cqt_window_max_workspace(int L, int hop, int n_bins, int B) {
     int hshift, blk_cap;
-    size_t lds;
+    size_t lds; bool in_lds;
     if (L <= 0 || hop <= 0 || n_bins <= 0 || B <= 0) return 0;
-    if (cqt_blocks_geometry(L, hop, &hshift, &blk_cap, &lds) == AMT_OK) return 0;
+    if (cqt_blocks_geometry(L, hop, &hshift, &blk_cap, &lds, &in_lds) != AMT_OK || in_lds) return 0;   // (no workspace makes a hop supported)
     return (size_t)n_bins * B * ((size_t)blk_cap * 12 * sizeof(float) + ((size_t)blk_cap + 1) * 6 * sizeof(double));
 }
 
@@ -868,40 +862,28 @@ extern "C" int amt_cqt_window_max(const float *wave, int B, int L, size_t wave_s
     if (!wave || !phase_inc || !length || !coef || !out_max) return AMT_E_INVALID;
     if (B <= 0 || L <= 0 || n_bins <= 0) return AMT_E_INVALID;
     if (wave_stride < (size_t)L) return AMT_E_SHAPE;
-    if (!amt_is_pow2(hop) || hop < 128 || hop > 2048) return AMT_E_UNSUPPORTED;
     CqtBlocksArgs a{};
-    size_t lds;
-    const bool in_lds = cqt_blocks_geometry(L, hop, &a.hshift, &a.blk_cap, &lds) == AMT_OK;
+    size_t lds; bool in_lds;
+    if (cqt_blocks_geometry(L, hop, &a.hshift, &a.blk_cap, &lds, &in_lds) != AMT_OK) return AMT_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     AMT_HIP_CHECK(hipMemsetAsync(out_max, 0, (size_t)B * sizeof(float), st));
     a.wave_stride = wave_stride; a.L = L; a.H = hop; a.T = 1 + L / hop;
     a.out_max = (unsigned int *)out_max;
-    if (in_lds) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            AMT_HIP_CHECK(hipFuncSetAttribute((const void *)cqt_blocks_kernel<false, false>,
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-            attr_set = true;
-        }
-        cqt_blocks_kernel<false, false><<<dim3(n_bins, B), 256, lds, st>>>(wave, phase_inc, length, coef, a);
-    } else {
-        // a signal of more hop-blocks than the LDS holds (a whole song): block sums in the caller's HBM workspace
-        const size_t need = amt_cqt_window_max_workspace(L, hop, n_bins, B);
-        if (!workspace || workspace_bytes < need) return AMT_E_NOMEM;
-        a.pf_ws = (double *)workspace;               // doubles first: 8-byte aligned whatever blk_cap is
-        a.fg_ws = (float *)(a.pf_ws + (size_t)n_bins * B * ((size_t)a.blk_cap + 1) * 6);
-        cqt_blocks_kernel<false, true><<<dim3(n_bins, B), 256, 4 * CM_STAGE * sizeof(float), st>>>(wave, phase_inc, length,
-                                                                                                   coef, a);
-    }
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
+    if (in_lds) return amt_launch<cqt_blocks_kernel<false, false>>(AMT_LDS_CQT, dim3(n_bins, B), 256, lds, st, wave, phase_inc, length, coef, a);
+    // a signal of more hop-blocks than the LDS holds (a whole song): block sums in the caller's HBM workspace
+    const size_t need = amt_cqt_window_max_workspace(L, hop, n_bins, B);
+    if (!workspace || workspace_bytes < need) return AMT_E_NOMEM;
+    a.pf_ws = (double *)workspace;               // doubles first: 8-byte aligned whatever blk_cap is
+    a.fg_ws = (float *)(a.pf_ws + (size_t)n_bins * B * ((size_t)a.blk_cap + 1) * 6);
+    return amt_launch<cqt_blocks_kernel<false, true>>(0, dim3(n_bins, B), 256, 4 * CM_STAGE * sizeof(float), st, wave, phase_inc,
+                                                      length, coef, a);
 }
 
 // ---- MFMA form: geometry, table, launch ---------------------------------------------------------------------------
+// the hops the MFMA form takes, here and nowhere else
+static int cqm_hop_shift(int hop, int *hshift) { return amt_hop_shift(hop, 256, 2048, hshift) ? AMT_OK : AMT_E_UNSUPPORTED; }
 static int cqm_geometry(int L, int hop, int *hshift, int *nblk, int *q, int *r) {
-    if (!amt_is_pow2(hop) || hop < 256 || hop > 2048) return AMT_E_UNSUPPORTED;
-    *hshift = 0;
-    while ((1 << *hshift) < hop) ++*hshift;
+    if (cqm_hop_shift(hop, hshift) != AMT_OK) return AMT_E_UNSUPPORTED;
     *nblk = (L + hop - 1) / hop;
     const int n_mt = (*nblk + 15) / 16;
     *q = n_mt / 8; *r = n_mt % 8;
@@ -911,7 +893,8 @@ static int cqm_geometry(int L, int hop, int *hshift, int *nblk, int *q, int *r) 
 }
 
 extern "C" size_t amt_cqt_mfma_table_bytes(int hop, int n_bins) {
-    if (!amt_is_pow2(hop) || hop < 256 || hop > 2048 || n_bins <= 0) return 0;
+    int hshift;
+    if (cqm_hop_shift(hop, &hshift) != AMT_OK || n_bins <= 0) return 0;
     const size_t groups = (size_t)(n_bins + CQM_BINS - 1) / CQM_BINS;
     return groups * (size_t)(hop >> 5) * (2 * 128 * 32) * sizeof(_Float16);
 }
@@ -919,17 +902,19 @@ extern "C" size_t amt_cqt_mfma_table_bytes(int hop, int n_bins) {
 extern "C" int amt_cqt_mfma_table(const uint32_t *phase_inc, const int32_t *length, int n_bins, int hop, void *table,
                                   void *stream) {
     if (!phase_inc || !length || !table || n_bins <= 0) return AMT_E_INVALID;
-    const size_t bytes = amt_cqt_mfma_table_bytes(hop, n_bins);
-    if (!bytes) return AMT_E_UNSUPPORTED;
-    int hshift = 0;
-    while ((1 << hshift) < hop) ++hshift;
-    const size_t n_total = bytes / sizeof(_Float16) / 2;       // one thread per (h, l) pair
+    int hshift;
+    if (cqm_hop_shift(hop, &hshift) != AMT_OK) return AMT_E_UNSUPPORTED;
+    const size_t n_total = amt_cqt_mfma_table_bytes(hop, n_bins) / sizeof(_Float16) / 2;       // one thread per (h, l) pair
     cqt_mfma_table_kernel<<<(unsigned)((n_total + 255) / 256), 256, 0, (hipStream_t)stream>>>(
         phase_inc, length, n_bins, hop, hshift, (_Float16 *)table, n_total);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }
 
+// (full 8-tile groups per wave, remaining tiles) the MFMA kernel is instantiated for: what cqm_geometry can return
+using CqmShapes = amt_cases<amt_case<0, 1>, amt_case<0, 2>, amt_case<1, 0>, amt_case<1, 1>, amt_case<1, 2>, amt_case<2, 0>,
+                            amt_case<2, 1>, amt_case<2, 2>, amt_case<3, 0>, amt_case<3, 1>, amt_case<3, 2>, amt_case<4, 0>,
+                            amt_case<4, 1>, amt_case<4, 2>>;
 extern "C" int amt_cqt_window_max_mfma(const float *wave, int B, int L, size_t wave_stride, int hop,
                                        const uint32_t *phase_inc, const int32_t *length, const void *table, int n_bins,
                                        float *out_max, float *amax_scratch, void *stream) {
@@ -943,18 +928,6 @@ extern "C" int amt_cqt_window_max_mfma(const float *wave, int B, int L, size_t w
     const size_t nrow = 16 * (size_t)(8 * a.q + a.r);
     const size_t lds_epi = 2 * (((nrow * 18 * 4 + 15) & ~(size_t)15) + ((((size_t)a.nblk + 1) * 6 * sizeof(double) + 15) & ~(size_t)15));
     const size_t lds = lds_ops > lds_epi ? lds_ops : lds_epi;
-    void (*kern)(CqmArgs) = nullptr;
-    switch (a.q * 3 + a.r) {
-#define CQM_CASE(Q_, R_) case Q_ * 3 + R_: kern = cqt_max_mfma_kernel<Q_, R_>; break;
-        CQM_CASE(0, 1) CQM_CASE(0, 2)
-        CQM_CASE(1, 0) CQM_CASE(1, 1) CQM_CASE(1, 2) CQM_CASE(2, 0) CQM_CASE(2, 1) CQM_CASE(2, 2)
-        CQM_CASE(3, 0) CQM_CASE(3, 1) CQM_CASE(3, 2) CQM_CASE(4, 0) CQM_CASE(4, 1) CQM_CASE(4, 2)
-#undef CQM_CASE
-        default: return AMT_E_UNSUPPORTED;
-    }
-    AMT_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-    AMT_HIP_CHECK(hipMemsetAsync(out_max, 0, (size_t)B * sizeof(float), st));
-    cqt_amax_kernel<<<B, 256, 0, st>>>(wave, wave_stride, L, amax_scratch);
     a.wave = wave; a.wave_stride = wave_stride; a.phase_inc = phase_inc; a.length = length;
     a.table = (const _Float16 *)table; a.amax = amax_scratch; a.out_max = (unsigned int *)out_max;
     a.L = L; a.H = hop; a.T = 1 + L / hop; a.n_bins = n_bins; a.KS = hop >> 5;
@@ -963,7 +936,9 @@ extern "C" int amt_cqt_window_max_mfma(const float *wave, int B, int L, size_t w
     { const char *e = getenv("AMT_CQM_DEBUG"); a.debug = e ? atoi(e) : 0; }
 #endif
     const int groups = (n_bins + CQM_BINS - 1) / CQM_BINS;
-    kern<<<dim3(groups, B), 512, lds, st>>>(a);
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
+    return amt_dispatch(CqmShapes{}, a.q, a.r, [&](auto Q, auto R) -> int {
+        AMT_HIP_CHECK(hipMemsetAsync(out_max, 0, (size_t)B * sizeof(float), st));
+        cqt_amax_kernel<<<B, 256, 0, st>>>(wave, wave_stride, L, amax_scratch);
+        return amt_launch<cqt_max_mfma_kernel<Q(), R()>>(AMT_LDS_CQT, dim3(groups, B), 512, lds, st, a);
+    });
 }

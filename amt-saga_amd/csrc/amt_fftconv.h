@@ -1,6 +1,7 @@
 // Internal interface of the FFT-domain convolution form (amt_fftconv.hip), used by amt_rdcnn.hip (conv mode 3).
 #pragma once
 #include "amt_common.h"
+#include "amt_launch.h"
 
 struct amt_fftconv_layer;
 
@@ -12,6 +13,26 @@ struct FcEpilogue {
     // W-pooled pair in place of the spatial output (either form; identity shortcut, no next transform): wmax / wavg
     // [B][H][W / 8][C] = max / mean of the output's columns 8 g .. 8 g + 7 (EPI = 5 of both row kernels); out_sp is then null
     float *wmax = nullptr, *wavg = nullptr; size_t wp_stride = 0;
+};
+
+// Device copies of a layer's folded BN vectors for the stand-alone entries (amt_fftconv_create, amt_fftpk_create): s1 / t1
+// always, s2 / t2 (the BN after the shortcut add) where given (host [channels], null = absent; release() also frees what a
+// failed upload left); a shortcut passed to a layer without them is ignored.
+struct FcBnCopies {
+    float *s1 = nullptr, *t1 = nullptr, *s2 = nullptr, *t2 = nullptr;
+    hipError_t upload(const float *hs1, const float *ht1, const float *hs2, const float *ht2, int channels) {
+        const float *h[4] = {hs1, ht1, hs2, ht2};
+        float **d[4] = {&s1, &t1, &s2, &t2};
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < 4 && e == hipSuccess; ++i) {
+            if (h[i]) e = hipMalloc(d[i], channels * sizeof(float));
+            if (h[i] && e == hipSuccess) e = hipMemcpy(*d[i], h[i], channels * sizeof(float), hipMemcpyHostToDevice);
+        }
+        return e;
+    }
+    void release() {
+        for (float **p : {&s1, &t1, &s2, &t2}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    }
 };
 
 // kernel: host [4][16][32][32] (Keras layout kh, kw, cin, cout)

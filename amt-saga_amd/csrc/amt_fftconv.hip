@@ -471,7 +471,7 @@ struct amt_fftconv_layer {
     _Float16 *gw = nullptr;
     int *gsw = nullptr;
     float2 *tw = nullptr;
-    float *s1 = nullptr, *t1 = nullptr, *s2 = nullptr, *t2 = nullptr;      // optional device copies (stand-alone entry)
+    FcBnCopies bn;                     // stand-alone entry only
 };
 
 static inline unsigned short fc_f16_bits(_Float16 h) { unsigned short b; memcpy(&b, &h, 2); return b; }
@@ -570,8 +570,9 @@ int amt_fftconv_layer_create_internal(amt_fftconv_layer **out, const float *kern
 
 void amt_fftconv_layer_destroy_internal(amt_fftconv_layer *L) {
     if (!L) return;
-    for (void *p : {(void *)L->gw, (void *)L->gsw, (void *)L->tw, (void *)L->s1, (void *)L->t1, (void *)L->s2, (void *)L->t2})
+    for (void *p : {(void *)L->gw, (void *)L->gsw, (void *)L->tw})
         if (p) (void)hipFree(p);
+    L->bn.release();
     delete L;
 }
 
@@ -584,14 +585,7 @@ static void fc_strides(int H, int *sf, int *sh) { *sf = H * 64; *sh = 64; }
 static const size_t FC_ROW_LDS = (size_t)(16 * FC_PS) * 4 + FC_NF * sizeof(float2);
 template <bool IN_FREQ, int EPI>
 static int fc_row_launch_t(const FcRowArgs &a, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        AMT_HIP_CHECK(hipFuncSetAttribute((const void *)fc_row_kernel<IN_FREQ, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FC_ROW_LDS));
-        attr = true;
-    }
-    fc_row_kernel<IN_FREQ, EPI><<<a.B * a.H, FC_THREADS, FC_ROW_LDS, st>>>(a);
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
+    return amt_launch<fc_row_kernel<IN_FREQ, EPI>>(FC_ROW_LDS, a.B * a.H, FC_THREADS, FC_ROW_LDS, st, a);
 }
 template <bool IN_FREQ>
 static int fc_row_launch(const FcRowArgs &a, hipStream_t st) {
@@ -625,19 +619,12 @@ int amt_fftconv_gemm(const amt_fftconv_layer *L, const float *Xf, const float *a
     const size_t rows_cap = (size_t)FC_CW * H;
     const size_t lds = 2 * (rows_cap + 1) * FC_APITCH * sizeof(_Float16) + (size_t)4 * 16 * FC_OPITCH * 4 + 2 * FC_CW * 4 + rows_cap * 4 +
                        2 * rows_cap + 16;
-    static size_t attr = 0;
-    if (lds > attr) {
-        AMT_HIP_CHECK(hipFuncSetAttribute((const void *)fc_gemm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = lds;
-    }
     const int nchunks = (B + FC_CW - 1) / FC_CW;
     int per = 1;
     while ((size_t)((nchunks + per - 1) / per) * FC_NP > 4096 && per < 16) per *= 2;      // ~2 resident rounds of workgroups
     FcGemmArgs a{Xf, Yf, amaxf, L->gw, L->gsw, B, H, per, 0, 0};
     fc_strides(H, &a.sf, &a.sh);
-    fc_gemm_kernel<<<dim3(FC_NP, (nchunks + per - 1) / per), 256, lds, st>>>(a);
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
+    return amt_launch<fc_gemm_kernel>(lds, dim3(FC_NP, (nchunks + per - 1) / per), 256, lds, st, a);     // (the limit grows with H)
 }
 
 int amt_fftconv_inverse_epilogue(const amt_fftconv_layer *L, const float *Yf, const FcEpilogue &ep, int B, int H, int W,
@@ -664,18 +651,7 @@ int amt_fftconv_create(amt_fftconv_layer **layer, const float *kernel_host, cons
     if (!layer || !kernel_host || !s1 || !t1) return AMT_E_INVALID;
     int rc = amt_fftconv_layer_create_internal(layer, kernel_host);
     if (rc != AMT_OK) return rc;
-    amt_fftconv_layer *L = *layer;
-    auto up = [&](const float *h, float **d) -> hipError_t {
-        if (!h) return hipSuccess;
-        hipError_t e = hipMalloc(d, 32 * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(*d, h, 32 * sizeof(float), hipMemcpyHostToDevice);
-        return e;
-    };
-    hipError_t e = up(s1, &L->s1);
-    if (e == hipSuccess) e = up(t1, &L->t1);
-    if (e == hipSuccess) e = up(s2, &L->s2);
-    if (e == hipSuccess) e = up(t2, &L->t2);
-    if (e != hipSuccess) { amt_fftconv_layer_destroy_internal(L); *layer = nullptr; return AMT_E_HIP; }
+    if ((*layer)->bn.upload(s1, t1, s2, t2, 32) != hipSuccess) { amt_fftconv_layer_destroy_internal(*layer); *layer = nullptr; return AMT_E_HIP; }
     return AMT_OK;
 }
 
@@ -695,8 +671,8 @@ int amt_fftconv_run(const amt_fftconv_layer *L, const float *in, const float *sh
     for (int i = 0; i < (repeat_gemm > 0 ? repeat_gemm : 1) && rc == AMT_OK; ++i) rc = amt_fftconv_gemm(L, Xf, amaxf, B, H, Yf, st);
     if (rc != AMT_OK) return rc;
     FcEpilogue ep{};
-    ep.s1 = L->s1; ep.t1 = L->t1;
-    if (shortcut && L->s2) { ep.s2 = L->s2; ep.t2 = L->t2; ep.sc = shortcut; ep.sc_stride = stride; }
+    ep.s1 = L->bn.s1; ep.t1 = L->bn.t1;
+    if (shortcut && L->bn.s2) { ep.s2 = L->bn.s2; ep.t2 = L->bn.t2; ep.sc = shortcut; ep.sc_stride = stride; }
     return amt_fftconv_inverse_epilogue(L, Yf, ep, B, H, W, out, stride, nullptr, nullptr, nullptr, st);
 }
 

@@ -520,13 +520,14 @@ struct amt_fftpk_layer {
     _Float16 *gw = nullptr;
     int *gsw = nullptr;
     float2 *tw = nullptr;
-    float *s1 = nullptr, *t1 = nullptr, *s2 = nullptr, *t2 = nullptr;      // optional device copies (stand-alone entry)
+    FcBnCopies bn;                     // stand-alone entry only
 };
 
 void amt_fftpk_layer_destroy_internal(amt_fftpk_layer *L) {
     if (!L) return;
-    for (void *p : {(void *)L->gw, (void *)L->gsw, (void *)L->tw, (void *)L->s1, (void *)L->t1, (void *)L->s2, (void *)L->t2})
+    for (void *p : {(void *)L->gw, (void *)L->gsw, (void *)L->tw})
         if (p) (void)hipFree(p);
+    L->bn.release();
     delete L;
 }
 
@@ -541,6 +542,7 @@ int amt_fftpk_layer_create_internal(amt_fftpk_layer **out, const float *kernel /
         tw[m] = make_float2((float)cos(ang), (float)sin(ang));
     }
     float *kdev = nullptr;
+    int rc = AMT_OK;
     hipError_t e = hipMalloc(&kdev, kbytes);
     if (e == hipSuccess) e = hipMemcpy(kdev, kernel, kbytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMalloc(&L->gw, gw_halfs * sizeof(_Float16));
@@ -549,18 +551,17 @@ int amt_fftpk_layer_create_internal(amt_fftpk_layer **out, const float *kernel /
     if (e == hipSuccess) e = hipMemcpy(L->tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         const size_t lds = (size_t)(128 * 128 + 2 * 64 * 2 + 4) * sizeof(double);
-        e = hipFuncSetAttribute((const void *)pk_weights_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) {
-            pk_weights_kernel<<<PK_NP, 256, lds, 0>>>(kdev, L->gw, L->gsw);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(0);
+        rc = amt_launch<pk_weights_kernel>(lds, PK_NP, 256, lds, 0, kdev, L->gw, L->gsw);
+        if (rc == AMT_OK) e = hipStreamSynchronize(0);
     }
     if (kdev) (void)hipFree(kdev);
     if (e != hipSuccess) {
         snprintf(amt_hip_err_buf, sizeof(amt_hip_err_buf), "fftpk weights: %s", hipGetErrorString(e));
+        rc = AMT_E_HIP;
+    }
+    if (rc != AMT_OK) {
         amt_fftpk_layer_destroy_internal(L);
-        return AMT_E_HIP;
+        return rc;
     }
     *out = L;
     return AMT_OK;
@@ -571,14 +572,7 @@ size_t amt_fftpk_freq_floats(int B) { return (size_t)PK_NP * PK_KF * B; }
 static const size_t PK_ROW_LDS = (size_t)(8 * PK_PS) * 4 + PK_TWN * sizeof(float2);
 template <bool IN_FREQ, int EPI>
 static int pk_row_launch_t(const PkRowArgs &a, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        AMT_HIP_CHECK(hipFuncSetAttribute((const void *)pk_row_kernel<IN_FREQ, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PK_ROW_LDS));
-        attr = true;
-    }
-    pk_row_kernel<IN_FREQ, EPI><<<32 * ((a.B + 7) / 8), PK_THREADS, PK_ROW_LDS, st>>>(a);
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
+    return amt_launch<pk_row_kernel<IN_FREQ, EPI>>(PK_ROW_LDS, 32 * ((a.B + 7) / 8), PK_THREADS, PK_ROW_LDS, st, a);
 }
 
 int amt_fftpk_forward_fft(const amt_fftpk_layer *L, const float *in_sp, size_t in_stride, int B, float *Xf, float *amaxf, hipStream_t st) {
@@ -591,19 +585,12 @@ int amt_fftpk_forward_fft(const amt_fftpk_layer *L, const float *in_sp, size_t i
 
 int amt_fftpk_gemm(const amt_fftpk_layer *L, const float *Xf, const float *amaxf, int B, float *Yf, hipStream_t st) {
     if (!L || !Xf || !Yf || !amaxf || B <= 0) return AMT_E_INVALID;
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    }
     PkGemmArgs a{Xf, Yf, amaxf, L->gw, L->gsw, B, 0, 0, 0};
     a.nchunks = (B + PK_CW - 1) / PK_CW;
     a.ntasks = PK_NP * a.nchunks;
-    const int wgs = std::min(a.ntasks, 2 * cus);
+    const int wgs = std::min(a.ntasks, 2 * amt_cu_count());
     a.tasks_per_wg = (a.ntasks + wgs - 1) / wgs;
-    pk_gemm_kernel<<<(a.ntasks + a.tasks_per_wg - 1) / a.tasks_per_wg, 256, 0, st>>>(a);
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
+    return amt_launch<pk_gemm_kernel>(0, (a.ntasks + a.tasks_per_wg - 1) / a.tasks_per_wg, 256, 0, st, a);
 }
 
 int amt_fftpk_inverse_epilogue(const amt_fftpk_layer *L, const float *Yf, const FcEpilogue &ep, int B, float *out_sp, size_t out_stride,
@@ -640,18 +627,7 @@ int amt_fftpk_create(amt_fftpk_layer **layer, const float *kernel_host, const fl
     if (!layer || !kernel_host || !s1 || !t1) return AMT_E_INVALID;
     int rc = amt_fftpk_layer_create_internal(layer, kernel_host);
     if (rc != AMT_OK) return rc;
-    amt_fftpk_layer *L = *layer;
-    auto up = [&](const float *h, float **d) -> hipError_t {
-        if (!h) return hipSuccess;
-        hipError_t e = hipMalloc(d, PK_C * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(*d, h, PK_C * sizeof(float), hipMemcpyHostToDevice);
-        return e;
-    };
-    hipError_t e = up(s1, &L->s1);
-    if (e == hipSuccess) e = up(t1, &L->t1);
-    if (e == hipSuccess) e = up(s2, &L->s2);
-    if (e == hipSuccess) e = up(t2, &L->t2);
-    if (e != hipSuccess) { amt_fftpk_layer_destroy_internal(L); *layer = nullptr; return AMT_E_HIP; }
+    if ((*layer)->bn.upload(s1, t1, s2, t2, PK_C) != hipSuccess) { amt_fftpk_layer_destroy_internal(*layer); *layer = nullptr; return AMT_E_HIP; }
     return AMT_OK;
 }
 
@@ -668,7 +644,7 @@ int amt_fftpk_run(const amt_fftpk_layer *L, const float *in, const float *shortc
     const size_t stride = (size_t)PK_H * PK_W * PK_C;
     int rc = amt_fftpk_forward_fft(L, in, stride, B, Xf, amaxf, st);
     FcEpilogue ep{};
-    ep.s1 = L->s1; ep.t1 = L->t1;
+    ep.s1 = L->bn.s1; ep.t1 = L->bn.t1;
     // chain > 0: that many extra applications of the same layer with the activations handed over in the frequency domain
     // (no shortcut, no spatial output: the register epilogue and the re-zeroing of the gaps), then the last one as below
     for (int c = 0; c < chain && rc == AMT_OK; ++c) {
@@ -677,7 +653,7 @@ int amt_fftpk_run(const amt_fftpk_layer *L, const float *in, const float *shortc
     }
     for (int i = 0; i < (repeat_gemm > 0 ? repeat_gemm : 1) && rc == AMT_OK; ++i) rc = amt_fftpk_gemm(L, Xf, amaxf, B, Yf, st);
     if (rc != AMT_OK) return rc;
-    if (shortcut && L->s2) { ep.s2 = L->s2; ep.t2 = L->t2; ep.sc = shortcut; ep.sc_stride = stride; }
+    if (shortcut && L->bn.s2) { ep.s2 = L->bn.s2; ep.t2 = L->bn.t2; ep.sc = shortcut; ep.sc_stride = stride; }
     return amt_fftpk_inverse_epilogue(L, Yf, ep, B, out, stride, nullptr, nullptr, nullptr, st);
 }
 

@@ -6,7 +6,7 @@
 // give-back"), so the probe runs on random non-zero operands by default; zeros give the cycle-limited figure.
 // bench.py calls it in the same process as the timed steps, so "executed MFMA rate vs what this chip sustains"
 // is a ratio of two numbers measured in one run on one device (round 2 carried a literal copied from a profile).
-#include "amt_common.h"
+#include "amt_launch.h"
 
 typedef _Float16 pr_h8 __attribute__((ext_vector_type(8)));
 typedef float pr_f4 __attribute__((ext_vector_type(4)));
@@ -47,10 +47,7 @@ extern "C" int amt_probe_mfma_f16(int waves_per_simd, int iters, int random_oper
                                   double *tflops_best, double *ms_best, void *stream) {
     if (!tflops_best || waves_per_simd < 1 || waves_per_simd > 8 || iters < 1 || launches < 1) return AMT_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    int dev = 0, cus = 0;
-    AMT_HIP_CHECK(hipGetDevice(&dev));
-    AMT_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const int blocks = cus * waves_per_simd, n = blocks * 256;
+    const int blocks = amt_cu_count() * waves_per_simd, n = blocks * 256;
     pr_h8 *a = nullptr;
     float *out = nullptr;
     AMT_HIP_CHECK(hipMalloc(&a, (size_t)n * sizeof(pr_h8)));

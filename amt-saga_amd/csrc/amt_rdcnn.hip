@@ -10,6 +10,7 @@
 //
 // All kernels stay in THIS translation unit: the build gives it per-file code generation flags (build.py).
 #include "amt_common.h"
+#include "amt_launch.h"
 #include "amt_fftconv.h"
 #include "amt_convh.h"
 #include "amt_rdcnn_topology.h"
@@ -197,7 +198,7 @@ static bool conv_channels_supported(int cin, int cout) {
            (cin == 64 && cout == 128) || (cin == 128 && cout == 128);
 }
 
-// ---- THE launch of a tiled kernel --------------------------------------------------------------------------------------
+// ---- the tile of a tiled kernel (its launch: amt_launch.h) -----------------------------------------------------------
 // the workgroup tile into the launch parameters; returns the number of position tiles (gridDim.x)
 static unsigned apply_tile(ConvParams &p, int TH, int TW, int NWIN) {
     p.TH = TH; p.TW = TW; p.NWIN = NWIN;
@@ -206,26 +207,13 @@ static unsigned apply_tile(ConvParams &p, int TH, int TW, int NWIN) {
     return (unsigned)((size_t)groups * p.tiles_h * p.tiles_w);
 }
 static unsigned apply_plan(ConvParams &p, const ConvPlan &pl) { return apply_tile(p, pl.TH, pl.TW, pl.NWIN); }
-// Kern's first launch in the process raises its dynamic-LDS limit to lds_cap bytes (0: it stays within the default)
-template <auto Kern, class... Args>
-static int launch_tiled(int lds_cap, dim3 grid, unsigned block, size_t lds, hipStream_t st, Args... args) {
-    static bool attr_set = false;
-    if (lds_cap && !attr_set) {
-        AMT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_cap));
-        attr_set = true;
-    }
-    Kern<<<grid, block, lds, st>>>(args...);
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
-}
-
 static int launch_conv16(const ConvOp &c, ConvParams p, hipStream_t st) {
     const dim3 grid(apply_plan(p, c.bf16), c.bf16.nslice);
     return amt_dispatch(ConvKernelSizes{}, c.kh, c.kw, [&](auto KH, auto KW) {
         return amt_dispatch(Bf16Shapes{}, c.cin, c.bf16.cw, [&](auto CI, auto CW) {
             return amt_dispatch(Flag{}, c.bf16.masked, [&](auto MASKED) {
-                return launch_tiled<conv_bf16x6_kernel<KH(), KW(), CI(), CW(), MASKED() != 0>>(
-                    80 * 1024, grid, 512, c.bf16.lds, st, p, static_cast<const uint4 *>(c.bf16.w));
+                return amt_launch<conv_bf16x6_kernel<KH(), KW(), CI(), CW(), MASKED() != 0>>(
+                    AMT_LDS_CONV, grid, 512, c.bf16.lds, st, p, static_cast<const uint4 *>(c.bf16.w));
             });
         });
     });
@@ -245,10 +233,7 @@ static void choose_tile_h(ConvOp &c) {
 }
 
 // AMT_CONV_TS diagnostic: phase split of a workgroup's life, four 100-MHz timestamps per workgroup of a split-fp16 launch
-static bool conv_ts_wanted() {
-    static const bool want = getenv("AMT_CONV_TS") != nullptr;
-    return want;
-}
+static bool conv_ts_wanted() { static const bool want = amt_env_switch("AMT_CONV_TS", false); return want; }
 static int conv_ts_buffer(size_t nwg, unsigned long long **out) {
     static unsigned long long *ts_dev = nullptr;
     static size_t ts_cap = 0;
@@ -285,8 +270,7 @@ static int conv_ts_report(const ConvOp &c, const char *form, const unsigned long
 static void choose_tile_w(ConvOp &c) {
     ConvPlan &p = c.f16;
     p.wm_ms = 0;
-    const char *e = getenv("AMT_CONV_WMAJOR");
-    if (e && e[0] == '0') return;
+    if (!amt_env_switch("AMT_CONV_WMAJOR", true)) return;
     if (!p.masked || c.kh != 4 || c.kw != 16 || !in_list(F16Cins{}, c.cin)) return;
     const int npos = c.H * c.W, ms = (npos + HXW_NWAVE - 1) / HXW_NWAVE;
     p.wm_ms = ms <= 3 ? 3 : ms <= 5 ? 5 : 8;
@@ -301,8 +285,8 @@ static int launch_convs(int kh, int kw, int cin, bool masked, dim3 grid, size_t 
     return amt_dispatch(ConvKernelSizes{}, kh, kw, [&](auto KH, auto KW) {
         return amt_dispatch(F16Cins{}, cin, [&](auto CI) {
             return amt_dispatch(Flag{}, masked, [&](auto MASKED) {
-                return launch_tiled<conv_f16x3s_kernel<KH(), KW(), CI(), MASKED() != 0, 2, TRAIN>>(
-                    80 * 1024, grid, 512, lds, st, p, static_cast<const uint4 *>(w), hs);
+                return amt_launch<conv_f16x3s_kernel<KH(), KW(), CI(), MASKED() != 0, 2, TRAIN>>(
+                    AMT_LDS_CONV, grid, 512, lds, st, p, static_cast<const uint4 *>(w), hs);
             });
         });
     });
@@ -320,7 +304,7 @@ static int launch_convh(const ConvOp &c, ConvParams p, const float *amax_in, flo
     if (conv_ts_wanted()) { const int rc = conv_ts_buffer(nwg, &hs.ts); if (rc != AMT_OK) return rc; }
     const int rc = !wmajor ? launch_convs<false>(c.kh, c.kw, c.cin, pl.masked, dim3(grid, pl.nslice), pl.lds, p, pl.w, hs, st)
                            : amt_dispatch(WmajorShapes{}, c.cin, pl.wm_ms, [&](auto CI, auto MS) {
-                                 return launch_tiled<conv_f16x3w_kernel<4, 16, CI(), MS()>>(
+                                 return amt_launch<conv_f16x3w_kernel<4, 16, CI(), MS()>>(
                                      160 * 1024, dim3((unsigned)nwg), 64 * HXW_NWAVE, pl.wm_lds, st, p,
                                      static_cast<const uint4 *>(pl.w), hs, pl.nslice);
                              });
@@ -333,7 +317,7 @@ static int launch_conv(const ConvOp &c, ConvParams p, hipStream_t st) {
     return amt_dispatch(ConvKernelSizes{}, c.kh, c.kw, [&](auto KH, auto KW) {
         return amt_dispatch(F32Shapes{}, c.cin, c.f32.cw, [&](auto CI, auto CW) {
             return amt_dispatch(amt_values<2, 1>{}, c.MT, [&](auto MT) {
-                return launch_tiled<conv_mfma_kernel<KH(), KW(), CI(), CW(), MT()>>(152 * 1024, grid, 256, c.f32.lds, st, p);
+                return amt_launch<conv_mfma_kernel<KH(), KW(), CI(), CW(), MT()>>(152 * 1024, grid, 256, c.f32.lds, st, p);
             });
         });
     });
@@ -359,7 +343,7 @@ static int launch_conv1_mfma(const ConvOp &c, const Conv1Params &cp, hipStream_t
                        (size_t)(TH1 + c.kh - 1) * (TW1 + c.kw - 1) * 4;
     const unsigned grid = (unsigned)std::min<size_t>((size_t)cp.B * th * twn, 256 * 8);
     return amt_dispatch(ConvKernelSizes{}, c.kh, c.kw, [&](auto KH, auto KW) {
-        return launch_tiled<conv1_mfma_kernel<KH(), KW()>>(0, grid, 256, lds, st, cp, TH1, TW1, th, twn);
+        return amt_launch<conv1_mfma_kernel<KH(), KW()>>(0, grid, 256, lds, st, cp, TH1, TW1, th, twn);
     });
 }
 static int launch_conv1(const ConvOp &c, const Conv1Params &cp, hipStream_t st) {
@@ -546,7 +530,7 @@ int amt_rdcnn_create(amt_rdcnn **out, const amt_rdcnn_desc *desc, const float *w
     if (!tp.shortcut_ok) return AMT_E_UNSUPPORTED;
     amt_rdcnn *n = new amt_rdcnn();
     n->d = d;
-    if (const char *e = getenv("AMT_FC_POOLED")) n->fc_pooled = e[0] != '0';
+    n->fc_pooled = amt_env_switch("AMT_FC_POOLED", true);
     n->flat = tp.flat;
     n->towers.resize(d.n_towers);
     for (int t = 0; t < d.n_towers; ++t) {

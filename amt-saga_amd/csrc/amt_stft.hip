@@ -26,6 +26,7 @@
 //    networks' MFMA kernels on a side stream.
 #include <type_traits>
 #include "amt_fft.h"
+#include "amt_launch.h"
 #include "amt_ordered.h"
 
 struct amt_stft_plan {
@@ -500,16 +501,9 @@ __global__ __launch_bounds__(256) void window_max_kernel(const float *__restrict
 // host launchers
 // diagnostics both STFT launchers read: AMT_STFT_PPB = most frame pairs per workgroup (default 16), AMT_STFT_REUSE=0 =
 // every pair loads its 16 samples per thread instead of carrying ten of them in registers
-static int stft_ppb_max() {
-    static int v = 0;
-    if (!v) { const char *e = getenv("AMT_STFT_PPB"); v = (e && atoi(e) > 0) ? atoi(e) : 16; }
-    return v;
-}
-static int stft_reuse_ok() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("AMT_STFT_REUSE"); v = !(e && atoi(e) == 0); }
-    return v;
-}
+// (read once per process: a static's initialisation is safe under concurrent callers)
+static int stft_ppb_max() { static const int v = (int)amt_env_number("AMT_STFT_PPB", 16); return v; }
+static int stft_reuse_ok() { static const int v = amt_env_switch("AMT_STFT_REUSE", true); return v; }
 
 template <int N>
 static int launch_stft(const amt_stft_plan *plan, const float *wave, int B, int L,
@@ -640,7 +634,7 @@ int amt_device_info(int *cu_count, int *lds_bytes, char *arch, int arch_len) {
     AMT_HIP_CHECK(hipGetDevice(&dev));
     hipDeviceProp_t prop;
     AMT_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-    if (cu_count) *cu_count = prop.multiProcessorCount;
+    if (cu_count) *cu_count = amt_cu_count();
     if (lds_bytes) *lds_bytes = (int)prop.sharedMemPerBlock;
     if (arch && arch_len > 0) {
         strncpy(arch, prop.gcnArchName, arch_len - 1);

@@ -22,6 +22,7 @@
 // A small tape (list of ops over numbered tensors) is built from the topology (amt_rdcnn_topology.h) once; a step
 // walks it forwards, then backwards accumulating gradients per tensor (the shortcut source receives two).
 #include "amt_common.h"
+#include "amt_launch_core.h"
 #include "amt_convh.h"
 #include "amt_rdcnn_topology.h"
 #include <algorithm>
@@ -708,14 +709,12 @@ namespace {
 #define TR_TRY(x) do { const int rc_ = (x); if (rc_ != AMT_OK) return rc_; } while (0)
 
 // The AMT_TRAIN_* environment, read once: when a trainer (which holds one of these) is created
-bool env_is_zero(const char *name) { const char *e = getenv(name); return e && atoi(e) == 0; }
-size_t env_size(const char *name, size_t dflt) { const char *e = getenv(name); return e && atol(e) >= 0 ? (size_t)atol(e) : dflt; }
 struct TrainOptions {
-    bool fast = !env_is_zero("AMT_TRAIN_FAST");              // =0: every convolution on im2col + f32 GEMM (+ col2im)
-    bool wgrad_direct = !env_is_zero("AMT_TRAIN_WGRAD");     // =0: weight gradients through im2col + GEMM
-    bool fused_bn = !env_is_zero("AMT_TRAIN_FUSED_BN");      // =0: the generic column-reduction BatchNormalization
-    size_t fast_min_m = env_size("AMT_TRAIN_FAST_MIN_M", 2048);   // fewest output positions (B H W) for the fast forms
-    bool trace = getenv("AMT_TRAIN_TRACE") != nullptr;       // set: synchronise and report after every op
+    bool fast = amt_env_switch("AMT_TRAIN_FAST", true);              // =0: every convolution on im2col + f32 GEMM (+ col2im)
+    bool wgrad_direct = amt_env_switch("AMT_TRAIN_WGRAD", true);     // =0: weight gradients through im2col + GEMM
+    bool fused_bn = amt_env_switch("AMT_TRAIN_FUSED_BN", true);      // =0: the generic column-reduction BatchNormalization
+    size_t fast_min_m = (size_t)amt_env_number("AMT_TRAIN_FAST_MIN_M", 2048, 0);   // fewest output positions (B H W) for the fast forms
+    bool trace = amt_env_switch("AMT_TRAIN_TRACE", false);           // set: synchronise and report after every op
 };
 
 // Per-batch device storage: knows its capacity and frees what it replaces when it grows.  Reads as the pointer.

@@ -558,6 +558,11 @@ def test_small_topologies(env, case):
     (1024, 1024 * 21 + 7, ((55.0, 75, 12), (27.5, 24, 192))),
     (256, 256 * 64 + 200, ((110.0, 48, 24),)),
     (512, 300, ((2000.0, 12, 12),)),                           # shorter than one block
+    # The kernel is instantiated per (Q, R) = (M-tiles per wave, leftover M-tiles) of the block count: the cases above
+    # are (1, 0), (1, 0), (0, 2), (1, 0), (0, 1), the full window below (4, 1); these are the shortest signals of
+    # Q = 2 (257 blocks: 17 M-tiles = (2, 1)) and Q = 3 (289 blocks: 19 M-tiles = (3, 0))
+    pytest.param(256, 256 * 256 + 57, ((2000.0, 12, 12),), marks=pytest.mark.timeout(60)),
+    pytest.param(256, 256 * 288 + 31, ((880.0, 12, 12),), marks=pytest.mark.timeout(60)),
 ])
 def test_cqt_window_max_mfma_form(env, hop, L, grids):
     """amt_cqt_window_max_mfma (block sums as a split-fp16 GEMM against the phasor table on a bin-independent block
