@@ -131,6 +131,8 @@ PROTOTYPES = {
                                      C.c_int, vp, vp, vp, C.c_int, vp, vp]),
     'amt_short_window': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t,
                                    vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]),
+    'amt_note_features': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, vp, C.c_int,
+                                    vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     'amt_gather_frames': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, vp, C.c_int,
                                     C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_size_t, vp]),
     'amt_amplitude_to_db': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, C.c_float,

@@ -54,6 +54,19 @@ def midi_to_hz(m):
     return 440.0 * (2.0 ** ((np.asanyarray(m, dtype=np.float64) - 69.0) / 12.0))
 
 
+def tone_to_fft_bin(fft_freq, tone):
+    """audio_complete.midi_tone_to_FFT (util_audio.py:278-284): two bins below the first FFT bin above the tone, not
+    below bin 0."""
+    return max(bisect.bisect_right(fft_freq, midi_to_hz(tone)) - 2, 0)
+
+
+def tone_bin_table(sr, n_fft, tone_lo, tone_hi):
+    """int32 [tone_hi - tone_lo + 1]: tone_to_fft_bin of every MIDI tone tone_lo .. tone_hi -- the host table
+    amt_note_features indexes with the step's decided pitches."""
+    freq = fft_frequencies(sr, n_fft)
+    return np.array([tone_to_fft_bin(freq, t) for t in range(int(tone_lo), int(tone_hi) + 1)], dtype=np.int32)
+
+
 def resize_source_frames(t, target):
     """Index form of audio_complete._resize (util_audio.py:384-409): for a
     source of t frames, the source frame of each of `target` output columns;
@@ -231,6 +244,22 @@ class AudioBatch:
         _lib.check(self.lib.amt_short_window(
             ptr(self.mag), ptr(self.ph), B, T, self.F, self.ldf, T * self.ldf, ptr(src_frame),
             frames, ptr(band_min), bands, ptr(ref), int(mode), ptr(out), stream_ptr()))
+        return out
+
+    def note_features(self, src_frame, pitch, tone_bin, tone_lo, bands, ref=None, want=('lin', 'log10', 'phase'),
+                      const_tone=60):
+        """The FFT-side instrument towers of a step in one launch (amt_note_features; training.py:347-363): the band of
+        `bands` bins from tone_bin[pitch - tone_lo] over the frames of src_frame, as any of 'lin' (mag / ref), 'log10'
+        and 'phase'.  pitch [B] int32 device, or None: const_tone for every window.  Returns {kind: [B, bands, frames]}."""
+        B, T = self.mag.shape[0], self.mag.shape[1]
+        frames = src_frame.shape[1]
+        if not want or any(k not in ('lin', 'log10', 'phase') for k in want):
+            raise ValueError('Requested attribute does not exist')
+        out = {k: empty((B, bands, frames)) for k in want}
+        _lib.check(self.lib.amt_note_features(
+            ptr(self.mag), ptr(self.ph) if 'phase' in out else None, B, T, self.F, self.ldf, T * self.ldf, ptr(src_frame),
+            frames, ptr(pitch), int(const_tone), ptr(tone_bin), int(tone_lo), int(tone_bin.shape[0]), int(bands), ptr(ref),
+            ptr(out.get('lin')), ptr(out.get('log10')), ptr(out.get('phase')), stream_ptr()))
         return out
 
 
@@ -682,7 +711,7 @@ class audio_complete:
 
     def midi_tone_to_FFT(self, tone):                       # util_audio.py:278-284
         """Two bins below the first FFT bin above the tone, not below bin 0."""
-        return max(bisect.bisect_right(self._fft_freq, midi_to_hz(tone)) - 2, 0)
+        return tone_to_fft_bin(self._fft_freq, tone)
 
     # ---- window management: frame index maps on the device -------------------------------
     def _take(self, index, names=SPECTRAL, with_F=True):

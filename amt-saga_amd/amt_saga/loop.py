@@ -14,6 +14,9 @@ per launch:
     pitch     = rint(pitch_classifier(C_sw_pitch))
     C_sw_inst = slice_C(onset, dur, 8, bpt=4) / ref_C_inst    training.py:343-346
     program   = argmax(InstrumentClassifier(C_sw_inst))
+                (instrument_model=: any of the reference's ten instrument models, INSTRUMENT_MODELS below -- its towers
+                 read the focused FFT bands, their log10 and phase, training.py:347-363, from one amt_note_features
+                 launch, or the focused CQT slices, :365-380; note_features() composes them)
     C_velocity = slice_C(..., bpt=2, nbins=36, lowest=pitch-10) / ref_C_foc   training.py:382-388
     velocity  = rint(VelocityClassifier(C_velocity))
     guess     = template bank[(program group, pitch)]         stand-in for render(), synth.py
@@ -32,7 +35,7 @@ import numpy as np
 import torch
 
 from . import _lib, song_walk, synth
-from .audio import AudioBatch, cqt_slices, cqt_table, cqt_window_max, midi_to_hz
+from .audio import AudioBatch, cqt_slices, cqt_table, cqt_window_max, midi_to_hz, tone_bin_table
 from .device import empty, ptr, require_gpu, stream_ptr, to_dev, zeros
 from .heads import (InstrumentClassifier, VelocityClassifier, pitch_classifier,
                     timming_classifier)
@@ -42,10 +45,42 @@ from .song_walk import (SONG_DETECT, SONG_EVENT_FIELDS, SONG_FINISHED, SONG_FORC
 
 EVENT_FIELDS = ('window', 'iter', 'pitch', 'program', 'velocity', 'onset_frame', 'end_frame')
 
+# The reference's ten instrument models (training.py:466-477): name -> (InstrumentClassifier variant, as gen_model
+# builds it, training.py:76-98; the recipe arrays its towers read, in tower order, as thread_training feeds them).
+# The arrays are those of the feature recipe, training.py:343-380:
+#   C_sw_inst                  slice_C at instrument_bins_per_tone from A0                     / ref_C_inst
+#   C_sw_inst_foc(_const)      slice_C at 4 x that from the decided pitch (from C4)            / ref_C_foc
+#   F_sw_inst_foc(_const)      the FFT band from midi_tone_to_FFT(pitch) (of C4), mag          / ref_mag
+#   F_sw_inst_foc(_const)_log10    the same band, log10(1000 mag + 1)                          / its maximum
+#   ph                         the phase angle of the pitch's band, (angle + 3.15) / 6.3
+INSTRUMENT_MODELS = {
+    'instrument': (InstrumentClassifier.INSTRUMENT, ('C_sw_inst',)),
+    'instrument_focused_lin': (InstrumentClassifier.INSTRUMENT_FOCUSED, ('F_sw_inst_foc',)),
+    'instrument_focused_lin_log10': (InstrumentClassifier.INSTRUMENT_FOCUSED, ('F_sw_inst_foc_log10',)),
+    'instrument_focused_const_lin': (InstrumentClassifier.INSTRUMENT_FOCUSED_CONST, ('F_sw_inst_foc_const',)),
+    'instrument_focused_const_lin_log10': (InstrumentClassifier.INSTRUMENT_FOCUSED_CONST,
+                                           ('F_sw_inst_foc_const_log10',)),
+    'instrument_dual_lin': (InstrumentClassifier.INSTRUMENT_DUAL, ('C_sw_inst', 'F_sw_inst_foc')),
+    'instrument_dual_lin_phase': (InstrumentClassifier.INSTRUMENT_DUAL, ('F_sw_inst_foc', 'ph')),
+    'instrument_focused': (InstrumentClassifier.INSTRUMENT_FOCUSED, ('C_sw_inst_foc',)),
+    'instrument_focused_const': (InstrumentClassifier.INSTRUMENT_FOCUSED_CONST, ('C_sw_inst_foc_const',)),
+    'instrument_dual': (InstrumentClassifier.INSTRUMENT_DUAL, ('C_sw_inst', 'C_sw_inst_foc')),
+}
+CONST_TONE = 60        # the _const models' fixed window position: C4 (training.py:289-290, :378)
+# recipe array -> the output of amt_note_features it is, for the decided pitch and for the constant tone
+_FFT_FEATURES = {'F_sw_inst_foc': 'lin', 'F_sw_inst_foc_log10': 'log10', 'ph': 'phase'}
+_FFT_FEATURES_CONST = {'F_sw_inst_foc_const': 'lin', 'F_sw_inst_foc_const_log10': 'log10'}
+FEATURE_NAMES = ('C_sw_inst', 'C_sw_inst_foc', 'C_sw_inst_foc_const') + tuple(_FFT_FEATURES) + tuple(_FFT_FEATURES_CONST)
+
 
 class TranscriptionLoop:
     def __init__(self, params, heads=('timing', 'pitch', 'velocity'), iters=1, subtract=True,
-                 groups=(0,), seeds=None, guess='bank', timbres=None, soundfont=None):
+                 groups=(0,), seeds=None, guess='bank', timbres=None, soundfont=None, instrument_model='instrument'):
+        if instrument_model not in INSTRUMENT_MODELS:
+            raise ValueError('Invalid Variant Selected')
+        self.instrument_model = instrument_model
+        # the recipe arrays the instrument towers read; none without the instrument head
+        self.instrument_inputs = INSTRUMENT_MODELS[instrument_model][1] if 'instrument' in heads else ()
         self.p = params
         self.heads = tuple(heads)
         self.iters = int(iters)
@@ -94,7 +129,8 @@ class TranscriptionLoop:
         if 'pitch' in self.heads:
             self.nets['pitch'] = pitch_classifier(params, weight_seed=seeds.get('pitch', 101))
         if 'instrument' in self.heads:
-            self.nets['instrument'] = InstrumentClassifier(params, 'instrument',
+            self.nets['instrument'] = InstrumentClassifier(params, INSTRUMENT_MODELS[instrument_model][0],
+                                                           prefix=instrument_model,
                                                            weight_seed=seeds.get('instrument', 102))
         if 'velocity' in self.heads:
             self.nets['velocity'] = VelocityClassifier(params, weight_seed=seeds.get('velocity', 103))
@@ -119,6 +155,16 @@ class TranscriptionLoop:
                                   12 * p.instrument_bins_per_tone, dev)
         self.tab_reff = cqt_table(sr, f_lo, span * p.instrument_bins_per_tone * 4,
                                   12 * p.instrument_bins_per_tone * 4, dev)
+        # the focused instrument towers: instrument_bands bins at 4 x instrument_bins_per_tone from the decided pitch
+        # (training.py:365-380) -> one global grid from pitch_low, as the velocity grid above; built for the models
+        # that read it
+        self.foc_bpt = 4 * p.instrument_bins_per_tone
+        self.tab_foc = None
+        if any(k.startswith('C_sw_inst_foc') for k in self.instrument_inputs):
+            self.tab_foc = cqt_table(sr, f_lo, self.foc_bpt * span + p.instrument_bands, 12 * self.foc_bpt, dev)
+        # midi_tone_to_FFT (util_audio.py:278-284) of every tone the pitch head can decide: what amt_note_features
+        # indexes with the step's pitches
+        self.tone_bin = to_dev(tone_bin_table(sr, p.N, lo, p.pitch_high), torch.int32)
         # index of a program group inside this loop's bank
         remap = np.zeros(3, dtype=np.int32)
         for i, g in enumerate(self.groups):
@@ -173,14 +219,9 @@ class TranscriptionLoop:
         refs = dict(refs or {})
         if 'ref_mag' not in refs:
             refs['ref_mag'] = b.ref_max.clone()
-        need_cqt = any(h in self.heads for h in ('pitch', 'instrument', 'velocity'))
-        if need_cqt:
-            if 'pitch' in self.heads and 'ref_C_1' not in refs:
-                refs['ref_C_1'] = cqt_window_max(b.wave, self.tab_ref1, p.H)
-            if 'instrument' in self.heads and 'ref_C_inst' not in refs:
-                refs['ref_C_inst'] = cqt_window_max(b.wave, self.tab_refi, p.H)
-            if 'velocity' in self.heads and 'ref_C_foc' not in refs:
-                refs['ref_C_foc'] = cqt_window_max(b.wave, self.tab_reff, p.H)
+        for key, tab in self.normalisers:
+            if key not in refs:
+                refs[key] = cqt_window_max(b.wave, getattr(self, tab), p.H)
         self.refs = refs
         return b
 
@@ -193,21 +234,70 @@ class TranscriptionLoop:
         p = self.p
         s = song.reshape(1, -1).to(torch.float32).contiguous()
         out = {'ref_mag': AudioBatch(s, p.N, p.H).stft(with_phase=False).ref_max[0].clone()}
-        if 'pitch' in self.heads:
-            out['ref_C_1'] = cqt_window_max(s, self.tab_ref1, p.H)[0]
-        if 'instrument' in self.heads:
-            out['ref_C_inst'] = cqt_window_max(s, self.tab_refi, p.H)[0]
-        if 'velocity' in self.heads:
-            out['ref_C_foc'] = cqt_window_max(s, self.tab_reff, p.H)[0]
+        for key, tab in self.normalisers:
+            out[key] = cqt_window_max(s, getattr(self, tab), p.H)[0]
         return out
 
     @property
+    def normalisers(self):
+        """(song-level CQT normaliser, the table of its grid) of every normaliser this loop's heads divide by
+        (training.py:271-282), in a fixed order: ref_C_1 for the pitch head, ref_C_inst where an instrument tower reads
+        C_sw_inst, ref_C_foc for the velocity head and for the focused CQT towers.  ref_mag comes with the STFT."""
+        inputs = self.instrument_inputs
+        out = []
+        if 'pitch' in self.heads:
+            out.append(('ref_C_1', 'tab_ref1'))
+        if 'C_sw_inst' in inputs:
+            out.append(('ref_C_inst', 'tab_refi'))
+        if 'velocity' in self.heads or any(k.startswith('C_sw_inst_foc') for k in inputs):
+            out.append(('ref_C_foc', 'tab_reff'))
+        return tuple(out)
+
+    @property
     def needs_wave(self):
-        return any(h in self.heads for h in ('pitch', 'instrument', 'velocity'))
+        return 'pitch' in self.heads or 'velocity' in self.heads or any(k.startswith('C_') for k in self.instrument_inputs)
 
     @property
     def needs_phase(self):
-        return self.iters > 1 and self.needs_wave
+        # the unit phase: read by the iSTFT behind the CQT heads from iteration 1 on, and by a `ph` tower at once
+        return (self.iters > 1 and self.needs_wave) or 'ph' in self.instrument_inputs
+
+    def note_features(self, b, src, wave_r, pitch, names):
+        """The instrument towers' part of the feature recipe (training.py:343-380) for the windows of the AudioBatch
+        `b`: the arrays `names` (of FEATURE_NAMES), each a [B, instrument_bands, instrument_frames] device tensor, in
+        the order asked for.  src [B, frames] int32: the step's resize table; wave_r [B, L]: what the CQT towers read
+        as the windows' waveform (may be None when no C_* array is asked for); pitch [B] int32: the decided pitches
+        (the loop's constant 60 without the pitch head).  Needs self.refs (prepare() / the song walk).
+        The FFT-side arrays of the decided pitch come from one amt_note_features launch, those of the constant tone
+        from another; every CQT array is one amt_cqt_slices launch."""
+        p, refs = self.p, self.refs
+        B = b.mag.shape[0]
+        names = tuple(names)
+        if any(k not in FEATURE_NAMES for k in names):
+            raise ValueError('Requested attribute does not exist')
+        got = {}
+        for table, tone in ((_FFT_FEATURES, pitch), (_FFT_FEATURES_CONST, None)):
+            want = tuple(dict.fromkeys(table[k] for k in names if k in table))
+            if want:
+                out = b.note_features(src, tone, self.tone_bin, p.pitch_low, p.instrument_bands, ref=refs['ref_mag'],
+                                      want=want, const_tone=CONST_TONE)
+                got.update({k: out[table[k]] for k in names if k in table})
+        for k in names:
+            if k in got:
+                continue
+            if k == 'C_sw_inst':
+                got[k] = cqt_slices(wave_r, src, self.tab_inst, p.instrument_bands, p.H, ref=refs['ref_C_inst'])
+                continue
+            if self.tab_foc is None:
+                raise ValueError('Requested attribute does not exist')       # the loop's model has no focused CQT tower
+            bin0 = empty((B,), torch.int32)
+            if k == 'C_sw_inst_foc':
+                _lib.check(self.lib.amt_affine_i32(ptr(pitch), B, self.foc_bpt, -self.foc_bpt * p.pitch_low, ptr(bin0),
+                                                   stream_ptr()))
+            else:
+                bin0.fill_(self.foc_bpt * (CONST_TONE - p.pitch_low))
+            got[k] = cqt_slices(wave_r, src, self.tab_foc, p.instrument_bands, p.H, bin0=bin0, ref=refs['ref_C_foc'])
+        return [got[k] for k in names]
 
     def _step(self, b, wave_fn, fmax, before_subtract=None, stems=None):
         """One detect -> subtract step on the windows of `b` -- the head sequence both traversals share (iterate() for
@@ -255,8 +345,8 @@ class TranscriptionLoop:
         else:
             pitch = torch.full((B,), 60, dtype=torch.int32, device=onset.device)
         if 'instrument' in self.heads:
-            ci = cqt_slices(wave_r, src, self.tab_inst, p.instrument_bands, p.H, ref=self.refs['ref_C_inst'])
-            tr['instrument'] = self.nets['instrument'].classify(ci)
+            towers = self.note_features(b, src, wave_r, pitch, self.instrument_inputs)
+            tr['instrument'] = self.nets['instrument'].classify(towers[0] if len(towers) == 1 else towers)
             program = self._argmax(tr['instrument'])
         if 'velocity' in self.heads:
             bin0 = empty((B,), torch.int32)

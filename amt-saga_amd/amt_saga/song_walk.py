@@ -16,9 +16,6 @@ from .device import empty, ptr, require_gpu, stream_ptr, to_dev, zeros
 # one record per step and song; onset / end / offset are song frames
 SONG_EVENT_FIELDS = ('song', 'step', 'kind', 'pitch', 'program', 'velocity', 'onset_frame', 'end_frame', 'offset_frame')
 SONG_DETECT, SONG_SLIDE, SONG_FORCED_SLIDE, SONG_FINISHED = 0, 1, 2, 3
-# head -> (song-level normaliser, the loop's table of its CQT grid); ref_mag comes with the STFT
-NORMALISERS = (('pitch', 'ref_C_1', 'tab_ref1'), ('instrument', 'ref_C_inst', 'tab_refi'),
-               ('velocity', 'ref_C_foc', 'tab_reff'))
 
 
 def song_wave_segments(lens, t_song, timing_frames, sr, positions, min_len=0):
@@ -187,7 +184,7 @@ class SongState:
         self.stems = empty((len(lp.groups), pool_frames, ldf)) if self.keep_stems else None
         b = self.batch = AudioBatch(None, p.N, p.H)
         b.mag, b.ph, b.ref_max = zeros((B, tf, ldf)), zeros((B, tf, ldf, 2)), zeros((B,))
-        self.ref_keys = ['ref_mag'] + [k for h, k, _ in NORMALISERS if h in lp.heads]
+        self.ref_keys = ['ref_mag'] + [k for k, _ in lp.normalisers]       # ref_mag comes with the STFT
         self.refs = {k: torch.ones((B,), dtype=torch.float32, device=dev) for k in self.ref_keys}
         self.t_song, self.offset, self.count = (zeros((B,), torch.int32) for _ in range(3))
         self.frame_base, self.sample_base = zeros((B,), torch.int64), zeros((B,), torch.int64)
@@ -250,7 +247,7 @@ class SongState:
             new_refs = [ref_mag] + [
                 torch.cat([cqt_window_max(self.samples[f0 * H:f0 * H + L][None, :], getattr(lp, tab), H)
                            for f0, L in zip(fbase, lens)]).contiguous()
-                for head, _, tab in NORMALISERS if head in lp.heads]
+                for _, tab in lp.normalisers]
         else:
             new_refs = [to_dev(refs[k]).reshape(n).contiguous() for k in self.ref_keys]
         positions = [-(-t // half) for t in t_song]

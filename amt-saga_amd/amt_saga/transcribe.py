@@ -30,8 +30,11 @@ provide for the inference direction:
     --format {flac,wav} (both modes): the container of --residual / --residual-dir / --stems-dir -- flac (default), or
     wav: PCM-24 WAV through audio.save_wav, a song's residual and stems in one call, named .residual.wav / .group<g>.wav.
 
+    --instrument-model NAME (both modes): the instrument head is the reference's model NAME (training.py:466-477; one of
+    loop.INSTRUMENT_MODELS), fed the recipe arrays that model was trained on; the default is the plain CQT model.
+
 Weights: a directory with {timing_start,timing_end,pitch,instrument,velocity}.npz in the
-naming of amt_saga/rdcnn.py; without it the heads carry their seeded synthetic weights (the
+naming of amt_saga/rdcnn.py (the instrument net's file is <its model's name>.npz: instrument.npz by default); without it the heads carry their seeded synthetic weights (the
 reference ships no checkpoint), which exercises the whole path but transcribes nothing.
 """
 import argparse
@@ -44,7 +47,7 @@ import torch
 
 from . import audio, events as ev, flac as host_flac, wav as host_wav
 from .hyperparams import Hyperparams
-from .loop import TranscriptionLoop
+from .loop import INSTRUMENT_MODELS, TranscriptionLoop
 
 
 def window_starts(n_samples, win_len, hop_len):
@@ -65,11 +68,18 @@ def cut_windows(wf, win_len, hop_len):
     return out, starts
 
 
-def _make_loop(p, iters, heads, groups, weights_dir, guess):
-    loop = TranscriptionLoop(p, heads=heads, iters=iters, groups=groups, guess=guess)
+def _model_option(instrument_model):
+    """The keyword that names a non-default instrument model to _make_loop; none for the default, whose call stays the
+    six-argument one that callers wrap (a cache of loops keyed by those six)."""
+    return {} if instrument_model == 'instrument' else {'instrument_model': instrument_model}
+
+
+def _make_loop(p, iters, heads, groups, weights_dir, guess, instrument_model='instrument'):
+    loop = TranscriptionLoop(p, heads=heads, iters=iters, groups=groups, guess=guess, instrument_model=instrument_model)
     if weights_dir:
         for name, net in loop.nets.items():
-            f = os.path.join(weights_dir, name + '.npz')
+            # the instrument net's file carries its model's name, as the reference's checkpoints do (training.py:76-98)
+            f = os.path.join(weights_dir, (instrument_model if name == 'instrument' else name) + '.npz')
             if os.path.exists(f):
                 net.load_weights(f)
     return loop.setup_device()
@@ -77,7 +87,7 @@ def _make_loop(p, iters, heads, groups, weights_dir, guess):
 
 def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument', 'velocity'),
                groups=(0, 1, 2), weights_dir=None, guess='bank', loop=None, batch=1024, traversal='windows',
-               silence=1e-3, sr=None, residual=False, stems=False):
+               silence=1e-3, sr=None, residual=False, stems=False, instrument_model='instrument'):
     """wf: float32 mono waveform at params.sr -- or, with `sr` given, a waveform [n] or [n, channels] at `sr`, resampled
     to params.sr (and downmixed) on the device first (audio.resample): everything below, the length the note times are
     computed from included, then sees the resampled signal.  Returns (notes, events) where notes is the
@@ -92,7 +102,9 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
     hop * (frames - 1) samples (run_songs(residual=True)); None if the walk stopped before the song's end.
     stems=True (traversal='song' only: ValueError): the song's instrument stems, a [len(groups), hop * (frames - 1)]
     float32 device tensor (run_songs(stems=True); row g belongs to groups[g]), are appended to what is returned --
-    (notes, events[, residual][, stems])."""
+    (notes, events[, residual][, stems]).
+    instrument_model: which of the reference's ten instrument models the instrument head is (loop.INSTRUMENT_MODELS);
+    no effect on a `loop` handed in."""
     if traversal not in ('windows', 'song'):
         raise ValueError('Requested attribute does not exist')
     if residual and traversal != 'song':
@@ -101,7 +113,7 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
         raise ValueError("transcribe: stems=True needs traversal='song'")
     p = params or Hyperparams(N=2048)
     if loop is None:
-        loop = _make_loop(p, iters, heads, groups, weights_dir, guess)
+        loop = _make_loop(p, iters, heads, groups, weights_dir, guess, **_model_option(instrument_model))
     if sr is not None:
         wf = audio.resample(wf, sr, p.sr)                              # 1-d float32, on the device; sr == p.sr: a downmix
     on_dev = isinstance(wf, torch.Tensor) and wf.is_cuda
@@ -131,7 +143,7 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
 
 def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', 'instrument', 'velocity'),
                           groups=(0, 1, 2), weights_dir=None, guess='bank', loop=None, slots=8, silence=1e-3, poll=16,
-                          pool_frames=None, residual=False, stems=False):
+                          pool_frames=None, residual=False, stems=False, instrument_model='instrument'):
     """The song queue behind transcribe_songs (TranscriptionLoop.iter_song_queue): yields (index, notes, events) as
     each song finishes, in finishing order -- (index, notes, events[, residual waveform][, stems [G, samples]]) with
     residual=True / stems=True.  wfs: a sequence or an iterator of mono float32 waveforms at params.sr; an
@@ -139,7 +151,7 @@ def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', '
     pulled (audio.resample)."""
     p = params or Hyperparams(N=2048)
     if loop is None:
-        loop = _make_loop(p, iters, heads, groups, weights_dir, guess)
+        loop = _make_loop(p, iters, heads, groups, weights_dir, guess, **_model_option(instrument_model))
     lens = {}
 
     def feed():
@@ -205,6 +217,9 @@ def _shared_options(ap, sr_help, **stems_dir):
     ap.add_argument('--weights', default=None)
     ap.add_argument('--iters', type=int, default=5)
     ap.add_argument('--guess', default='bank', choices=('bank', 'render'))
+    ap.add_argument('--instrument-model', default='instrument', choices=tuple(INSTRUMENT_MODELS), metavar='NAME',
+                    help='which of the ten instrument models the instrument head is: ' + ', '.join(INSTRUMENT_MODELS) +
+                         '; --weights then looks for NAME.npz')
     ap.add_argument('--sr', type=int, default=None, help=sr_help)
     ap.add_argument('--stems-dir', default=None, **stems_dir)
     ap.add_argument('--flac', default='host', choices=FLAC_WRITERS, help=_FLAC_HELP)
@@ -342,7 +357,8 @@ def main_songs(argv):
             rate, wfs = first[1], itertools.chain([first], wfs)
         wfs = _same_rate(a.songs, wfs, rate, a.decode)
     queue = iter_transcribe_songs(wfs, Hyperparams(N=2048, sr=rate), iters=a.iters, weights_dir=a.weights, guess=a.guess,
-                                  slots=a.slots, residual=keep, stems=keep_stems, groups=CLI_GROUPS)
+                                  slots=a.slots, residual=keep, stems=keep_stems, groups=CLI_GROUPS,
+                                  instrument_model=a.instrument_model)
     for item in queue:
         i, notes = item[0], item[1]
         out = os.path.join(a.out_dir, stems[i] + '.mid')
@@ -384,7 +400,7 @@ def main(argv=None):
         model_sr, file_sr = a.sr, sr
     got = transcribe(wf, Hyperparams(N=2048, sr=model_sr), iters=a.iters, weights_dir=a.weights, guess=a.guess,
                      traversal=a.traversal, sr=file_sr, residual=a.residual is not None, stems=a.stems_dir is not None,
-                     groups=CLI_GROUPS)
+                     groups=CLI_GROUPS, instrument_model=a.instrument_model)
     notes = got[0]
     ev.write_midi(notes, a.outfile)
     print('%d notes -> %s' % (len(notes), a.outfile))

@@ -127,6 +127,28 @@ __global__ __launch_bounds__(256) void compress_bands_kernel(
     }
 }
 
+// ---- the scalings of training.py:347-363, one element at a time: what short_window_kernel and note_features_kernel
+// both write, so that the two agree bit for bit whatever walks the tile
+__device__ __forceinline__ float sw_lin(float m, const float *__restrict__ ref, int b) {       // :352, :361
+    return ref ? __fdiv_rn(m, ref[b]) : m;
+}
+__device__ __forceinline__ float sw_log10(float m) {                                           // :350, :359
+    return log10f(__fmul_rn(m, 1000.0f) + 1.0f);
+}
+__device__ __forceinline__ float sw_phase(float2 q) {                                          // :362-363
+    return __fdiv_rn(atan2f(q.y, q.x) + 3.15f, 6.3f);
+}
+// the largest of the threads' lmax over the workgroup, in every thread (red: 16 floats, bmax: one, both LDS)
+__device__ __forceinline__ float sw_tile_max(float lmax, float *red, float *bmax) {
+    lmax = block_max(lmax, red);
+    if (threadIdx.x == 0) *bmax = lmax;
+    __syncthreads();
+    return *bmax;
+}
+__device__ __forceinline__ float sw_log10_norm(float v, float tile_max) {                      // :351, :360
+    return __fdiv_rn(v, tile_max);
+}
+
 // One workgroup per window: gather [bands][frames] from `frames` source rows.
 __global__ __launch_bounds__(256) void short_window_kernel(
     const float *__restrict__ mag, const float2 *__restrict__ phase, int T, int F, int ldf,
@@ -150,20 +172,96 @@ __global__ __launch_bounds__(256) void short_window_kernel(
         float val;
         if (mode == 2) {
             const float2 q = ok ? ph[(size_t)t * ldf + f] : make_float2(0.f, 0.f);
-            val = __fdiv_rn(atan2f(q.y, q.x) + 3.15f, 6.3f);
+            val = sw_phase(q);
         } else {
             const float m = ok ? mg[(size_t)t * ldf + f] : 0.f;
-            if (mode == 0) val = ref ? __fdiv_rn(m, ref[b]) : m;
-            else { val = log10f(__fmul_rn(m, 1000.0f) + 1.0f); lmax = fmaxf(lmax, val); }
+            if (mode == 0) val = sw_lin(m, ref, b);
+            else { val = sw_log10(m); lmax = fmaxf(lmax, val); }
         }
         o[i] = val;
     }
     if (mode == 1) {
-        lmax = block_max(lmax, red);
-        if (threadIdx.x == 0) bmax = lmax;
+        const float d = sw_tile_max(lmax, red, &bmax);
+        for (int i = threadIdx.x; i < n; i += blockDim.x) o[i] = sw_log10_norm(o[i], d);
+    }
+}
+
+// The FFT-side instrument towers of one step (training.py:347-363) in one launch: for window b the band of `bands` bins
+// from tone_bin[pitch[b] - tone_lo] (= midi_tone_to_FFT of the decided pitch; pitch NULL: const_tone for every window,
+// the _const models' C4, :289-290) over the frames src_frame[b][*], as mag / ref, log10(1000 mag + 1) / its tile maximum
+// and the scaled phase angle -- each output NULL or [B][bands][frames].
+//
+// One workgroup per window (the log10 tile maximum is a workgroup reduction).  Lanes run ALONG THE BINS of a frame, the
+// contiguous direction of the frame-major spectra: wave w takes frames w, w + 4, ..., its lanes bins lane, lane + 64,
+// ... of the band, so a wave's load is one run of 256 B (512 B of phase) and the frame index is a scalar.  A magnitude
+// is read once and feeds both out_lin and out_log10.  The [bands][frames] transposition happens in the LDS: a value goes
+// to tile[r * fs + j] with fs = frames | 1 -- an odd row pitch, so the 32 lanes of a store group, `fs` dwords apart, fall
+// on 32 different banks -- and leaves in output order, i = r * frames + j: consecutive lanes read consecutive dwords but
+// for one skipped pad per row (at most two lanes on a bank) and store one coalesced run.  LDS: one tile for lin and
+// (after it has been written out) phase, one for log10, bands x fs floats each -- 12.5 KiB apiece at 348 x 8, so the
+// tile never limits the workgroups per CU before their 256 threads do.
+__global__ __launch_bounds__(256) void note_features_kernel(
+    const float *__restrict__ mag, const float2 *__restrict__ phase, int T, int F, int ldf, size_t spec_stride,
+    const int32_t *__restrict__ src_frame, int frames, const int32_t *__restrict__ pitch, int const_tone,
+    const int32_t *__restrict__ tone_bin, int tone_lo, int n_tones, int bands, const float *__restrict__ ref,
+    float *__restrict__ out_lin, float *__restrict__ out_log10, float *__restrict__ out_phase) {
+    extern __shared__ float nf_tile[];
+    __shared__ float red[16];
+    __shared__ float bmax;
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
+    const int fs = frames | 1;
+    const int n = bands * frames;
+    float *tile_a = nf_tile;                                          // lin, then phase
+    float *tile_b = nf_tile + ((out_lin || out_phase) ? (size_t)bands * fs : 0);   // log10
+    const int tone = pitch ? pitch[b] : const_tone;
+    const int lo = tone_bin[min(max(tone - tone_lo, 0), n_tones - 1)];
+    const size_t ob = (size_t)b * n;
+    if (out_lin || out_log10) {
+        const float *mg = mag + (size_t)b * spec_stride;
+        float lmax = -INFINITY;
+        for (int j = wave; j < frames; j += nwave) {
+            const int t = src_frame[(size_t)b * frames + j];
+            const bool row_ok = t >= 0 && t < T;                      // uniform over the wave
+            const float *row = mg + (size_t)(row_ok ? t : 0) * ldf;
+            for (int r = lane; r < bands; r += 64) {
+                const int f = lo + r;
+                const float m = (row_ok && f >= 0 && f < F) ? row[f] : 0.f;
+                if (out_lin) tile_a[r * fs + j] = sw_lin(m, ref, b);
+                if (out_log10) {
+                    const float v = sw_log10(m);
+                    lmax = fmaxf(lmax, v);
+                    tile_b[r * fs + j] = v;
+                }
+            }
+        }
+        float d = 0.f;
+        if (out_log10) d = sw_tile_max(lmax, red, &bmax);             // (its barrier also publishes the tiles)
+        else __syncthreads();
+        for (int i = threadIdx.x; i < n; i += blockDim.x) {
+            const int r = i / frames, j = i - r * frames;
+            if (out_lin) out_lin[ob + i] = tile_a[r * fs + j];
+            if (out_log10) out_log10[ob + i] = sw_log10_norm(tile_b[r * fs + j], d);
+        }
+    }
+    if (out_phase) {
+        if (out_lin) __syncthreads();                                 // tile_a has been read out
+        const float2 *ph = phase + (size_t)b * spec_stride;
+        for (int j = wave; j < frames; j += nwave) {
+            const int t = src_frame[(size_t)b * frames + j];
+            const bool row_ok = t >= 0 && t < T;
+            const float2 *row = ph + (size_t)(row_ok ? t : 0) * ldf;
+            for (int r = lane; r < bands; r += 64) {
+                const int f = lo + r;
+                const float2 q = (row_ok && f >= 0 && f < F) ? row[f] : make_float2(0.f, 0.f);
+                tile_a[r * fs + j] = sw_phase(q);
+            }
+        }
         __syncthreads();
-        const float d = bmax;
-        for (int i = threadIdx.x; i < n; i += blockDim.x) o[i] = __fdiv_rn(o[i], d);
+        for (int i = threadIdx.x; i < n; i += blockDim.x) {
+            const int r = i / frames, j = i - r * frames;
+            out_phase[ob + i] = tile_a[r * fs + j];
+        }
     }
 }
 
@@ -288,6 +386,24 @@ int amt_short_window(const float *mag, const float *phase_ri, int B, int T, int 
     short_window_kernel<<<B, 256, 0, (hipStream_t)stream>>>(
         mag, reinterpret_cast<const float2 *>(phase_ri), T, F, ldf, spec_stride, src_frame, frames,
         band_min, bands, ref, mode, out);
+    AMT_LAUNCH_CHECK();
+    return AMT_OK;
+}
+
+int amt_note_features(const float *mag, const float *phase_ri, int B, int T, int F, int ldf, size_t spec_stride,
+                      const int32_t *src_frame, int frames, const int32_t *pitch, int const_tone,
+                      const int32_t *tone_bin, int tone_lo, int n_tones, int bands, const float *ref,
+                      float *out_lin, float *out_log10, float *out_phase, void *stream) {
+    if (!src_frame || !tone_bin || B <= 0 || T <= 0 || frames <= 0 || bands <= 0 || n_tones <= 0) return AMT_E_INVALID;
+    if (!out_lin && !out_log10 && !out_phase) return AMT_E_INVALID;
+    if ((out_phase && !phase_ri) || ((out_lin || out_log10) && !mag)) return AMT_E_ATTRIB;
+    if (F <= 0 || ldf < F) return AMT_E_SHAPE;
+    const size_t tile = (size_t)bands * (size_t)(frames | 1) * sizeof(float);
+    const size_t lds = tile * (((out_lin || out_phase) ? 1 : 0) + (out_log10 ? 1 : 0));
+    if (lds > 64 * 1024 - 128) return AMT_E_UNSUPPORTED;              // the tile is staged whole (the loop's: 12.5 KiB)
+    note_features_kernel<<<B, 256, lds, (hipStream_t)stream>>>(
+        mag, reinterpret_cast<const float2 *>(phase_ri), T, F, ldf, spec_stride, src_frame, frames, pitch, const_tone,
+        tone_bin, tone_lo, n_tones, bands, ref, out_lin, out_log10, out_phase);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }

@@ -361,6 +361,25 @@ int amt_short_window(const float *mag, const float *phase_ri, int B, int T, int 
                      int frames, const int32_t *band_min, int bands,
                      const float *ref, int mode, float *out, void *stream);
 
+/* The FFT-side instrument towers of one step in ONE launch (training.py:347-363): for every window b the rows
+ * [lo, lo + bands), lo = tone_bin[clamp(pitch[b] - tone_lo, 0, n_tones - 1)], of the frames src_frame[b][0..frames)
+ * (zero where the frame is < 0 or >= T or the bin >= F), scaled three ways:
+ *   out_lin   = mag / ref[b]  (ref NULL => 1)                         (F_sw_inst_foc / _const, :352,:361)
+ *   out_log10 = log10(mag*1000+1) / its maximum over the window's tile (.._log10, :350-351,:359-360)
+ *   out_phase = (angle(phase)+3.15)/6.3                               (ph, :362-363)
+ * each NULL (not wanted) or [B][bands][frames] f32; a magnitude is read once however many are wanted.  Every output is
+ * bit for bit what amt_short_window writes in the respective mode with band_min[b] = lo.
+ *   pitch [B] int32 device: the step's decided MIDI pitches; NULL => const_tone for every window (the _const models'
+ *   C4, training.py:289-290).  tone_bin [n_tones] int32 device: audio_complete.midi_tone_to_FFT (util_audio.py:278-284)
+ *   of the tones tone_lo .. tone_lo + n_tones - 1, built on the host.
+ * AMT_E_INVALID: a missing table, a non-positive count, or no output at all; AMT_E_ATTRIB: an output whose spectrum is
+ * NULL; AMT_E_SHAPE: ldf < F; AMT_E_UNSUPPORTED: a tile (bands x (frames | 1) floats per staged output) beyond the LDS
+ * of a workgroup. */
+int amt_note_features(const float *mag, const float *phase_ri, int B, int T, int F, int ldf, size_t spec_stride,
+                      const int32_t *src_frame, int frames, const int32_t *pitch, int const_tone,
+                      const int32_t *tone_bin, int tone_lo, int n_tones, int bands, const float *ref,
+                      float *out_lin, float *out_log10, float *out_phase, void *stream);
+
 /* window management as index maps: audio_complete.section :286-328, .slice :351-365, .concat :374-382,
  * .resize :469-507 (column selection with zero padding) and .section_power :334-349 (band of bins):
  *   out[b][j][k] = src[b][src_frame[b*table_stride + j]][band_min + k]
