@@ -415,7 +415,8 @@ int amt_spectral_flatness(const float *mag, int B, int T, int F, int ldf, size_t
  * ------------------------------------------------------------------------ */
 typedef struct amt_cqt_args {
     const float   *wave;        /* [B][wave_stride], L valid samples                    */
-    const int32_t *src_frame;   /* [B][frames] STFT-frame index of each output column, -1 => zeros */
+    const int32_t *src_frame;   /* [B][frames] STFT-frame index of each output column, -1 => zeros; every index
+                                 * lies in -1 .. T - 1, T = 1 + L / hop (the caller's duty: not checked on the device) */
     const int32_t *bin0;        /* [B] first bin of the table for each window, or NULL => 0 */
     const uint32_t *phase_inc;  /* [n_table] per-bin frequency, cycles/sample * 2^32    */
     const int32_t *length;      /* [n_table] filter length N_k in samples               */
@@ -426,8 +427,9 @@ typedef struct amt_cqt_args {
     int32_t        B, L, hop, frames, n_bins, n_table;
 } amt_cqt_args;
 
-/* Block-sum kernel (needs coef) when hop is a power of two in 128..2048 and L/hop <= ~1300 (the block sums live
- * in LDS); otherwise every frame is summed directly over its own N_k samples (any L and hop, coef unused). */
+/* Block-sum kernel (needs coef) when hop is a power of two in 128..2048 and L / hop <= 1692, i.e. L < 1693 hop (the
+ * block sums of L / hop + 3 blocks and their prefix sums live in 159 KiB of LDS); otherwise every frame is summed
+ * directly over its own N_k samples (any L and hop, coef unused). */
 int amt_cqt_slices(const amt_cqt_args *args, void *stream);
 
 /* Complex form (util_audio.py:424-429 with magnitude_only=False: librosa.cqt's complex output is returned as is):
@@ -444,7 +446,7 @@ int amt_cqt_coef(const uint32_t *phase_inc, const int32_t *length, int n_table, 
  * n_frames, pitch_frames, bins_per_tone=...)), the maximum of the whole CQT): out_max[b] = max over the
  * n_bins rows of the table and over EVERY frame t = 0 .. L/hop of |C[k, t]| of signal b -- a window, or a whole
  * song.  O(L) per bin whatever the filter length (prefix sums of per-hop block sums); hop a power of two in
- * 128..2048.  Up to ~1300 hops the block sums live in LDS; longer signals need
+ * 128..2048.  Up to L / hop = 1692 the block sums live in LDS; longer signals need
  * amt_cqt_window_max_workspace(L, hop, n_bins, B) bytes of device scratch (AMT_E_NOMEM if it is missing). */
 size_t amt_cqt_window_max_workspace(int L, int hop, int n_bins, int B);
 int amt_cqt_window_max(const float *wave, int B, int L, size_t wave_stride, int hop,
