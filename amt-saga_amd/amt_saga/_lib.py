@@ -118,6 +118,11 @@ PROTOTYPES = {
     'amt_pcm_unpack_ragged': (C.c_int, [vp, C.c_longlong, vp, C.c_int, C.c_longlong, vp, vp, C.c_longlong, vp]),
     'amt_pcm_peak_ragged': (C.c_int, [vp, vp, vp, C.c_int, C.c_longlong, vp, vp]),
     'amt_pcm_pack_ragged': (C.c_int, [vp, vp, vp, C.c_int, C.c_longlong, C.c_int, vp, vp, vp, C.c_longlong, vp]),
+    'amt_spec_levels_ragged': (C.c_int, [vp, C.c_longlong, vp, C.c_int, C.c_int, C.c_int, vp, C.c_longlong, vp, vp, vp,
+                                         C.c_longlong, vp]),
+    'amt_png_file_bound': (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    'amt_png_scratch_bytes': (C.c_longlong, [vp, C.c_int]),
+    'amt_png_encode_ragged': (C.c_int, [vp, C.c_longlong, vp, C.c_int, vp, vp, C.c_longlong, vp, C.c_longlong, vp, vp]),
     'amt_istft': (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp,
                             C.c_size_t, vp]),
     'amt_istft_ragged': (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, vp, vp, C.c_longlong, vp]),

@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, flac as _flac, wav as _wav
+from . import _lib, flac as _flac, png as _png, wav as _wav
 from .device import empty, per_device, ptr, require_gpu, stream_ptr, to_dev, zeros
 
 _PLANS = {}
@@ -910,6 +910,19 @@ class audio_complete:
                             fmt='float32', norm=True)
         _flac.save_float(np.asarray(self.wf), filename, sr=self.sr, bps=24)
 
+    def plot_spec(self, width=12, height=5, filename=None):
+        """util_audio.py:509-518 without the figure window: the dB spectrogram D (ref = ref_mag, 80 dB) on a log
+        frequency axis as a PNG file of 100 pixels per inch -- width x height inches, the reference's arguments --
+        rendered and encoded on the device (spectrogram_png).  Returns the file's bytes; filename: also written
+        there."""
+        self.mag
+        size = (int(round(100 * width)), int(round(100 * height)))
+        data = spectrogram_png([self._dev('mag')], [float(self.ref_mag)], size=size, axis='log', sr=self.sr,
+                               n_fft=self.N)[0]
+        if filename is not None:
+            _write_files([data], filename)
+        return data
+
 
 # ======================================================================================
 # Sample-rate conversion (the `sr=` of librosa.load, util_audio.py:962-964)
@@ -1441,3 +1454,145 @@ def wav_encode(waves, sr, fmt='pcm24', norm=False):
 def save_wav(waves, paths, sr, fmt='pcm24', norm=False):
     """wav_encode(waves, sr, fmt, norm) written to `paths`, one file per signal, one write per file."""
     _write_files(wav_encode(waves, sr, fmt=fmt, norm=norm), paths)
+
+
+# ======================================================================================
+# Spectrogram images on the device (plot_spec, util_audio.py:509-518; plot_specs, util_audio.py:938-960)
+# ======================================================================================
+def _image_sizes(size, n):
+    """[(W, H)] * n from one (W, H) or a list of n of them."""
+    sizes = [tuple(size)] * n if len(size) == 2 and not hasattr(size[0], '__len__') else [tuple(s) for s in size]
+    if len(sizes) != n or any(len(s) != 2 for s in sizes):
+        raise ValueError('Invalid Input shape. Expected: one (W, H) or one per spectrogram (%d) . Got: %r' % (n, size))
+    return [(_png._dim(w, 'W'), _png._dim(h, 'H')) for w, h in sizes]
+
+
+def spectrogram_levels(mags, refs, size=(1200, 500), axis='log', sr=44100, n_fft=2048, top_db=80.0, fmin=_png.FMIN):
+    """The dB picture of audio_complete.D as plot_spec draws it (util_audio.py:509-518), without a logarithm: every
+    magnitude spectrogram of `mags` -- float32 device tensors [T, >= F] frame-major, F = n_fft // 2 + 1, rows of any
+    stride (a region of the song pool as SongState.region_spectra returns it is taken as a view) -- becomes a uint8
+    device image [H, W] of levels 0 .. 255 over top_db below its reference level: refs[i], a number or a 0-d / 1-element
+    device tensor (read on the device: nothing is synchronised).  size: (W, H) for all, or one per spectrogram; axis
+    'log' (from fmin to sr / 2, the reference's y_axis='log') or 'linear'; row 0 is the highest frequency.  ONE
+    amt_spec_levels_ragged launch on the current stream; the images are views of one buffer.  The rule: DESIGN 26."""
+    if axis not in _png.AXES:
+        raise ValueError('Requested attribute does not exist: axis must be one of %s' % (_png.AXES,))
+    thr = _png.thresholds(top_db)
+    mags = [mags] if isinstance(mags, torch.Tensor) and mags.dim() == 2 else list(mags)
+    F = int(n_fft) // 2 + 1
+    for m in mags:
+        if not (isinstance(m, torch.Tensor) and m.is_cuda and m.dtype == torch.float32 and m.dim() == 2
+                and m.shape[0] >= 1 and m.shape[1] >= F and (m.shape[1] == 1 or m.stride(1) == 1)):
+            raise ValueError('Invalid Input shape. Expected: float32 device tensors [T, >= %d] . Got: %s'
+                             % (F, tuple(m.shape) if hasattr(m, 'shape') else type(m).__name__))
+    n = len(mags)
+    if n == 0:
+        raise ValueError('Invalid Input shape. Expected: at least one spectrogram . Got: an empty list')
+    if n > MAX_SIGNALS:
+        raise ValueError('Invalid Input shape. Expected: at most %d spectrograms a call . Got: %d' % (MAX_SIGNALS, n))
+    refs = list(refs.reshape(-1).unbind(0)) if isinstance(refs, torch.Tensor) else list(refs)
+    if len(refs) != n:
+        raise ValueError('Invalid Input shape. Expected: one reference level per spectrogram (%d) . Got: %d' % (n, len(refs)))
+    sizes = _image_sizes(size, n)
+    if len({m.device for m in mags}) != 1:
+        raise ValueError('Invalid Input shape. Expected: spectrograms of one device . Got: several')
+    lib, dev = _lib.load(), mags[0].device
+    anchor = min(m.data_ptr() for m in mags)
+    tables, at, meta, out_at, extent = [], {}, [], 0, 0
+    for m, (W, H) in zip(mags, sizes):
+        T, ldf = int(m.shape[0]), int(_stride0(m))
+        for key, build in ((('r', H), lambda: _png.axis_rows(F, H, sr, n_fft, axis, fmin)),
+                           (('c', T, W), lambda: _png.axis_cols(T, W))):
+            if key not in at:
+                at[key] = sum(t.size for t in tables)
+                tables.append(build().reshape(-1))
+        base = (m.data_ptr() - anchor) // 4
+        meta.append([base, T, ldf, F, W, H, at[('r', H)], at[('c', T, W)], out_at, 0])
+        extent = max(extent, base + (T - 1) * ldf + F)
+        out_at += W * H
+    host = np.concatenate(tables).astype(np.int32)
+    d_tab, d_meta, d_thr = to_dev(host, torch.int32), to_dev(np.asarray(meta, np.int64), torch.int64), to_dev(thr)
+    if all(isinstance(r, torch.Tensor) for r in refs):
+        d_ref = torch.stack([r.reshape(()).to(torch.float32) for r in refs]).to(dev)
+    else:
+        d_ref = to_dev(np.asarray([float(r) for r in refs], np.float32))
+    out = torch.empty((out_at,), dtype=torch.uint8, device=dev)
+    _lib.check(lib.amt_spec_levels_ragged(C.c_void_p(anchor), extent, ptr(d_meta), n, max(w for w, _ in sizes),
+                                          max(h for _, h in sizes), ptr(d_tab), host.size, ptr(d_thr), ptr(d_ref),
+                                          ptr(out), out_at, stream_ptr()))
+    return [out[row[8]:row[8] + W * H].view(H, W) for row, (W, H) in zip(meta, sizes)]
+
+
+def png_encode_streams(images, palette='cubehelix'):
+    """amt_png_encode_ragged for `images` (see png_encode), one call on the current stream: returns (out, file_off) --
+    out a uint8 device buffer in which file i lies at [file_off[i], file_off[i + 1]), file_off int64 [n + 1] on the
+    device.  The call waits for the upload of its two small tables (and so for the stream's earlier work); the kernels
+    are only enqueued and nothing is copied back."""
+    return _png_encode(images, palette)[:2]
+
+
+def png_encode(images, palette='cubehelix'):
+    """matplotlib's savefig of plot_spec (util_audio.py:509-518) without the figure: every image of `images` -- uint8
+    device tensors [H, W], W and H in 1 .. 16384 -- as the bytes of a complete PNG file, indexed colour with the
+    256-entry `palette` ('cubehelix') or greyscale ('gray').  Filters, deflate, Adler-32 and CRC-32 run on the device
+    (amt_png_encode_ragged, ONE call for the whole list on the current stream); only the finished files are copied
+    back, in one copy after the sizes.  The bytes are those of the rule in DESIGN 26, whatever the batch."""
+    out, file_off, bound, n = _png_encode(images, palette)
+    off = file_off.cpu().tolist()
+    if off[-1] > bound:
+        raise RuntimeError('png_encode: the files need %d bytes, the buffer has %d' % (off[-1], bound))
+    data = out[:off[-1]].cpu().numpy().tobytes()
+    return [data[off[i]:off[i + 1]] for i in range(n)]
+
+
+def _png_encode(images, palette):
+    """The checks and the one call of png_encode / png_encode_streams: (out, file_off, bytes of out, images)."""
+    pal = _png.palette(palette)
+    items = [images] if isinstance(images, torch.Tensor) and images.dim() == 2 else list(images)
+    for im in items:
+        if not (isinstance(im, torch.Tensor) and im.is_cuda and im.dtype == torch.uint8 and im.dim() == 2):
+            raise ValueError('Invalid Input shape. Expected: uint8 device tensors [H, W] . Got: %s'
+                             % (tuple(im.shape) if hasattr(im, 'shape') else type(im).__name__,))
+    if not items:
+        raise ValueError('Invalid Input shape. Expected: at least one image . Got: an empty list')
+    if len(items) > MAX_SIGNALS:
+        raise ValueError('Invalid Input shape. Expected: at most %d images a call . Got: %d' % (MAX_SIGNALS, len(items)))
+    for im in items:
+        _png._dim(int(im.shape[1]), 'W'), _png._dim(int(im.shape[0]), 'H')
+    if len({im.device for im in items}) != 1:
+        raise ValueError('Invalid Input shape. Expected: images of one device . Got: several')
+    items = [im if im.is_contiguous() else im.contiguous() for im in items]
+    lib, dev, n = _lib.load(), items[0].device, len(items)
+    anchor = min(im.data_ptr() for im in items)
+    meta = (C.c_longlong * (3 * n))()
+    extent = bound = 0
+    for i, im in enumerate(items):
+        H, W = int(im.shape[0]), int(im.shape[1])
+        meta[3 * i], meta[3 * i + 1], meta[3 * i + 2] = im.data_ptr() - anchor, W, H
+        extent = max(extent, im.data_ptr() - anchor + W * H)
+        bound += int(lib.amt_png_file_bound(W, H, int(pal is not None)))
+    need = int(lib.amt_png_scratch_bytes(meta, n))
+    if need < 0:
+        _lib.check(_lib.AMT_E_INVALID)
+    scratch = torch.empty((need,), dtype=torch.uint8, device=dev)
+    out = torch.empty((bound,), dtype=torch.uint8, device=dev)
+    file_off = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+    d_pal = to_dev(np.ascontiguousarray(pal).reshape(-1), torch.uint8) if pal is not None else None
+    _lib.check(lib.amt_png_encode_ragged(C.c_void_p(anchor), extent, meta, n, ptr(d_pal) if pal is not None else None,
+                                         ptr(scratch), need, ptr(out), bound, ptr(file_off), stream_ptr()))
+    # the images and the scratch stay referenced until the call is enqueued; torch's allocator keeps a freed block for
+    # the stream that used it, so work enqueued later on this stream cannot overtake the encoder
+    return out, file_off, bound, n
+
+
+def spectrogram_png(mags, refs, size=(1200, 500), axis='log', sr=44100, n_fft=2048, top_db=80.0, palette='cubehelix'):
+    """spectrogram_levels and png_encode together: one levels launch and one encode call for the whole list; returns
+    one PNG file (bytes) per spectrogram."""
+    _png.palette(palette)                                              # (refused before any device work)
+    return png_encode(spectrogram_levels(mags, refs, size=size, axis=axis, sr=sr, n_fft=n_fft, top_db=top_db),
+                      palette=palette)
+
+
+def save_spectrograms(mags, paths, refs, **kw):
+    """spectrogram_png(mags, refs, ...) written to `paths`, one file per spectrogram, one write per file."""
+    _write_files(spectrogram_png(mags, refs, **kw), paths)

@@ -196,6 +196,7 @@ class SongState:
         self.wave = empty((B, self.l_row))
         self.song_of, self.region = [-1] * B, [None] * B           # host: the slot's song (-1: free) and pool region
         self.frames = [0] * B                                      # host: frames of the slot's song
+        self.lens = [0] * B                                        # host: samples of the slot's song
         self.residual = None                                       # walk_songs(residual=True): one waveform per slot
         self.stem_audio = None                                     # walk_songs(stems=True): one [G, samples] per slot
         self.steps = self.positions = self.bound = 0
@@ -266,6 +267,7 @@ class SongState:
         for j, (slot, idx, _, f0) in enumerate(took):
             mask[slot] = 1 + j
             self.song_of[slot], self.region[slot], self.frames[slot] = idx, int(f0), int(t_song[j])
+            self.lens[slot] = lens[j]
         d_mask, d_seg = to_dev(mask, torch.int32), to_dev(seg_new, torch.int32)
         d_ts, d_song = to_dev(np.asarray(t_song, np.int32), torch.int32), \
             to_dev(np.asarray([idx for _, idx, _, _ in took], np.int32), torch.int32)
@@ -284,6 +286,7 @@ class SongState:
     def release(self, slot):
         self.pool.release(self.region[slot])
         self.song_of[slot], self.region[slot], self.frames[slot] = -1, None, 0
+        self.lens[slot] = 0
 
     def residual_waves(self, slots):
         """What the walk left of the songs in `slots` (every one finished), as audio: the iSTFT of the residual
@@ -309,19 +312,41 @@ class SongState:
         out, base, lens = self._region_waves('stem_waves', slots, self.stems)
         return [out[:, int(a):int(a) + n] for a, n in zip(base, lens)]
 
-    def _region_waves(self, who, slots, mags):
-        """The iSTFT of the slots' regions of every mags[g] ([G, pool_frames, ldf]) times s_ph, one amt_istft_ragged
-        launch per g.  Returns (out [G, samples], first sample per slot, samples per slot)."""
+    def region_spectra(self, slots):
+        """What the walk left and what it took out of the songs in `slots` (every one finished), as magnitude
+        spectrograms where they lie: per slot (residual, stems) -- residual the song's region of s_mag, [t_song, ldf],
+        with keep_residual, else None; stems [G, t_song, ldf], row g of lp.groups[g], with keep_stems, else None.
+        Views of the pool, nothing is copied or launched: they are what audio.spectrogram_png draws, valid until the
+        slot is released.  ValueError: a state built with neither flag, a free slot, or a song that is not finished."""
+        if not (self.keep_residual or self.keep_stems):
+            raise ValueError('region_spectra: the state was built without keep_residual and without keep_stems')
+        out = []
+        for b in self._finished_slots('region_spectra', slots):
+            f0, t = self.region[b], self.frames[b]
+            out.append((self.s_mag[f0:f0 + t] if self.keep_residual else None,
+                        self.stems[:, f0:f0 + t] if self.keep_stems else None))
+        return out
+
+    def _finished_slots(self, who, slots):
+        """`slots` as integers, every one holding a finished song; else the ValueError of residual_waves."""
         slots = [int(b) for b in slots]
-        G = int(mags.shape[0])
         if not slots:
-            return empty((G, 0)), [], []
+            return slots
         fin = self.finished.cpu().numpy()
         for b in slots:
             if not 0 <= b < self.slots or self.region[b] is None:
                 raise ValueError('%s: slot %d holds no song' % (who, b))
             if not fin[b]:
                 raise ValueError('%s: the song in slot %d is not finished' % (who, b))
+        return slots
+
+    def _region_waves(self, who, slots, mags):
+        """The iSTFT of the slots' regions of every mags[g] ([G, pool_frames, ldf]) times s_ph, one amt_istft_ragged
+        launch per g.  Returns (out [G, samples], first sample per slot, samples per slot)."""
+        G = int(mags.shape[0])
+        slots = self._finished_slots(who, slots)
+        if not slots:
+            return empty((G, 0)), [], []
         lp, H = self.lp, self.lp.p.H
         frames = [self.frames[b] for b in slots]
         lens = [H * (t - 1) for t in frames]

@@ -29,6 +29,10 @@ provide for the inference direction:
     and the WAV files of a group in one decode call each); every other file is read as FLAC.
     --format {flac,wav} (both modes): the container of --residual / --residual-dir / --stems-dir -- flac (default), or
     wav: PCM-24 WAV through audio.save_wav, a song's residual and stems in one call, named .residual.wav / .group<g>.wav.
+    --spectrogram-dir DIR (with --traversal song, or with --songs) [--spectrogram-size WxH, default 1200x500]: the dB
+    spectrograms of the input, of what the walk left and of what it took out per group, as <input stem>.song.png,
+    .residual.png and .group<g>.png (plot_specs, util_audio.py:938-960), levels and PNG files made on the device
+    (audio.save_spectrograms), all against the song's own maximum.
 
     --instrument-model NAME (both modes): the instrument head is the reference's model NAME (training.py:466-477; one of
     loop.INSTRUMENT_MODELS), fed the recipe arrays that model was trained on; the default is the plain CQT model.
@@ -45,7 +49,7 @@ import sys
 import numpy as np
 import torch
 
-from . import audio, events as ev, flac as host_flac, wav as host_wav
+from . import audio, events as ev, flac as host_flac, png as host_png, wav as host_wav
 from .hyperparams import Hyperparams
 from .loop import INSTRUMENT_MODELS, TranscriptionLoop
 
@@ -87,7 +91,7 @@ def _make_loop(p, iters, heads, groups, weights_dir, guess, instrument_model='in
 
 def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument', 'velocity'),
                groups=(0, 1, 2), weights_dir=None, guess='bank', loop=None, batch=1024, traversal='windows',
-               silence=1e-3, sr=None, residual=False, stems=False, instrument_model='instrument'):
+               silence=1e-3, sr=None, residual=False, stems=False, instrument_model='instrument', on_finish=None):
     """wf: float32 mono waveform at params.sr -- or, with `sr` given, a waveform [n] or [n, channels] at `sr`, resampled
     to params.sr (and downmixed) on the device first (audio.resample): everything below, the length the note times are
     computed from included, then sees the resampled signal.  Returns (notes, events) where notes is the
@@ -104,7 +108,9 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
     float32 device tensor (run_songs(stems=True); row g belongs to groups[g]), are appended to what is returned --
     (notes, events[, residual][, stems]).
     instrument_model: which of the reference's ten instrument models the instrument head is (loop.INSTRUMENT_MODELS);
-    no effect on a `loop` handed in."""
+    no effect on a `loop` handed in.
+    on_finish(0, 0, state) (traversal='song' only): called after the walk with the song's SongState, its pool still in
+    place -- iter_song_queue's hook; state.region_spectra([0]) is what write_song_spectrograms draws."""
     if traversal not in ('windows', 'song'):
         raise ValueError('Requested attribute does not exist')
     if residual and traversal != 'song':
@@ -121,6 +127,8 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
         wf32 = wf if on_dev else np.ascontiguousarray(wf, dtype=np.float32)      # (run_songs takes either)
         events, st = loop.run_songs([wf32], max_notes=iters, silence=silence, residual=residual, stems=stems)
         evs = events.cpu().numpy()
+        if on_finish is not None:
+            on_finish(0, 0, st)
         notes = ev.song_events_to_notes(evs, 1 + len(wf32) // p.H, len(wf32), sr=p.sr)
         return (notes, evs) + ((st.residual[0],) if residual else ()) + ((st.stem_audio[0],) if stems else ())
     L = p.H * (p.timing_frames - 1)
@@ -143,12 +151,13 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
 
 def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', 'instrument', 'velocity'),
                           groups=(0, 1, 2), weights_dir=None, guess='bank', loop=None, slots=8, silence=1e-3, poll=16,
-                          pool_frames=None, residual=False, stems=False, instrument_model='instrument'):
+                          pool_frames=None, residual=False, stems=False, instrument_model='instrument', on_finish=None):
     """The song queue behind transcribe_songs (TranscriptionLoop.iter_song_queue): yields (index, notes, events) as
     each song finishes, in finishing order -- (index, notes, events[, residual waveform][, stems [G, samples]]) with
     residual=True / stems=True.  wfs: a sequence or an iterator of mono float32 waveforms at params.sr; an
     item may also be a (waveform [n] or [n, channels], sr) pair, which is resampled to params.sr on the device as it is
-    pulled (audio.resample)."""
+    pulled (audio.resample).  on_finish(index, slot, state): iter_song_queue's hook, called when a song is found
+    finished, before its slot and its pool region are given away."""
     p = params or Hyperparams(N=2048)
     if loop is None:
         loop = _make_loop(p, iters, heads, groups, weights_dir, guess, **_model_option(instrument_model))
@@ -163,7 +172,7 @@ def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', '
             lens[i] = len(w)
             yield w
     for item in loop.iter_song_queue(feed(), slots, max_notes=iters, silence=silence, poll=poll,
-                                     pool_frames=pool_frames, residual=residual, stems=stems):
+                                     pool_frames=pool_frames, on_finish=on_finish, residual=residual, stems=stems):
         i, evs = item[0], item[1]
         n = lens.pop(i)
         one = evs.copy()
@@ -204,6 +213,13 @@ _FORMAT_HELP = ("container of --residual / --residual-dir / --stems-dir: 'flac' 
                 ".residual.wav and .group<g>.wav; with 'wav', --flac has no effect")
 
 
+_SPECTROGRAM_HELP = ('with --traversal song, or with --songs: write <stem>.song.png (the STFT of the input), '
+                     '<stem>.residual.png (what the walk left) and <stem>.group<g>.png (what it took out, per '
+                     'instrument group) per song as it finishes: dB spectrograms over 80 dB on a log frequency axis, '
+                     'all drawn against the song\'s own maximum, so that a colour is a level across them; levels and '
+                     'PNG files are made on the device, one levels call and one encode call per song')
+
+
 DECODERS = ('host', 'device')
 _DECODE_HELP = ("reader of the input files: 'host' = the pure-Python reader (the default), 'device' = the HIP decoder "
                 "(--songs: --slots files per decode call, as the queue pulls them; CRC-8, CRC-16 and MD5 verified as the "
@@ -226,6 +242,9 @@ def _shared_options(ap, sr_help, **stems_dir):
     ap.add_argument('--flac-predictor', default='fixed', choices=FLAC_PREDICTORS, help=_FLAC_PREDICTOR_HELP)
     ap.add_argument('--decode', default='host', choices=DECODERS, help=_DECODE_HELP)
     ap.add_argument('--format', default='flac', choices=FORMATS, help=_FORMAT_HELP)
+    ap.add_argument('--spectrogram-dir', default=None, metavar='DIR', help=_SPECTROGRAM_HELP)
+    ap.add_argument('--spectrogram-size', default='1200x500', metavar='WxH',
+                    help='pixels of every --spectrogram-dir image, each side 1 .. 16384 (default 1200x500)')
 
 
 def _check_writer(a):
@@ -308,6 +327,41 @@ def write_song_audio(rate, residual=None, residual_path=None, stems=None, stems_
         print(line)
 
 
+def _spectrogram_size(a):
+    """(W, H) of --spectrogram-size, checked before any work; None without --spectrogram-dir."""
+    if a.spectrogram_dir is None:
+        return None
+    try:
+        return host_png.parse_size(a.spectrogram_size)
+    except ValueError as e:
+        raise SystemExit('--spectrogram-size: ' + str(e))
+
+
+def write_song_spectrograms(st, slot, directory, name, size=(1200, 500)):
+    """The pictures of a finished song (plot_specs, util_audio.py:938-960: the reference's before / after comparison):
+    <directory>/<name>.song.png from an STFT of the song's samples in the pool, <name>.residual.png from the region of
+    the pool the slides wrote back, <name>.group<g>.png from its stem regions (g the reference group id of the row,
+    CLI_GROUPS) -- SongState.region_spectra(slot), so the state keeps residual and stems and the song is finished
+    (ValueError otherwise).  Every image: dB over 80 dB below the SONG's maximum (the slot's ref_mag, read on the
+    device), log frequency axis, `size` = (W, H) pixels.  ONE audio.spectrogram_levels launch and ONE audio.png_encode
+    call for all of them, on the walk's stream and ahead of the slot's release."""
+    residual, stems = st.region_spectra([slot])[0]
+    p, f0 = st.lp.p, st.region[slot]
+    song = audio.AudioBatch(st.samples[f0 * p.H:f0 * p.H + st.lens[slot]][None, :], p.N, p.H, sample_rate=p.sr).stft(False)
+    mags, kinds = [song.mag[0]], ['song']
+    if residual is not None:
+        mags.append(residual)
+        kinds.append('residual')
+    if stems is not None:
+        for row, g in zip(stems.unbind(0), CLI_GROUPS):
+            mags.append(row)
+            kinds.append('group%d' % g)
+    paths = [os.path.join(directory, '%s.%s.png' % (name, k)) for k in kinds]
+    audio.save_spectrograms(mags, paths, [st.refs['ref_mag'][slot]] * len(mags), size=size, sr=p.sr, n_fft=p.N)
+    for path in paths:
+        print('spectrogram -> %s' % path)
+
+
 def _same_rate(paths, pairs, rate, decode):
     """The queue's input without --sr: every (waveform, rate) of `pairs` as one channel, a file of another rate than
     `rate` refused."""
@@ -334,9 +388,10 @@ def main_songs(argv):
                          'took out of the song, 24-bit FLAC at the rate the model runs at')
     a = ap.parse_args(argv)
     _check_writer(a)
+    size = _spectrogram_size(a)
     os.makedirs(a.out_dir, exist_ok=True)
     keep, keep_stems = a.residual_dir is not None, a.stems_dir is not None
-    for d in (a.residual_dir, a.stems_dir):
+    for d in (a.residual_dir, a.stems_dir, a.spectrogram_dir):
         if d is not None:
             os.makedirs(d, exist_ok=True)
     stems = [os.path.splitext(os.path.basename(f))[0] for f in a.songs]
@@ -356,9 +411,13 @@ def main_songs(argv):
             first = next(wfs)
             rate, wfs = first[1], itertools.chain([first], wfs)
         wfs = _same_rate(a.songs, wfs, rate, a.decode)
+    draw = size is not None
+
+    def on_finish(i, slot, st):
+        write_song_spectrograms(st, slot, a.spectrogram_dir, stems[i], size)
     queue = iter_transcribe_songs(wfs, Hyperparams(N=2048, sr=rate), iters=a.iters, weights_dir=a.weights, guess=a.guess,
-                                  slots=a.slots, residual=keep, stems=keep_stems, groups=CLI_GROUPS,
-                                  instrument_model=a.instrument_model)
+                                  slots=a.slots, residual=keep or draw, stems=keep_stems or draw, groups=CLI_GROUPS,
+                                  instrument_model=a.instrument_model, on_finish=on_finish if draw else None)
     for item in queue:
         i, notes = item[0], item[1]
         out = os.path.join(a.out_dir, stems[i] + '.mid')
@@ -391,6 +450,9 @@ def main(argv=None):
         raise SystemExit('--residual needs --traversal song (independent windows have no song-level residual)')
     if a.stems_dir is not None and a.traversal != 'song':
         raise SystemExit('--stems-dir needs --traversal song (independent windows have no song-level stems)')
+    if a.spectrogram_dir is not None and a.traversal != 'song':
+        raise SystemExit('--spectrogram-dir needs --traversal song (independent windows have no song-level spectra)')
+    size = _spectrogram_size(a)
     wf, sr = next(_read_inputs([a.infile], a.decode))
     if a.sr is None:                             # the model at the file's rate
         wf, model_sr, file_sr = _mono(wf, sr, a.decode), sr, None
@@ -398,9 +460,18 @@ def main(argv=None):
         raise SystemExit('--sr: the rate must be positive')
     else:                                        # the file at the model's rate: resampled and downmixed on the device
         model_sr, file_sr = a.sr, sr
+    draw = size is not None
+    name = os.path.splitext(os.path.basename(a.infile))[0]
+
+    def on_finish(i, slot, st):
+        if not int(st.finished[slot]):
+            raise SystemExit('--spectrogram-dir: the walk stopped before the end of the song')
+        os.makedirs(a.spectrogram_dir, exist_ok=True)
+        write_song_spectrograms(st, slot, a.spectrogram_dir, name, size)
     got = transcribe(wf, Hyperparams(N=2048, sr=model_sr), iters=a.iters, weights_dir=a.weights, guess=a.guess,
-                     traversal=a.traversal, sr=file_sr, residual=a.residual is not None, stems=a.stems_dir is not None,
-                     groups=CLI_GROUPS, instrument_model=a.instrument_model)
+                     traversal=a.traversal, sr=file_sr, residual=a.residual is not None or draw,
+                     stems=a.stems_dir is not None or draw, groups=CLI_GROUPS, instrument_model=a.instrument_model,
+                     on_finish=on_finish if draw else None)
     notes = got[0]
     ev.write_midi(notes, a.outfile)
     print('%d notes -> %s' % (len(notes), a.outfile))
@@ -412,7 +483,7 @@ def main(argv=None):
         os.makedirs(a.stems_dir, exist_ok=True)
     write_song_audio(model_sr, residual=got[2] if a.residual is not None else None, residual_path=a.residual,
                      stems=got[-1] if a.stems_dir is not None else None, stems_dir=a.stems_dir,
-                     name=os.path.splitext(os.path.basename(a.infile))[0], flac=a.flac, format=a.format,
+                     name=name, flac=a.flac, format=a.format,
                      predictor=a.flac_predictor)
 
 

@@ -270,6 +270,45 @@ int amt_pcm_pack_ragged(const float *wave, const long long *base, const long lon
                         void *stream);
 
 /* ------------------------------------------------------------------------ *
+ * Spectrogram images on the device (replaces the librosa.display.specshow + matplotlib savefig of
+ * audio_complete.plot_spec, util_audio.py:509-518, and plot_specs, util_audio.py:938-960)
+ *
+ * Two stages: magnitudes -> 8-bit level images (a comparison against 255 thresholds, no logarithm), and 8-bit images ->
+ * complete PNG files (row filters, deflate with run-length matches and stored / fixed / dynamic Huffman blocks, Adler-32,
+ * CRC-32, all on the device).  The rule of both lives in csrc/amt_png_core.h.  DESIGN.md 26.
+ * ------------------------------------------------------------------------ */
+/* The dB picture of audio_complete.D (util_audio.py:176-180) as plot_spec shows it (util_audio.py:509-518), for n
+ * spectrograms in ONE launch.  mag: float32, frame-major; image i reads mag[mag_base + t ldf + f].  image_meta int64
+ * [n][10], device: mag_base (floats), T, ldf, F, W, H, first int of its row table in `tables`, first int of its column
+ * table, first output byte, reserved.  A row table is H pairs [bin lo, bin hi), row 0 the top of the image; a column
+ * table is W pairs [frame lo, frame hi).  Pixel (j, i) = the number of k in 1 .. 255 with v >= thr[k - 1] * ref[image] (one
+ * float32 product, rounded to nearest), v the float32 maximum over its bins and frames, NaN skipped, starting from 0.
+ * thr float32 [255] ascending, ref float32 [n]: device.  A ref that is not finite or below 2^-100 gives an all-zero
+ * image.  max_w, max_h (host) size the grid.  Nothing outside mag[0 .. mag_floats), tables[0 .. table_ints) or
+ * out[0 .. out_bytes) is touched whatever the tables hold: an image whose geometry would leave them is left unwritten,
+ * a table entry outside its axis is clamped.  AMT_E_INVALID: a NULL pointer, n outside 1 .. 65535, max_w or max_h
+ * outside 1 .. 16384, a negative size. */
+int amt_spec_levels_ragged(const float *mag, long long mag_floats, const long long *image_meta, int n, int max_w,
+                           int max_h, const int *tables, long long table_ints, const float *thr, const float *ref,
+                           unsigned char *out, long long out_bytes, void *stream);
+/* Bytes of the largest PNG file amt_png_encode_ragged writes for a w x h image (palette: 0 or 1); negative
+ * (AMT_E_INVALID) for w or h outside 1 .. 16384. */
+long long amt_png_file_bound(int w, int h, int palette);
+/* Scratch bytes of amt_png_encode_ragged for the n images of image_meta (host); negative for what that call refuses. */
+long long amt_png_scratch_bytes(const long long *image_meta, int n);
+/* matplotlib's savefig of plot_spec (util_audio.py:509-518) without the figure: n 8-bit images -> n complete PNG files
+ * in one call (pieces -> sizes -> scan -> gather, as amt_flac_encode_ragged).  The call uploads its two small tables
+ * into the scratch and waits for that upload on `stream`; the kernels are only enqueued.  image_meta int64 [n][3], HOST: first
+ * byte of the image in pix, W, H; the image is H rows of W bytes.  pix [pix_bytes], device.  palette: 768 device bytes
+ * (R, G, B of 256 entries; colour type 3), or NULL (greyscale, colour type 0).  out [out_bytes], device: file i at
+ * [file_off[i], file_off[i + 1]); file_off int64 [n + 1], device.  out_bytes >= the sum of amt_png_file_bound over the
+ * images and scratch_bytes >= amt_png_scratch_bytes, else AMT_E_SHAPE.  AMT_E_INVALID with nothing written: a NULL
+ * pointer (palette excepted), a scratch that is not 16-byte aligned, n outside 1 .. 65535, W or H outside 1 .. 16384, an image outside pix. */
+int amt_png_encode_ragged(const unsigned char *pix, long long pix_bytes, const long long *image_meta, int n,
+                          const unsigned char *palette, void *scratch, long long scratch_bytes, unsigned char *out,
+                          long long out_bytes, long long *file_off, void *stream);
+
+/* ------------------------------------------------------------------------ *
  * Spectral subtraction (replaces audio_complete.subtract, util_audio.py:221-259)
  * ------------------------------------------------------------------------ */
 typedef struct amt_subtract_args {
