@@ -123,6 +123,9 @@ PROTOTYPES = {
     'amt_png_file_bound': (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     'amt_png_scratch_bytes': (C.c_longlong, [vp, C.c_int]),
     'amt_png_encode_ragged': (C.c_int, [vp, C.c_longlong, vp, C.c_int, vp, vp, C.c_longlong, vp, C.c_longlong, vp, vp]),
+    'amt_score_scratch_bytes': (C.c_longlong, [C.c_longlong, C.c_longlong]),
+    'amt_score_check_notes': (C.c_int, [vp, vp, C.c_longlong]),
+    'amt_score_pairs': (C.c_int, [vp, vp]),                      # (amt_score_args *: score.ScoreArgs)
     'amt_istft': (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp,
                             C.c_size_t, vp]),
     'amt_istft_ragged': (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, vp, vp, C.c_longlong, vp]),

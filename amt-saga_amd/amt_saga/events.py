@@ -138,11 +138,32 @@ def _read_vlq(buf, i):
             return v, i
 
 
-def read_midi(path):
+def _tempo_seconds(tempos, div):
+    """tick -> seconds under a tempo map: tempos = [(tick, us per quarter)] from every track, in file order.  120 bpm
+    holds until the first event; of two events on one tick the later one in the file holds."""
+    marks = [(0, TEMPO_US_PER_QUARTER)] + sorted(tempos, key=lambda m: m[0])         # (stable: file order within a tick)
+    ticks, rates, starts = [], [], []
+    for tick, tempo in marks:
+        if ticks and tick == ticks[-1]:
+            rates[-1] = tempo
+            continue
+        starts.append(starts[-1] + (tick - ticks[-1]) * rates[-1] / float(div) * 1e-6 if ticks else 0.0)
+        ticks.append(tick)
+        rates.append(tempo)
+
+    def seconds(t):
+        k = int(np.searchsorted(ticks, t, side='right')) - 1
+        return starts[k] + (t - ticks[k]) * rates[k] / float(div) * 1e-6
+    return seconds
+
+
+def read_midi(path, full=False):
     """Standard MIDI File reader for the note content note_sequence.save() / write_midi produce:
     format 0/1, ticks-per-quarter division, set-tempo meta events (the first tempo applies to the whole
     file, as in the single-tempo files magenta writes), running status, note-on with velocity 0 as
-    note-off, program changes.  Returns notes sorted by start time (seconds)."""
+    note-off, program changes.  Returns notes sorted by start time (seconds).
+    full=True (gold files, whose tempo changes): every set-tempo event of every track is honoured -- one tempo map for
+    the file, as format 1 keeps it -- and each note also carries its `channel`."""
     data = open(path, 'rb').read()
     if data[:4] != b'MThd':
         raise ValueError('not a Standard MIDI File')
@@ -152,6 +173,7 @@ def read_midi(path):
     pos = 14
     raw_notes = []
     tempo = None
+    tempos = []
     for _ in range(ntr):
         if data[pos:pos + 4] != b'MTrk':
             raise ValueError('missing MTrk chunk')
@@ -171,6 +193,8 @@ def read_midi(path):
                 ln2, i = _read_vlq(trk, i + 1)
                 if typ == 0x51 and tempo is None:
                     tempo = int.from_bytes(trk[i:i + 3], 'big')
+                if typ == 0x51:
+                    tempos.append((t, int.from_bytes(trk[i:i + 3], 'big')))
                 i += ln2
                 continue
             if status in (0xF0, 0xF7):                           # sysex
@@ -188,11 +212,17 @@ def read_midi(path):
                     open_notes.setdefault((ch, p), []).append((t, v))
                 elif open_notes.get((ch, p)):
                     t0, v0 = open_notes[(ch, p)].pop(0)     # overlapping same-pitch notes: FIFO
-                    raw_notes.append((p, prog.get(ch, 0), v0, t0, t))
+                    raw_notes.append((p, prog.get(ch, 0), v0, t0, t, ch))
             else:
                 i += 2
+    if full:
+        seconds = _tempo_seconds(tempos, div)
+        notes = [dict(pitch=p, program=pr, velocity=v, start=seconds(t0), end=seconds(t1), channel=ch)
+                 for p, pr, v, t0, t1, ch in raw_notes]
+        notes.sort(key=lambda n: (n['start'], n['pitch'], n['program']))
+        return notes
     us_per_tick = (tempo if tempo is not None else TEMPO_US_PER_QUARTER) / float(div)
     notes = [dict(pitch=p, program=pr, velocity=v, start=t0 * us_per_tick * 1e-6, end=t1 * us_per_tick * 1e-6)
-             for p, pr, v, t0, t1 in raw_notes]
+             for p, pr, v, t0, t1, _ in raw_notes]
     notes.sort(key=lambda n: (n['start'], n['pitch'], n['program']))
     return notes

@@ -34,6 +34,12 @@ provide for the inference direction:
     .residual.png and .group<g>.png (plot_specs, util_audio.py:938-960), levels and PNG files made on the device
     (audio.save_spectrograms), all against the song's own maximum.
 
+    --gold GOLD.mid (one file) / --gold-dir DIR (with --songs): score what was written against gold MIDI (amt_saga.score,
+    DESIGN 27).  One file: <outfile stem>.score.json beside the .mid.  --songs: when the last song has been written, every
+    song with a <stem>.mid in DIR is scored in ONE device call -- <stem>.score.json beside each .mid and scores.json for
+    the collection; a song without a gold file is named on stderr and left out.  The .mid files as written are what is
+    scored, so `python -m amt_saga.score` on the same files gives the same counts.
+
     --instrument-model NAME (both modes): the instrument head is the reference's model NAME (training.py:466-477; one of
     loop.INSTRUMENT_MODELS), fed the recipe arrays that model was trained on; the default is the plain CQT model.
 
@@ -49,7 +55,7 @@ import sys
 import numpy as np
 import torch
 
-from . import audio, events as ev, flac as host_flac, png as host_png, wav as host_wav
+from . import audio, events as ev, flac as host_flac, png as host_png, score as host_score, wav as host_wav
 from .hyperparams import Hyperparams
 from .loop import INSTRUMENT_MODELS, TranscriptionLoop
 
@@ -362,6 +368,25 @@ def write_song_spectrograms(st, slot, directory, name, size=(1200, 500)):
         print('spectrogram -> %s' % path)
 
 
+def write_scores(names, mid_paths, gold_paths, collection_path=None):
+    """Score the written .mid files against their gold files in one device call (score.score_files with the loop's
+    instrument groups): <mid path minus its extension>.score.json per song, and collection_path (scores.json) for the
+    collection when it is given.  Returns the collection's record."""
+    import json
+    counts, summ = host_score.score_files(mid_paths, gold_paths, group=host_score.loop_groups())
+    pairs, whole = host_score.report(names, mid_paths, gold_paths, counts, summ)
+    for mid, rec in zip(mid_paths, pairs):
+        out = os.path.splitext(mid)[0] + '.score.json'
+        with open(out, 'w') as f:
+            json.dump(rec, f, sort_keys=True)
+        print('score -> %s' % out)
+    if collection_path is not None:
+        with open(collection_path, 'w') as f:
+            json.dump(dict(whole, songs=pairs), f, sort_keys=True)
+        print('scores -> %s' % collection_path)
+    return whole
+
+
 def _same_rate(paths, pairs, rate, decode):
     """The queue's input without --sr: every (waveform, rate) of `pairs` as one channel, a file of another rate than
     `rate` refused."""
@@ -386,9 +411,15 @@ def main_songs(argv):
     _shared_options(ap, 'rate the model runs at; every file is resampled to it from its own rate (mixed rates allowed)',
                     help='write <stem>.group<g>.flac per song and instrument group as it finishes: what the subtractions '
                          'took out of the song, 24-bit FLAC at the rate the model runs at')
+    ap.add_argument('--gold-dir', default=None, metavar='DIR',
+                    help='when the last song has been written, score every song that has a <stem>.mid in DIR against it, '
+                         'all in one device call: <stem>.score.json beside each .mid and scores.json in --out-dir; a song '
+                         'without a gold file is named on stderr and left out')
     a = ap.parse_args(argv)
     _check_writer(a)
     size = _spectrogram_size(a)
+    if a.gold_dir is not None and not os.path.isdir(a.gold_dir):
+        raise SystemExit('--gold-dir: %s is not a directory' % a.gold_dir)
     os.makedirs(a.out_dir, exist_ok=True)
     keep, keep_stems = a.residual_dir is not None, a.stems_dir is not None
     for d in (a.residual_dir, a.stems_dir, a.spectrogram_dir):
@@ -427,6 +458,16 @@ def main_songs(argv):
                          residual_path=os.path.join(a.residual_dir, stems[i] + '.residual.' + a.format) if keep else None,
                          stems=item[-1] if keep_stems else None, stems_dir=a.stems_dir, name=stems[i], flac=a.flac,
                          format=a.format, predictor=a.flac_predictor)
+    if a.gold_dir is not None:
+        scored = []
+        for stem in stems:
+            gold = os.path.join(a.gold_dir, stem + '.mid')
+            if os.path.isfile(gold):
+                scored.append((stem, os.path.join(a.out_dir, stem + '.mid'), gold))
+            else:
+                print('%s: no gold file in %s, left out of the scores' % (stem, a.gold_dir), file=sys.stderr)
+        if scored:
+            write_scores(*zip(*scored), collection_path=os.path.join(a.out_dir, 'scores.json'))
 
 
 def main(argv=None):
@@ -444,8 +485,12 @@ def main(argv=None):
     _shared_options(ap, 'rate the model runs at; the file is resampled to it from its own rate', metavar='DIR',
                     help='with --traversal song: write <input stem>.group<g>.flac per instrument group, what the '
                          'subtractions took out of the song, 24-bit FLAC at the rate the model runs at')
+    ap.add_argument('--gold', default=None, metavar='GOLD.mid',
+                    help='score the written file against this gold MIDI file: <outfile stem>.score.json beside it')
     a = ap.parse_args(argv)
     _check_writer(a)
+    if a.gold is not None and not os.path.isfile(a.gold):
+        raise SystemExit('--gold: %s: no such file' % a.gold)
     if a.residual is not None and a.traversal != 'song':
         raise SystemExit('--residual needs --traversal song (independent windows have no song-level residual)')
     if a.stems_dir is not None and a.traversal != 'song':
@@ -485,6 +530,8 @@ def main(argv=None):
                      stems=got[-1] if a.stems_dir is not None else None, stems_dir=a.stems_dir,
                      name=name, flac=a.flac, format=a.format,
                      predictor=a.flac_predictor)
+    if a.gold is not None:
+        write_scores([name], [a.outfile], [a.gold])
 
 
 if __name__ == '__main__':

@@ -309,6 +309,50 @@ int amt_png_encode_ragged(const unsigned char *pix, long long pix_bytes, const l
                           long long out_bytes, long long *file_off, void *stream);
 
 /* ------------------------------------------------------------------------ *
+ * Scoring transcriptions against gold notes (stands where the reference's users call mir_eval.transcription on the
+ * MIDI/audio pairs it trains on, main.py:7).  The rule lives in csrc/amt_score_core.h.  DESIGN.md 27.
+ *
+ * Times are int64 microseconds, rint(seconds * 1e6) made on the host.  A pair is an estimated and a reference note list,
+ * a note {pitch 0..127, program 0..127, on, off}, both lists sorted by (pitch, on, off, program).  An estimate e matches
+ * a reference r when e.pitch == r.pitch and |e.on - r.on| <= 50000; in the offset variants also |e.off - r.off| <=
+ * max(50000, (r.off - r.on) / 5), an integer division taken as 0 when r.off <= r.on; in the program variants also
+ * group[e.program] == group[r.program].  The true positives of a variant are the size of a MAXIMUM-cardinality
+ * matching of its graph (not of a first-fit pass).  Frame k >= 0 is the instant 10000 k us; cell (k, pitch) of a list is
+ * set when a note of that pitch has on <= 10000 k < off; n_frames counts the k with 10000 k below the largest off of
+ * either list.  Each pair yields int64 [10]: n_est, n_ref, tp_on, tp_onoff, tp_on_prog, tp_onoff_prog, frame_tp
+ * (est & ref), frame_fp (est & ~ref), frame_fn (~est & ref), n_frames.
+ * ------------------------------------------------------------------------ */
+typedef struct amt_score_args {
+    const int32_t *est_pitch, *est_program;   /* device [n_est_total]: the estimates of all pairs back to back */
+    const int64_t *est_on, *est_off;
+    const int32_t *ref_pitch, *ref_program;   /* device [n_ref_total] */
+    const int64_t *ref_on, *ref_off;
+    const int64_t *est_offsets_host;          /* HOST [n_pairs + 1]: pair i holds estimates [est_offsets[i], est_offsets[i + 1]) */
+    const int64_t *ref_offsets_host;          /* HOST [n_pairs + 1] */
+    const int64_t *est_offsets, *ref_offsets; /* device [n_pairs + 1]: the same numbers, what the kernel reads */
+    const int32_t *group;                     /* device [128]: program -> group of the program variants */
+    void          *scratch;                   /* device, 16-byte aligned: owner / visited / stack of the matchings */
+    int64_t        scratch_bytes;             /* >= amt_score_scratch_bytes(est_offsets[n_pairs], ref_offsets[n_pairs]) */
+    int64_t       *out;                       /* device [n_pairs][10] */
+    int64_t        n_pairs;
+} amt_score_args;
+/* Scratch bytes of amt_score_pairs for that many notes per side over the whole call; negative (AMT_E_INVALID) for a
+ * negative count or one above 2^40. */
+long long amt_score_scratch_bytes(long long n_est_total, long long n_ref_total);
+/* HOST arrays [n]: AMT_OK when every pitch and every program lies in 0..127, else AMT_E_INVALID.  The caller runs it on
+ * what it is about to upload: the kernel masks a program and never indexes by a pitch, so a bad note costs a count,
+ * never a fault, but it has no meaning under the rule. */
+int amt_score_check_notes(const int32_t *pitch, const int32_t *program, long long n);
+/* Any number of pairs in ONE launch; out is zeroed and the kernel enqueued on `stream`, nothing is waited for.  The work
+ * item is one (pair, pitch): four waves find the four maximum matchings by augmenting paths with the candidates of a
+ * reference spread over the lanes, a fifth sweeps the frames.  Lists of any length and augmenting paths of any length:
+ * the matcher's arrays are in `scratch`.  The kernel reads the device offsets and holds every range inside the arrays
+ * whatever they say; lists that are not sorted give other counts, never a fault.  All checks come before any HIP call.
+ * AMT_E_INVALID: a NULL pointer, a scratch that is not 16-byte aligned, n_pairs < 0 or above 2^33, host offsets that
+ * begin below 0 or decrease, a pair with more than 2^31 - 1 notes on a side.  AMT_E_SHAPE: scratch_bytes too small. */
+int amt_score_pairs(const amt_score_args *args, void *stream);
+
+/* ------------------------------------------------------------------------ *
  * Spectral subtraction (replaces audio_complete.subtract, util_audio.py:221-259)
  * ------------------------------------------------------------------------ */
 typedef struct amt_subtract_args {
