@@ -1095,15 +1095,29 @@ def _file_view(buf, base, frames, channels):
     return v if channels == 1 else v.view(frames, channels)
 
 
-def _ragged_layout(sigs):
+def _ragged_layout(sigs, spans=None):
     """The input layout of amt_flac_encode_ragged, amt_pcm_peak_ragged and amt_pcm_pack_ragged: 1-d float32 signals
     that lie anywhere in one address space, named by one pointer and two tables.  Returns (anchor, base, lens):
     anchor = the lowest data_ptr of the signals that have samples, base[i] = signal i's offset from it in floats (0 for
-    an empty signal, whose pointer means nothing), lens[i] = its length.  No signal has samples: anchor is None."""
-    lens = [int(s.numel()) for s in sigs]
+    an empty signal, whose pointer means nothing), lens[i] = its length.  No signal has samples: anchor is None.
+    amt_spec_levels_ragged and amt_png_encode_ragged take their tensors the same way: spans[i] = the elements from
+    tensor i's first to its last, taken for lens; base counts in the tensor's own element size, and the extent the
+    call is told is the largest base + span."""
+    lens = [int(s.numel()) for s in sigs] if spans is None else list(spans)
     live = [s.data_ptr() for s, l in zip(sigs, lens) if l]
     anchor = min(live) if live else None
-    return anchor, [(s.data_ptr() - anchor) // 4 if l else 0 for s, l in zip(sigs, lens)], lens
+    base = [(s.data_ptr() - anchor) // s.element_size() if l else 0 for s, l in zip(sigs, lens)]
+    return anchor, base, lens
+
+
+def _fetch_split(who, out, offsets, limit):
+    """The tail of flac_encode and png_encode: the int64 device offsets [n + 1] to the host, a refusal in `who`'s words if
+    the last lies behind the `limit` bytes of the device buffer `out`, ONE device-to-host copy, the n pieces between."""
+    off = offsets.cpu().tolist()
+    if off[-1] > limit:
+        raise RuntimeError('%s: the %s need %d bytes, the buffer has %d' % (who + (off[-1], limit)))
+    data = out[:off[-1]].cpu().numpy().tobytes()
+    return [data[a:b] for a, b in zip(off, off[1:])]
 
 
 def _device_signals(waves):
@@ -1197,13 +1211,10 @@ def flac_encode(waves, sr, bps=24, blocksize=4096, predictor='fixed', lpc_order=
     sigs = _device_signals(waves)
     out, stream_off, minmax, md5, _ = flac_encode_streams(sigs, bps=bps, blocksize=blocksize, predictor=predictor,
                                                           lpc_order=lpc_order)
-    off = stream_off.cpu().tolist()
+    frames = _fetch_split(('flac_encode', 'streams'), out, stream_off, out.numel())
     minmax, md5 = minmax.cpu().tolist(), md5.cpu().numpy()
-    if off[-1] > out.numel():
-        raise RuntimeError('flac_encode: the streams need %d bytes, the buffer has %d' % (off[-1], out.numel()))
-    data = out[:off[-1]].cpu().numpy().tobytes()
-    return [flac_stream_header(s.numel(), sr, bps, blocksize, minmax[i][0], minmax[i][1], md5[i].tobytes())
-            + data[off[i]:off[i + 1]] for i, s in enumerate(sigs)]
+    return [flac_stream_header(s.numel(), sr, bps, blocksize, minmax[i][0], minmax[i][1], md5[i].tobytes()) + frames[i]
+            for i, s in enumerate(sigs)]
 
 
 def save_flac(waves, paths, sr, bps=24, predictor='fixed', lpc_order=12):
@@ -1497,18 +1508,17 @@ def spectrogram_levels(mags, refs, size=(1200, 500), axis='log', sr=44100, n_fft
     if len({m.device for m in mags}) != 1:
         raise ValueError('Invalid Input shape. Expected: spectrograms of one device . Got: several')
     lib, dev = _lib.load(), mags[0].device
-    anchor = min(m.data_ptr() for m in mags)
-    tables, at, meta, out_at, extent = [], {}, [], 0, 0
-    for m, (W, H) in zip(mags, sizes):
+    anchor, bases, spans = _ragged_layout(mags, [(int(m.shape[0]) - 1) * int(_stride0(m)) + F for m in mags])
+    extent = max(b + l for b, l in zip(bases, spans))
+    tables, at, meta, out_at = [], {}, [], 0
+    for m, base, (W, H) in zip(mags, bases, sizes):
         T, ldf = int(m.shape[0]), int(_stride0(m))
         for key, build in ((('r', H), lambda: _png.axis_rows(F, H, sr, n_fft, axis, fmin)),
                            (('c', T, W), lambda: _png.axis_cols(T, W))):
             if key not in at:
                 at[key] = sum(t.size for t in tables)
                 tables.append(build().reshape(-1))
-        base = (m.data_ptr() - anchor) // 4
         meta.append([base, T, ldf, F, W, H, at[('r', H)], at[('c', T, W)], out_at, 0])
-        extent = max(extent, base + (T - 1) * ldf + F)
         out_at += W * H
     host = np.concatenate(tables).astype(np.int32)
     d_tab, d_meta, d_thr = to_dev(host, torch.int32), to_dev(np.asarray(meta, np.int64), torch.int64), to_dev(thr)
@@ -1537,12 +1547,8 @@ def png_encode(images, palette='cubehelix'):
     256-entry `palette` ('cubehelix') or greyscale ('gray').  Filters, deflate, Adler-32 and CRC-32 run on the device
     (amt_png_encode_ragged, ONE call for the whole list on the current stream); only the finished files are copied
     back, in one copy after the sizes.  The bytes are those of the rule in DESIGN 26, whatever the batch."""
-    out, file_off, bound, n = _png_encode(images, palette)
-    off = file_off.cpu().tolist()
-    if off[-1] > bound:
-        raise RuntimeError('png_encode: the files need %d bytes, the buffer has %d' % (off[-1], bound))
-    data = out[:off[-1]].cpu().numpy().tobytes()
-    return [data[off[i]:off[i + 1]] for i in range(n)]
+    out, file_off, bound, _ = _png_encode(images, palette)
+    return _fetch_split(('png_encode', 'files'), out, file_off, bound)
 
 
 def _png_encode(images, palette):
@@ -1563,13 +1569,13 @@ def _png_encode(images, palette):
         raise ValueError('Invalid Input shape. Expected: images of one device . Got: several')
     items = [im if im.is_contiguous() else im.contiguous() for im in items]
     lib, dev, n = _lib.load(), items[0].device, len(items)
-    anchor = min(im.data_ptr() for im in items)
+    anchor, bases, spans = _ragged_layout(items)
+    extent = max(b + l for b, l in zip(bases, spans))
     meta = (C.c_longlong * (3 * n))()
-    extent = bound = 0
+    bound = 0
     for i, im in enumerate(items):
         H, W = int(im.shape[0]), int(im.shape[1])
-        meta[3 * i], meta[3 * i + 1], meta[3 * i + 2] = im.data_ptr() - anchor, W, H
-        extent = max(extent, im.data_ptr() - anchor + W * H)
+        meta[3 * i], meta[3 * i + 1], meta[3 * i + 2] = bases[i], W, H
         bound += int(lib.amt_png_file_bound(W, H, int(pal is not None)))
     need = int(lib.amt_png_scratch_bytes(meta, n))
     if need < 0:

@@ -48,6 +48,8 @@
 #include "amt_common.h"
 #include "amt_flac_common.h"
 #include "amt_flac_lpc_core.h"
+#include "amt_scratch.h"
+#include "amt_wg.h"
 
 #define AMT_FL_THREADS 256
 #define AMT_FL_MAXBS 4096
@@ -59,10 +61,6 @@ typedef unsigned long long fl_u64;
 
 static __host__ __device__ inline long long fl_bound(int blocksize, int bps) {
     return 13 + (8 + (long long)blocksize * bps + 7) / 8 + 2;
-}
-
-__device__ __forceinline__ long long fl_len(long long l, long long max_len) {
-    return l < 0 ? 0 : (l > max_len ? max_len : l);
 }
 
 // the one quantiser of the frame and the MD5 kernel
@@ -120,29 +118,6 @@ __device__ __forceinline__ void fl_put(unsigned *buf, unsigned pos, int n, unsig
 }
 
 __device__ __forceinline__ unsigned fl_byte(const unsigned *buf, int i) { return (buf[i >> 2] >> (24 - 8 * (i & 3))) & 0xffu; }
-
-// exclusive prefix sum over the 256 threads; lds: 4 words.  Every thread gets the block total as well.
-__device__ __forceinline__ fl_u64 fl_block_scan(fl_u64 v, fl_u64 *lds, fl_u64 *total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    fl_u64 incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const fl_u64 t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    __syncthreads();                                             // the previous use of lds is over
-    if (lane == 63) lds[w] = incl;
-    __syncthreads();
-    fl_u64 before = 0, all = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const fl_u64 t = lds[i];
-        if (i < w) before += t;
-        all += t;
-    }
-    *total = all;
-    return before + incl - v;
-}
 
 // The cost search of one predictor of order o over the block: the thread's sums of u >> k over its samples [i0, i1),
 // the butterflies, the best k of every partition of every level into kbest_o, the level totals.  Returns the smallest
@@ -202,8 +177,7 @@ __device__ __forceinline__ fl_u64 fl_cost_search(const Resid &resid, int o, fl_u
     // totals of the nine levels over the block
 #pragma unroll
     for (int lg = 0; lg <= 8; ++lg) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) c[lg] += __shfl_xor(c[lg], off, 64);
+        c[lg] = amt_wave_reduce(c[lg], amt_sum{});
         if (lane == 0) red[w][lg] = c[lg];
     }
     __syncthreads();
@@ -233,7 +207,7 @@ __device__ __forceinline__ void fl_emit_codes(const Resid &resid, int o, int i0,
     unsigned mine = leader ? 5u : 0u;
     for (int i = max(i0, o); i < i1; ++i) mine += (fl_zig(resid(i, bad)) >> k) + 1u + k;
     fl_u64 total;
-    unsigned pos = at + (unsigned)fl_block_scan(mine, scan_lds, &total);
+    unsigned pos = at + (unsigned)amt_block_scan<fl_u64, AMT_FL_THREADS>(mine, scan_lds, &total);
     if (leader) { fl_put(bits, pos, 5, (unsigned)k); pos += 5; }
     for (int i = max(i0, o); i < i1; ++i) {
         const unsigned u = fl_zig(resid(i, bad));
@@ -268,7 +242,7 @@ __global__ __launch_bounds__(AMT_FL_THREADS) void flac_frame_kernel(
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int b = blockIdx.y;
     const long long f = blockIdx.x;
-    const long long n_s = fl_len(len[b], max_len);
+    const long long n_s = amt_clamp_len(len[b], max_len);
     const long long nframes = (n_s + blocksize - 1) / blocksize;
     const long long slot = (long long)b * frames_max + f;
     if (f >= nframes) {                                           // past this signal's last frame
@@ -321,8 +295,7 @@ __global__ __launch_bounds__(AMT_FL_THREADS) void flac_frame_kernel(
             }
 #pragma unroll
             for (int l = 0; l < FLL_LAGS; ++l) {
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) acc[l] += __shfl_xor(acc[l], off, 64);
+                acc[l] = amt_wave_reduce(acc[l], amt_sum{});
                 if (lane == 0) acorr[w][l] = acc[l];
             }
             __syncthreads();
@@ -445,7 +418,7 @@ __global__ __launch_bounds__(AMT_FL_THREADS) void flac_frame_offsets_kernel(
     __shared__ fl_u64 lds[4];
     __shared__ int mm[2][4];
     const int tid = threadIdx.x, b = blockIdx.x;
-    const long long n_s = fl_len(len[b], max_len);
+    const long long n_s = amt_clamp_len(len[b], max_len);
     const long long nframes = (n_s + blocksize - 1) / blocksize;
     fl_u64 carry = 0;
     int mn = 0x7fffffff, mx = 0;
@@ -453,7 +426,7 @@ __global__ __launch_bounds__(AMT_FL_THREADS) void flac_frame_offsets_kernel(
         const long long f = f0 + tid;
         const long long v = f < nframes ? frame_bytes[(long long)b * frames_max + f] : 0;
         fl_u64 total;
-        const fl_u64 ex = fl_block_scan((fl_u64)v, lds, &total);
+        const fl_u64 ex = amt_block_scan<fl_u64, AMT_FL_THREADS>((fl_u64)v, lds, &total);
         if (f < nframes) {
             frame_off[(long long)b * frames_max + f] = (long long)(carry + ex);
             mn = min(mn, (int)v);
@@ -461,11 +434,8 @@ __global__ __launch_bounds__(AMT_FL_THREADS) void flac_frame_offsets_kernel(
         }
         carry += total;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        mn = min(mn, __shfl_xor(mn, off, 64));
-        mx = max(mx, __shfl_xor(mx, off, 64));
-    }
+    mn = amt_wave_reduce(mn, amt_min{});
+    mx = amt_wave_reduce(mx, amt_max{});
     if ((tid & 63) == 0) { mm[0][tid >> 6] = mn; mm[1][tid >> 6] = mx; }
     __syncthreads();
     if (tid == 0) {
@@ -486,7 +456,7 @@ __global__ __launch_bounds__(AMT_FL_THREADS) void flac_stream_offsets_kernel(lon
         const int i = i0 + tid;
         const fl_u64 v = i < n ? (fl_u64)stream_off[i + 1] : 0;
         fl_u64 total;
-        const fl_u64 ex = fl_block_scan(v, lds, &total);
+        const fl_u64 ex = amt_block_scan<fl_u64, AMT_FL_THREADS>(v, lds, &total);
         if (i < n) stream_off[i + 1] = (long long)(carry + ex + v);
         carry += total;
     }
@@ -519,7 +489,7 @@ __global__ __launch_bounds__(AMT_FL_MD5_LANES) void flac_md5_kernel(
     __shared__ unsigned m[64];
     const int lane = threadIdx.x;
     const int b = blockIdx.x;
-    const long long n_s = fl_len(len[b], max_len);
+    const long long n_s = amt_clamp_len(len[b], max_len);
     const float *x = wave + base[b];
     const int nb = bps >> 3;                                      // bytes per sample, blocks per 64 samples
     const unsigned mask = (1u << bps) - 1u;
@@ -577,8 +547,9 @@ long long amt_flac_frame_bound(int blocksize, int bps) {
 long long amt_flac_scratch_bytes(int n, long long max_len, int blocksize, int bps) {
     const long long bound = amt_flac_frame_bound(blocksize, bps);
     if (bound < 0 || n < 1 || max_len < 0) return AMT_E_INVALID;
-    const long long slots = (long long)n * fl_frames(max_len, blocksize);
-    return (slots * bound + 7) / 8 * 8 + 8 * slots;
+    amt_flac_layout L;
+    const long long need = amt_flac_make_layout(nullptr, n, fl_frames(max_len, blocksize), bound, &L);
+    return need < 0 ? AMT_E_INVALID : need;
 }
 
 // both entries: lpc_order 0 = the fixed predictors alone
@@ -595,31 +566,30 @@ static int fl_encode(const float *wave, const long long *base, const long long *
     if (bound < 0) return AMT_E_INVALID;
     const long long frames = fl_frames(max_len, blocksize);
     if (first_frame + frames >= (1LL << 31)) return AMT_E_INVALID;
-    const long long slots = (long long)n * frames;
-    if (scratch_bytes < amt_flac_scratch_bytes(n, max_len, blocksize, bps) || out_bytes < frames * bound)
-        return AMT_E_SHAPE;
-
-    long long *frame_off = (long long *)(scratch + (slots * bound + 7) / 8 * 8);
+    amt_flac_layout L;
+    const long long need = amt_flac_make_layout(scratch, n, frames, bound, &L);
+    if (need < 0) return AMT_E_INVALID;
+    if (scratch_bytes < need || out_bytes < frames * bound) return AMT_E_SHAPE;
     if (frames > 0) {
         const dim3 grid((unsigned)frames, (unsigned)n);
         if (lpc_order > 0)
             flac_frame_kernel<true><<<grid, AMT_FL_THREADS, 0, stream>>>(wave, base, len, max_len, blocksize, bps,
-                                                                         first_frame, frames, scratch, bound,
+                                                                         first_frame, frames, L.slots, bound,
                                                                          frame_bytes, lpc_order);
         else
             flac_frame_kernel<false><<<grid, AMT_FL_THREADS, 0, stream>>>(wave, base, len, max_len, blocksize, bps,
-                                                                          first_frame, frames, scratch, bound,
+                                                                          first_frame, frames, L.slots, bound,
                                                                           frame_bytes, 0);
         AMT_LAUNCH_CHECK();
     }
-    flac_frame_offsets_kernel<<<n, AMT_FL_THREADS, 0, stream>>>(len, max_len, blocksize, frames, frame_bytes, frame_off,
-                                                                stream_off, frame_minmax);
+    flac_frame_offsets_kernel<<<n, AMT_FL_THREADS, 0, stream>>>(len, max_len, blocksize, frames, frame_bytes,
+                                                                L.frame_off, stream_off, frame_minmax);
     AMT_LAUNCH_CHECK();
     flac_stream_offsets_kernel<<<1, AMT_FL_THREADS, 0, stream>>>(stream_off, n);
     AMT_LAUNCH_CHECK();
     if (frames > 0) {
         const dim3 grid((unsigned)frames, (unsigned)n);
-        flac_compact_kernel<<<grid, AMT_FL_THREADS, 0, stream>>>(scratch, bound, frames, frame_bytes, frame_off,
+        flac_compact_kernel<<<grid, AMT_FL_THREADS, 0, stream>>>(L.slots, bound, frames, frame_bytes, L.frame_off,
                                                                  stream_off, out, out_bytes);
         AMT_LAUNCH_CHECK();
     }

@@ -225,13 +225,12 @@ __global__ __launch_bounds__(AMT_FD_LANES) void flacdec_md5_kernel(
     }
 }
 
-static long long fd_round8(long long v) { return (v + 7) / 8 * 8; }
-
 extern "C" {
 
 long long amt_flac_decode_scratch_bytes(long long n_cand, long long slot_ints) {
-    if (n_cand < 0 || slot_ints < 0 || n_cand > (1LL << 40) || slot_ints > (1LL << 56)) return AMT_E_INVALID;
-    return fd_round8(4 * slot_ints) + 16 * n_cand;
+    fd_layout L;
+    const fd_i64 need = fd_make_layout(nullptr, n_cand, slot_ints, &L);
+    return need < 0 ? AMT_E_INVALID : need;
 }
 
 int amt_flac_decode_ragged(const unsigned char *data, long long data_bytes, const long long *stream_meta, int n,
@@ -245,25 +244,22 @@ int amt_flac_decode_ragged(const unsigned char *data, long long data_bytes, cons
     if (n < 1 || n_cand < 0 || data_bytes < 0 || slot_ints < 0 || out_values < 0 || verify < 0 || verify > 2)
         return AMT_E_INVALID;
     if (n > 65535 * 32 || n_cand > (1LL << 31) - 64) return AMT_E_UNSUPPORTED;
-    const long long need = amt_flac_decode_scratch_bytes(n_cand, slot_ints);
+    fd_layout L;
+    const fd_i64 need = fd_make_layout(scratch, n_cand, slot_ints, &L);
     if (need < 0) return AMT_E_INVALID;
     if (scratch_bytes < need) return AMT_E_SHAPE;
-
-    int *slots = (int *)scratch;
-    long long *next = (long long *)(scratch + fd_round8(4 * slot_ints));
-    long long *first = next + n_cand;
     if (n_cand > 0) {
         const unsigned blocks = (unsigned)((n_cand + AMT_FD_LANES - 1) / AMT_FD_LANES);
         flacdec_frame_kernel<<<blocks, AMT_FD_LANES, 0, stream>>>(data, data_bytes, stream_meta, n, cand_meta, n_cand,
-                                                                  slots, slot_ints, out_values, cand_out);
+                                                                  L.slots, slot_ints, out_values, cand_out);
         AMT_LAUNCH_CHECK();
     }
     flacdec_walk_kernel<<<n, AMT_FD_LANES, 0, stream>>>(stream_meta, n, cand_meta, n_cand, data_bytes, out_values,
-                                                        cand_out, next, first, status);
+                                                        cand_out, L.next, L.first, status);
     AMT_LAUNCH_CHECK();
     if (n_cand > 0) {
         flacdec_place_kernel<<<(unsigned)n_cand, AMT_FD_THREADS, 0, stream>>>(
-            data, data_bytes, stream_meta, n, cand_meta, n_cand, slots, out_values, cand_out, first, verify, out,
+            data, data_bytes, stream_meta, n, cand_meta, n_cand, L.slots, out_values, cand_out, L.first, verify, out,
             out_pcm, status);
         AMT_LAUNCH_CHECK();
     }

@@ -9,6 +9,7 @@
 #ifndef AMT_FLACDEC_CORE_H
 #define AMT_FLACDEC_CORE_H
 #include <stdint.h>
+#include "amt_scratch.h"
 
 #ifdef __HIP__
 #define AMT_FD_HD __host__ __device__ inline
@@ -270,6 +271,20 @@ AMT_FD_HD unsigned fd_crc16(const unsigned char *p, uint64_t n) {
         for (int j = 0; j < 8; ++j) crc = (crc & 0x8000u) ? ((crc << 1) ^ 0x8005u) & 0xffffu : (crc << 1) & 0xffffu;
     }
     return crc;
+}
+
+// The scratch of amt_flac_decode_ragged: the candidates' slots, then, on an 8-byte boundary, two int64 per candidate.
+struct fd_layout {
+    int *slots;                  // [slot_ints]
+    fd_i64 *next, *first;        // [n_cand]
+};
+inline fd_i64 fd_make_layout(void *scratch, fd_i64 n_cand, fd_i64 slot_ints, fd_layout *L) {
+    if (n_cand > (1LL << 40) || slot_ints > (1LL << 56)) return -1;
+    amt_carver c(scratch);
+    L->slots = c.take<int>(slot_ints);
+    L->next = c.take<fd_i64>(n_cand, 8);
+    L->first = c.take<fd_i64>(n_cand, 8);
+    return c.failed ? -1 : c.at;
 }
 
 #endif

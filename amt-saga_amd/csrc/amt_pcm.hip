@@ -22,6 +22,7 @@
 //  * every row is checked against both buffer sizes first (pcm_row_values / pcm_pack_bytes): all of it or nothing.
 #include "amt_common.h"
 #include "amt_pcm_core.h"
+#include "amt_wg.h"
 
 #define AMT_PCM_THREADS 256
 #define AMT_PCM_TILE (AMT_PCM_THREADS * PCM_RUN)
@@ -83,14 +84,12 @@ __global__ __launch_bounds__(AMT_PCM_THREADS) void pcm_unpack_kernel(
     }
 }
 
-__device__ __forceinline__ pcm_i64 pcm_len(pcm_i64 l, pcm_i64 max_len) { return l < 0 ? 0 : (l > max_len ? max_len : l); }
-
 __global__ __launch_bounds__(AMT_PCM_THREADS) void pcm_peak_kernel(
     const float *__restrict__ wave, const pcm_i64 *__restrict__ base, const pcm_i64 *__restrict__ len, pcm_i64 max_len,
     float *__restrict__ peak_out) {
     __shared__ float red[16];
     const int b = blockIdx.y;
-    const pcm_i64 n_s = pcm_len(len[b], max_len);
+    const pcm_i64 n_s = amt_clamp_len(len[b], max_len);
     if ((pcm_i64)blockIdx.x * AMT_PCM_PEAK_SPAN >= n_s) return;                // (whole workgroup)
     const float *x = wave + base[b];
     float m = 0.f;
@@ -130,7 +129,7 @@ __global__ __launch_bounds__(AMT_PCM_THREADS) void pcm_pack_kernel(
     int fmt, const float *__restrict__ peak, unsigned char *__restrict__ out, const pcm_i64 *__restrict__ out_base,
     pcm_i64 out_bytes) {
     const int b = blockIdx.y;
-    const pcm_i64 n_s = pcm_len(len[b], max_len), ob = out_base[b];
+    const pcm_i64 n_s = amt_clamp_len(len[b], max_len), ob = out_base[b];
     if (pcm_pack_bytes(n_s, ob, fmt, out_bytes) == 0) return;                  // the signal's bytes would leave `out`
     const float *x = wave + base[b];
     const float divisor = peak ? pcm_norm_divisor(peak[b]) : 0.f;

@@ -24,14 +24,13 @@
 //  * kernel 2 (one workgroup): Adler-32 and the last chunk's CRC per image, file sizes, their scan, chunk offsets.
 //  * kernel 3: a workgroup per chunk copies it to its place; a workgroup per image writes signature, IHDR, PLTE, IEND.
 //  * integer code apart from the one multiply and the comparisons of the levels; no packed-FP32 instructions: any stream.
-#include <vector>
 #include "amt_launch.h"
 #include "amt_png_core.h"
+#include "amt_wg.h"
 
 #define PNG_THREADS 256
 #define PNG_TILE 64                       /* rows and columns of a levels tile */
 #define PNG_TILE_PITCH 68
-#define PNG_RES 8                         /* uint32 per piece result: body bytes, CRC, byte sum, weighted sum, bytes */
 #define PNG_LDS_CAP (72 * 1024)           /* dynamic LDS of the piece kernel: the filtered bytes and the chunk */
 #define PNG_LEVELS_MAX_GRID 4096
 
@@ -101,33 +100,6 @@ struct png_or_lds {
 };
 typedef png_bits<png_or_lds> png_writer;
 
-__device__ __forceinline__ uint32_t png_wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, 64);
-    return v;
-}
-
-// exclusive scan of one value per thread over the workgroup; *total the sum.  red: 8 words of LDS.
-__device__ __forceinline__ uint32_t png_block_scan(uint32_t v, uint32_t *red, uint32_t *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t u = (uint32_t)__shfl_up((int)inc, off, 64);
-        if (lane >= off) inc += u;
-    }
-    __syncthreads();
-    if (lane == 63) red[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (int k = 0; k < PNG_THREADS / 64; ++k) {
-        if (k < wave) before += red[k];
-        all += red[k];
-    }
-    *total = all;
-    return before + inc - v;
-}
-
 struct png_piece_lds {
     uint32_t crc_table[256];
     uint32_t freq[288];
@@ -177,7 +149,7 @@ __global__ __launch_bounds__(PNG_THREADS) void png_piece_kernel(
             for (int f = 0; f < 5; ++f) sum[f] += (uint32_t)png_abs_signed(png_filter_byte(f, v, a, b, c));
         }
 #pragma unroll
-        for (int f = 0; f < 5; ++f) sum[f] = png_wave_sum_u32(sum[f]);
+        for (int f = 0; f < 5; ++f) sum[f] = amt_wave_reduce(sum[f], amt_sum{});
         const int f = png_pick_filter(sum);
         unsigned char *dst = fb + (png_i64)r * (W + 1);
         if (lane == 0) dst[0] = (unsigned char)f;
@@ -258,7 +230,7 @@ __global__ __launch_bounds__(PNG_THREADS) void png_piece_kernel(
         uint32_t mine = 0;
         png_walk_runs(fb, c0, c1, next_after, [&](int, int L, int byte) { mine += png_run_bits(L, byte, s.len, dist_bits); });
         uint32_t total;
-        const uint32_t before = png_block_scan(mine, s.red, &total);
+        const uint32_t before = amt_block_scan<uint32_t, PNG_THREADS>(mine, s.red, &total);
         const uint32_t head_bits = kind == PNG_KIND_FIXED ? 3 : s.head.bits;
         const uint32_t tok0 = 8u * hb + head_bits;                     // total + head_bits + len[EOB] == data_bits
         png_writer w(png_or_lds{ow}, tok0 + before);
@@ -312,7 +284,7 @@ __global__ __launch_bounds__(PNG_THREADS) void png_scan_kernel(
     const png_i64 *__restrict__ meta, const png_i64 *__restrict__ pieces, const uint32_t *__restrict__ res,
     unsigned char *__restrict__ slots, int n, int palette, png_i64 *__restrict__ sizes, png_i64 *__restrict__ piece_off,
     png_i64 *__restrict__ file_off) {
-    __shared__ png_i64 part[PNG_THREADS];
+    __shared__ png_i64 part[PNG_THREADS / 64];
     const int tid = threadIdx.x;
     const int per = (n + PNG_THREADS - 1) / PNG_THREADS;
     const int i0 = tid * per < n ? tid * per : n, i1 = i0 + per < n ? i0 + per : n;
@@ -337,11 +309,8 @@ __global__ __launch_bounds__(PNG_THREADS) void png_scan_kernel(
         sizes[i] = size;
         mine += size;
     }
-    part[tid] = mine;
-    __syncthreads();
-    png_i64 off = 0;
-    for (int u = 0; u < tid; ++u) off += part[u];
-    if (tid == PNG_THREADS - 1) file_off[n] = off + mine;
+    png_i64 total, off = amt_block_scan<png_i64, PNG_THREADS>(mine, part, &total);
+    if (tid == 0) file_off[n] = total;
     for (int i = i0; i < i1; ++i) {
         file_off[i] = off;
         const int W = (int)meta[4 * i + 1], H = (int)meta[4 * i + 2];
@@ -376,50 +345,6 @@ __global__ __launch_bounds__(PNG_THREADS) void png_gather_kernel(
     png_put_end(out + file_off[i + 1] - 12);
 }
 
-// the scratch layout of one call, from the host's table; 0 if the table is refused
-struct png_layout {
-    png_i64 P, meta_off, pieces_off, res_off, sizes_off, piece_off_off, slots_off, total, out_bound;
-    int cap;
-};
-static int png_make_layout(const long long *image_meta, int n, int palette, png_layout *L, std::vector<png_i64> *tables) {
-    if (!image_meta || n < 1 || n > 65535) return 0;
-    png_i64 P = 0, slot = 0, bound = 0;
-    int cap = 0;
-    if (tables) tables->assign((size_t)4 * n, 0);
-    for (int i = 0; i < n; ++i) {
-        const png_i64 base = image_meta[3 * i], w = image_meta[3 * i + 1], h = image_meta[3 * i + 2];
-        if (!png_dims_ok(w, h) || base < 0) return 0;
-        const int r = png_piece_rows((int)w);
-        if (tables) {
-            png_i64 *m = tables->data() + 4 * i;
-            m[0] = base; m[1] = w; m[2] = h; m[3] = P;
-        }
-        for (png_i64 y = 0; y < h; y += r) {
-            const png_i64 rows = h - y < r ? h - y : r, bytes = rows * (w + 1);
-            if (bytes > cap) cap = (int)bytes;
-            if (tables) {
-                const png_i64 row[4] = {i, y, rows, slot};
-                tables->insert(tables->end(), row, row + 4);
-            }
-            slot += (png_chunk_bound(bytes) + 4 + 15) / 16 * 16;       // (+ 4: the chunk is copied in whole words)
-            ++P;
-        }
-        bound += png_file_bound((int)w, (int)h, palette);
-    }
-    auto up = [](png_i64 v) { return (v + 15) / 16 * 16; };
-    L->P = P;
-    L->cap = (cap + 15) / 16 * 16;
-    L->meta_off = 0;
-    L->pieces_off = 32 * (png_i64)n;
-    L->res_off = up(L->pieces_off + 32 * P);
-    L->sizes_off = up(L->res_off + 4 * PNG_RES * P);
-    L->piece_off_off = up(L->sizes_off + 8 * (png_i64)n);
-    L->slots_off = up(L->piece_off_off + 8 * P);
-    L->total = L->slots_off + slot;
-    L->out_bound = bound;
-    return 1;
-}
-
 extern "C" {
 
 int amt_spec_levels_ragged(const float *mag, long long mag_floats, const long long *image_meta, int n, int max_w,
@@ -444,8 +369,8 @@ long long amt_png_file_bound(int w, int h, int palette) {
 
 long long amt_png_scratch_bytes(const long long *image_meta, int n) {
     png_layout L;
-    if (!png_make_layout(image_meta, n, 0, &L, nullptr)) return AMT_E_INVALID;
-    return L.total;
+    const png_i64 need = png_make_layout(nullptr, image_meta, n, 0, &L, nullptr);
+    return need < 0 ? AMT_E_INVALID : need;
 }
 
 int amt_png_encode_ragged(const unsigned char *pix, long long pix_bytes, const long long *image_meta, int n,
@@ -454,29 +379,26 @@ int amt_png_encode_ragged(const unsigned char *pix, long long pix_bytes, const l
     if (!pix || !scratch || ((uintptr_t)scratch & 15) || !out || !file_off || pix_bytes < 0) return AMT_E_INVALID;
     png_layout L;
     std::vector<png_i64> tables;
-    if (!png_make_layout(image_meta, n, palette != nullptr, &L, &tables)) return AMT_E_INVALID;
+    const png_i64 need = png_make_layout(scratch, image_meta, n, palette != nullptr, &L, &tables);
+    if (need < 0) return AMT_E_INVALID;
     for (int i = 0; i < n; ++i) {
         const png_i64 bytes = image_meta[3 * i + 1] * image_meta[3 * i + 2];
         if (bytes > pix_bytes || image_meta[3 * i] > pix_bytes - bytes) return AMT_E_INVALID;
     }
-    if (scratch_bytes < L.total || out_bytes < L.out_bound) return AMT_E_SHAPE;
+    if (scratch_bytes < need || out_bytes < L.out_bound) return AMT_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
-    unsigned char *sc = (unsigned char *)scratch;
     // the two small tables, the one upload of the call: it is waited for, since `tables` ends with this function
-    AMT_HIP_CHECK(hipMemcpyAsync(sc, tables.data(), tables.size() * sizeof(png_i64), hipMemcpyHostToDevice, st));
+    AMT_HIP_CHECK(hipMemcpyAsync(L.meta, tables.data(), tables.size() * sizeof(png_i64), hipMemcpyHostToDevice, st));
     AMT_HIP_CHECK(hipStreamSynchronize(st));
-    const png_i64 *meta = (const png_i64 *)(sc + L.meta_off), *pieces = (const png_i64 *)(sc + L.pieces_off);
-    uint32_t *res = (uint32_t *)(sc + L.res_off);
-    png_i64 *sizes = (png_i64 *)(sc + L.sizes_off), *piece_off = (png_i64 *)(sc + L.piece_off_off);
-    unsigned char *slots = sc + L.slots_off;
     const size_t lds = (size_t)L.cap + (size_t)L.cap + 16;
-    int rc = amt_launch<png_piece_kernel>(PNG_LDS_CAP, dim3((unsigned)L.P), dim3(PNG_THREADS), lds, st, pix, meta, pieces,
-                                          slots, res, L.cap);
+    int rc = amt_launch<png_piece_kernel>(PNG_LDS_CAP, dim3((unsigned)L.P), dim3(PNG_THREADS), lds, st, pix, L.meta,
+                                          L.pieces, L.slots, L.res, L.cap);
     if (rc != AMT_OK) return rc;
-    png_scan_kernel<<<1, PNG_THREADS, 0, st>>>(meta, pieces, res, slots, n, palette != nullptr, sizes, piece_off, file_off);
+    png_scan_kernel<<<1, PNG_THREADS, 0, st>>>(L.meta, L.pieces, L.res, L.slots, n, palette != nullptr, L.sizes,
+                                               L.piece_off, file_off);
     AMT_LAUNCH_CHECK();
-    png_gather_kernel<<<(unsigned)(L.P + n), PNG_THREADS, 0, st>>>(meta, pieces, res, slots, L.P, palette, piece_off,
-                                                                   file_off, out);
+    png_gather_kernel<<<(unsigned)(L.P + n), PNG_THREADS, 0, st>>>(L.meta, L.pieces, L.res, L.slots, L.P, palette,
+                                                                   L.piece_off, file_off, out);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }

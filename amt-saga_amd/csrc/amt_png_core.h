@@ -35,6 +35,8 @@
 #ifndef AMT_PNG_CORE_H
 #define AMT_PNG_CORE_H
 #include <stdint.h>
+#include <vector>
+#include "amt_scratch.h"
 
 #ifdef __HIP__
 #define AMT_PNG_HD __host__ __device__ inline
@@ -496,6 +498,60 @@ AMT_PNG_HD void png_dynamic_head_emit(B &w, const unsigned char *len, const png_
     png_cl_tokens(len, h->hlit, [&](int s, int eb, int v) {
         w.put(h->cl_code[s] | ((uint32_t)v << h->cl_len[s]), h->cl_len[s] + eb);
     });
+}
+
+#define PNG_RES 8                    /* uint32 per piece result: body bytes, CRC, byte sum, weighted sum, bytes */
+
+// The scratch of one amt_png_encode_ragged call, from the host's table [n][3] = first byte, W, H: the two tables the call
+// uploads back to back (meta int64 [n][4], pieces int64 [P][4]: tables->data(), if asked for), then every region on a
+// 16-byte boundary.  Returns the bytes of the scratch, -1 if the table is refused.
+struct png_layout {
+    png_i64 P, out_bound;
+    int cap;                                                           // LDS bytes of the longest piece, 16-aligned
+    png_i64 *meta, *pieces;                                            // [n][4], [P][4]
+    uint32_t *res;                                                     // [P][PNG_RES]
+    png_i64 *sizes, *piece_off;                                        // [n], [P]
+    unsigned char *slots;
+    png_i64 slot_bytes;
+};
+inline png_i64 png_make_layout(void *scratch, const long long *image_meta, int n, int palette, png_layout *L,
+                               std::vector<png_i64> *tables) {
+    if (!image_meta || n < 1 || n > 65535) return -1;
+    png_i64 P = 0, slot = 0, bound = 0;
+    int cap = 0;
+    if (tables) tables->assign((size_t)4 * n, 0);
+    for (int i = 0; i < n; ++i) {
+        const png_i64 base = image_meta[3 * i], w = image_meta[3 * i + 1], h = image_meta[3 * i + 2];
+        if (!png_dims_ok(w, h) || base < 0) return -1;
+        const int r = png_piece_rows((int)w);
+        if (tables) {
+            png_i64 *m = tables->data() + 4 * i;
+            m[0] = base; m[1] = w; m[2] = h; m[3] = P;
+        }
+        for (png_i64 y = 0; y < h; y += r) {
+            const png_i64 rows = h - y < r ? h - y : r, bytes = rows * (w + 1);
+            if (bytes > cap) cap = (int)bytes;
+            if (tables) {
+                const png_i64 row[4] = {i, y, rows, slot};
+                tables->insert(tables->end(), row, row + 4);
+            }
+            slot += (png_chunk_bound(bytes) + 4 + 15) / 16 * 16;       // (+ 4: the chunk is copied in whole words)
+            ++P;
+        }
+        bound += png_file_bound((int)w, (int)h, palette);
+    }
+    amt_carver c(scratch);
+    L->P = P;
+    L->out_bound = bound;
+    L->cap = (cap + 15) / 16 * 16;
+    L->meta = c.take<png_i64>(4 * (png_i64)n, 16);
+    L->pieces = c.take<png_i64>(4 * P);
+    L->res = c.take<uint32_t>(PNG_RES * P, 16);
+    L->sizes = c.take<png_i64>(n, 16);
+    L->piece_off = c.take<png_i64>(P, 16);
+    L->slots = c.take<unsigned char>(slot, 16);
+    L->slot_bytes = slot;
+    return c.failed ? -1 : c.at;
 }
 
 #endif

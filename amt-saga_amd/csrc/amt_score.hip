@@ -28,12 +28,6 @@
 #define SCORE_THREADS 320                 /* five waves */
 #define SCORE_MAX_GRID (1 << 16)
 
-struct score_scratch {
-    int *lo, *hi;                                              // [n_ref]: a reference's candidates, from its pitch's first
-    int *owner[SCORE_VARIANTS], *visited[SCORE_VARIANTS];      // [n_est]
-    int *stack_ref[SCORE_VARIANTS], *stack_via[SCORE_VARIANTS];// [n_ref]
-};
-
 // the candidates of r over the lanes of a wave
 struct score_wave_scan {
     const score_notes &E, &R;
@@ -119,15 +113,12 @@ __global__ __launch_bounds__(SCORE_THREADS) void score_pairs_kernel(
     }
 }
 
-static score_i64 score_up16(score_i64 v) { return (v + 15) / 16 * 16; }
-#define SCORE_MAX_NOTES ((score_i64)1 << 40)                   /* per side and call: the scratch stays far inside int64 */
-
 extern "C" {
 
 long long amt_score_scratch_bytes(long long n_est_total, long long n_ref_total) {
-    if (n_est_total < 0 || n_ref_total < 0 || n_est_total > SCORE_MAX_NOTES || n_ref_total > SCORE_MAX_NOTES)
-        return AMT_E_INVALID;
-    return 16 + 2 * SCORE_VARIANTS * score_up16(4 * n_est_total) + (2 + 2 * SCORE_VARIANTS) * score_up16(4 * n_ref_total);
+    score_scratch S;
+    const score_i64 need = score_make_layout(nullptr, n_est_total, n_ref_total, &S);
+    return need < 0 ? AMT_E_INVALID : need;
 }
 
 int amt_score_check_notes(const int32_t *pitch, const int32_t *program, long long n) {
@@ -152,22 +143,12 @@ int amt_score_pairs(const amt_score_args *a, void *stream) {
         }
     }
     const score_i64 n_est = offs[0][a->n_pairs], n_ref = offs[1][a->n_pairs];
-    const long long need = amt_score_scratch_bytes(n_est, n_ref);
+    score_scratch S;
+    const score_i64 need = score_make_layout(a->scratch, n_est, n_ref, &S);
     if (need < 0) return AMT_E_INVALID;
     if (a->scratch_bytes < need) return AMT_E_SHAPE;
     if (a->n_pairs == 0) return AMT_OK;
     hipStream_t st = (hipStream_t)stream;
-    unsigned char *sc = (unsigned char *)a->scratch;
-    const score_i64 eb = score_up16(4 * n_est), rb = score_up16(4 * n_ref);
-    score_scratch S;
-    S.lo = (int *)sc; sc += rb;
-    S.hi = (int *)sc; sc += rb;
-    for (int v = 0; v < SCORE_VARIANTS; ++v) {
-        S.owner[v] = (int *)sc; sc += eb;
-        S.visited[v] = (int *)sc; sc += eb;
-        S.stack_ref[v] = (int *)sc; sc += rb;
-        S.stack_via[v] = (int *)sc; sc += rb;
-    }
     const score_notes E = {a->est_pitch, a->est_program, (const score_i64 *)a->est_on, (const score_i64 *)a->est_off};
     const score_notes R = {a->ref_pitch, a->ref_program, (const score_i64 *)a->ref_on, (const score_i64 *)a->ref_off};
     AMT_HIP_CHECK(hipMemsetAsync(a->out, 0, (size_t)a->n_pairs * SCORE_OUT * sizeof(int64_t), st));

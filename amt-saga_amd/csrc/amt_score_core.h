@@ -33,6 +33,7 @@
 #ifndef AMT_SCORE_CORE_H
 #define AMT_SCORE_CORE_H
 #include <stdint.h>
+#include "amt_scratch.h"
 
 #ifdef __HIP__
 #define AMT_SCORE_HD __host__ __device__ inline
@@ -194,6 +195,29 @@ AMT_SCORE_HD void score_frames(const score_notes &E, score_i64 e0, score_i64 e1,
     count[1] = n_e - tp;
     count[2] = n_r - tp;
     *max_off = top;
+}
+
+// The scratch of amt_score_pairs, every array on a 16-byte boundary of the buffer and indexed by the note's place in the
+// call: the candidate ranges, then per variant the matcher's arrays.  16 bytes of slack close it, as they always have.
+#define SCORE_MAX_NOTES ((score_i64)1 << 40)                   /* per side and call: the scratch stays far inside int64 */
+struct score_scratch {
+    int *lo, *hi;                                              // [n_ref]: a reference's candidates, from its pitch's first
+    int *owner[SCORE_VARIANTS], *visited[SCORE_VARIANTS];      // [n_est]
+    int *stack_ref[SCORE_VARIANTS], *stack_via[SCORE_VARIANTS];// [n_ref]
+};
+inline score_i64 score_make_layout(void *scratch, score_i64 n_est, score_i64 n_ref, score_scratch *S) {
+    if (n_est > SCORE_MAX_NOTES || n_ref > SCORE_MAX_NOTES) return -1;
+    amt_carver c(scratch);
+    S->lo = c.take<int>(n_ref, 16);
+    S->hi = c.take<int>(n_ref, 16);
+    for (int v = 0; v < SCORE_VARIANTS; ++v) {
+        S->owner[v] = c.take<int>(n_est, 16);
+        S->visited[v] = c.take<int>(n_est, 16);
+        S->stack_ref[v] = c.take<int>(n_ref, 16);
+        S->stack_via[v] = c.take<int>(n_ref, 16);
+    }
+    c.take<unsigned char>(16, 16);
+    return c.failed ? -1 : c.at;
 }
 
 #endif

@@ -161,8 +161,8 @@ int amt_resample_ragged(const amt_resampler *rs, const float *in, const int64_t 
  * Host only. */
 long long amt_flac_frame_bound(int blocksize, int bps);
 /* audio_to_flac (util_audio.py:966-968): bytes of `scratch` amt_flac_encode_ragged needs for n signals of at most
- * max_len samples: one slot of amt_flac_frame_bound bytes per frame of an [n][frames(max_len)] grid, rounded up to 8,
- * then one int64 per slot (the frame's byte offset inside its stream).  Negative for invalid arguments.  Host only. */
+ * max_len samples, as amt_flac_make_layout (csrc/amt_scratch.h) lays it out: one slot of amt_flac_frame_bound bytes per
+ * frame of an [n][frames(max_len)] grid, then the slots' int64 offsets.  Negative for invalid arguments.  Host only. */
 long long amt_flac_scratch_bytes(int n, long long max_len, int blocksize, int bps);
 /* audio_to_flac (util_audio.py:966-968) for n signals in ONE call: signal i = wave[base[i] .. + len[i]) (floats; base
  * may be any offset, negative included, that lands in memory the caller owns; a len above max_len is cut to max_len).
@@ -206,8 +206,8 @@ int amt_flac_encode_lpc_ragged(const float *wave, const long long *base, const l
  * wasted bits, block sizes 1 .. 65536, bps 4 .. 24 (above 24 is refused: float32 is exact to 24 bits).  DESIGN.md 16.
  * ------------------------------------------------------------------------ */
 /* audio_from_file (util_audio.py:962-964): bytes of `scratch` amt_flac_decode_ragged needs for n_cand candidates whose
- * slots (channels * block size int32 each) sum to slot_ints: the slots rounded up to 8, then two int64 per candidate.
- * Negative for invalid arguments.  Host only. */
+ * slots (channels * block size int32 each) sum to slot_ints, as fd_make_layout (csrc/amt_flacdec_core.h) lays it out:
+ * the slots, then two int64 per candidate.  Negative for invalid arguments.  Host only. */
 long long amt_flac_decode_scratch_bytes(long long n_cand, long long slot_ints);
 /* audio_from_file (util_audio.py:962-964) for n streams in ONE call.  data [data_bytes]: the files' bytes.
  * stream_meta int64 [n][9]: byte offset in data, size, first frame byte (relative to the offset), channels, bps, total

@@ -131,6 +131,30 @@ def test_bytes_against_restatement(env, bps, blocksize, cap):
     _compare(got, _reference(bps, blocksize, cap), (bps, blocksize))
 
 
+def _many_short(count, n):
+    """`count` signals of n samples: windows of the committed signals, a different signal and start for neighbours."""
+    sig = R.signals()
+    names = sorted(LENGTHS)
+    return [sig[names[i % len(names)]][7 * i:7 * i + n].copy() for i in range(count)]
+
+
+@pytest.mark.parametrize('tag', ['301_frames', '300_signals'])
+def test_offset_scans_carry_past_one_pass(env, tag):
+    """The two offset scans walk their items 256 at a time and carry the running sum on: one signal of 16 * 300 + 5
+    samples at block size 16 is 301 frames (the frame-offset scan carries once), 300 signals of 40 samples in one call
+    make the stream-offset scan carry.  Bytes, sizes, min / max, offsets and MD5 against the restatement."""
+    sig = R.signals()
+    waves = [sig['tone_noise'][:16 * 300 + 5].copy()] if tag == '301_frames' else _many_short(300, 40)
+    got = _encode_raw(env, waves, 24, 16)
+    assert sum(len(sizes) for _, sizes, _, _, _ in got) == (301 if tag == '301_frames' else 900)
+    assert len({len(stream) for stream, _, _, _, _ in got}) > (0 if tag == '301_frames' else 10)
+    ref = []
+    for y in waves:
+        q = R.quantise(y, 24)
+        ref.append((R.encode_frames(q, 24, 16, 0)[0], R.pcm_md5(q, 24)))
+    _compare(got, ref, tag)
+
+
 @pytest.mark.parametrize('first_frame', [126, 2046, 65534, (1 << 21) - 2, (1 << 26) - 2])
 def test_frame_numbers(env, first_frame):
     """Two- and three-block signals at block size 16: the frame numbers first_frame .. first_frame + 2 cross into the

@@ -106,6 +106,25 @@ def test_six_ragged_images_one_call_equals_one_per_call(env):
         assert np.array_equal(R.decode(g)[0], im)
 
 
+@pytest.mark.parametrize('tag', ['300_of_3x2', '257_mixed'])
+def test_more_images_than_threads_in_one_call(env, tag):
+    """The size scan gives every thread of its one workgroup a run of images: 300 images of 3 x 2 and 257 images of
+    mixed tiny sizes both make runs of 2 with the last thread short, so every file offset behind the first run is a sum
+    across threads.  Every file byte for byte, palette and grey."""
+    rng = np.random.RandomState(300 if tag == '300_of_3x2' else 257)
+    if tag == '300_of_3x2':
+        shapes = [(2, 3)] * 300
+    else:
+        shapes = [(1 + (i * 5) % 7, 1 + (i * 3) % 11) for i in range(257)]                     # (H, W)
+        assert len(set(shapes)) > 50
+    imgs = [rng.randint(0, 1 << rng.randint(1, 9), size=hw).astype(np.uint8) for hw in shapes]
+    pal = env['png'].palette('cubehelix')
+    for palette in (None, pal):
+        got = _encode(env, imgs, palette)
+        assert len({len(g) for g in got}) > 1
+        assert [g == R.encode(im, palette) for im, g in zip(imgs, got)] == [True] * len(imgs)
+
+
 def test_invalid_sizes_are_refused_with_nothing_written(env):
     torch, lib, _lib = env['torch'], env['lib'], env['_lib']
     from amt_saga.device import ptr
