@@ -10,8 +10,27 @@ import numpy as np
 MAX_DIM = 16384                       # PNG_MAX_DIM: width and height of an image
 THRESHOLDS = 255
 AXES = ('log', 'linear')
-PALETTES = ('cubehelix', 'gray')
+PALETTES = ('cubehelix', 'gray', 'roll')
 FMIN = 27.5                           # the lowest frequency of the log axis: A0
+
+# The piano-roll palette, entry by entry; every entry that is not named here is black.
+ROLL_COLOURS = {
+    # background: white-key row, black-key row, and the tick shade of each
+    0: (250, 250, 250), 1: (232, 232, 236), 2: (205, 205, 210), 3: (190, 190, 197),
+    # one list: sixteen group hues at 16 + 2 g, the darker onset variant at 16 + 2 g + 1
+    16: (66, 133, 244), 17: (26, 82, 168), 18: (219, 68, 55), 19: (150, 35, 28),
+    20: (15, 157, 88), 21: (8, 100, 54), 22: (244, 160, 0), 23: (170, 105, 0),
+    24: (171, 71, 188), 25: (110, 35, 125), 26: (0, 172, 193), 27: (0, 110, 125),
+    28: (255, 112, 67), 29: (190, 70, 35), 30: (124, 179, 66), 31: (78, 120, 35),
+    32: (92, 107, 192), 33: (50, 62, 130), 34: (240, 98, 146), 35: (170, 50, 95),
+    36: (0, 137, 123), 37: (0, 85, 76), 38: (192, 202, 51), 39: (128, 136, 25),
+    40: (141, 110, 99), 41: (90, 66, 58), 42: (120, 144, 156), 43: (72, 92, 102),
+    44: (255, 202, 40), 45: (185, 140, 10), 46: (126, 87, 194), 47: (80, 50, 135),
+    # a pair, 64 + 4 class + estimate onset + 2 gold onset: estimate only (red), gold only (blue), both (green)
+    68: (229, 57, 53), 69: (140, 20, 20),
+    72: (30, 136, 229), 74: (13, 71, 161),
+    76: (67, 160, 71), 77: (27, 94, 32), 78: (0, 77, 64), 79: (10, 50, 15),
+}
 
 
 def thresholds(top_db=80.0):
@@ -89,11 +108,17 @@ def palette(name='cubehelix'):
     rotations -1.5, hue 1, gamma 1: phi = 2 pi (start / 3 + rotations x), a = hue x (1 - x) / 2,
     R = x + a (-0.14861 cos phi + 1.78277 sin phi), G = x + a (-0.29227 cos phi - 0.90649 sin phi),
     B = x + a 1.97294 cos phi, clipped to [0, 1]; 8-bit by floor(255 v + 0.5).  Black at level 0, white at 255, the
-    luminance 0.30 R + 0.59 G + 0.11 B rising with the level."""
+    luminance 0.30 R + 0.59 G + 0.11 B rising with the level.
+    'roll': the literal table ROLL_COLOURS of the piano-roll pixel values (amt_saga.roll.legend()), black elsewhere."""
     if name not in PALETTES:
         raise ValueError('Requested attribute does not exist: palette must be one of %s' % (PALETTES,))
     if name == 'gray':
         return None
+    if name == 'roll':
+        table = np.zeros((256, 3), dtype=np.uint8)
+        for value, rgb in ROLL_COLOURS.items():
+            table[value] = rgb
+        return table
     x = np.arange(256, dtype=np.float64) / 255.0
     phi = 2.0 * np.pi * (0.5 / 3.0 + -1.5 * x)
     a = 1.0 * x * (1.0 - x) / 2.0

@@ -9,6 +9,7 @@ float64, a zero denominator giving 0.0 as mir_eval does.
 
     python -m amt_saga.score EST.mid GOLD.mid [EST2.mid GOLD2.mid ...]
     python -m amt_saga.score --est-dir D --gold-dir G            (files paired by stem)
+    ... --roll-dir DIR: also <name>.roll.png per pair, the estimate drawn against the gold notes (amt_saga.roll)
 
 One JSON line per pair and one for the collection; one device call for everything.  Gold files are read with every
 tempo change honoured and without channel 9 (drums), as the reference's get_notes(include_drums=False) reads them; the
@@ -195,7 +196,12 @@ def main(argv=None):
     ap.add_argument('files', nargs='*', metavar='EST.mid GOLD.mid')
     ap.add_argument('--est-dir', default=None)
     ap.add_argument('--gold-dir', default=None)
+    ap.add_argument('--roll-dir', default=None, metavar='DIR',
+                    help='also write <name>.roll.png per pair: the piano roll of the estimate against the gold notes '
+                         '(estimate only, gold only, both), drawn and encoded on the device in one call (amt_saga.roll)')
     a = ap.parse_args(sys.argv[1:] if argv is None else list(argv))
+    if a.roll_dir is not None and os.path.exists(a.roll_dir) and not os.path.isdir(a.roll_dir):
+        raise SystemExit('--roll-dir: %s is not a directory' % a.roll_dir)
     if (a.est_dir is None) != (a.gold_dir is None):
         raise SystemExit('--est-dir and --gold-dir go together')
     if a.est_dir is not None:
@@ -220,10 +226,20 @@ def main(argv=None):
     for p in est + gold:
         if not os.path.isfile(p):
             raise SystemExit('%s: no such file' % p)
+    if a.roll_dir is not None and len(set(names)) != len(names):
+        raise SystemExit('--roll-dir: two pairs would write the same .roll.png (equal file names)')
     counts, summ = score_files(est, gold, group=loop_groups())
     pairs, whole = report(names, est, gold, counts, summ)
     for rec in pairs + [whole]:
         print(json.dumps(rec, sort_keys=True))
+    if a.roll_dir is not None:
+        from . import roll
+        os.makedirs(a.roll_dir, exist_ok=True)
+        paths = [os.path.join(a.roll_dir, nm + '.roll.png') for nm in names]
+        roll.save_piano_rolls([ev.read_midi(p, full=True) for p in est], paths, [read_gold(p) for p in gold],
+                              group=loop_groups())
+        for path in paths:
+            print('roll -> %s' % path, file=sys.stderr)
 
 
 if __name__ == '__main__':

@@ -40,6 +40,12 @@ provide for the inference direction:
     the collection; a song without a gold file is named on stderr and left out.  The .mid files as written are what is
     scored, so `python -m amt_saga.score` on the same files gives the same counts.
 
+    --roll-dir DIR [--roll-width W, default 1200] [--roll-row-px N, default 5] (both modes): the piano roll of what was
+    written, <stem>.roll.png -- pitches 21..108, from 0 to the song's duration, a tick every second, coloured by
+    instrument group, so that it lines up with <stem>.song.png at the same width -- and, for a song with a gold file
+    (--gold / --gold-dir), <stem>.roll.gold.png: estimate only, gold only, both.  Drawn and encoded on the device
+    (amt_saga.roll); with --songs all rolls of the collection come from ONE rasteriser call after the last song.
+
     --instrument-model NAME (both modes): the instrument head is the reference's model NAME (training.py:466-477; one of
     loop.INSTRUMENT_MODELS), fed the recipe arrays that model was trained on; the default is the plain CQT model.
 
@@ -55,7 +61,7 @@ import sys
 import numpy as np
 import torch
 
-from . import audio, events as ev, flac as host_flac, png as host_png, score as host_score, wav as host_wav
+from . import audio, events as ev, flac as host_flac, png as host_png, roll as host_roll, score as host_score, wav as host_wav
 from .hyperparams import Hyperparams
 from .loop import INSTRUMENT_MODELS, TranscriptionLoop
 
@@ -226,6 +232,13 @@ _SPECTROGRAM_HELP = ('with --traversal song, or with --songs: write <stem>.song.
                      'PNG files are made on the device, one levels call and one encode call per song')
 
 
+_ROLL_HELP = ('write <stem>.roll.png per song: the piano roll of the notes written, pitches 21..108 from 0 to the '
+              'song\'s duration with a tick every second, coloured by instrument group; with --gold / --gold-dir also '
+              '<stem>.roll.gold.png for a song that has a gold file: estimate only, gold only, both; rasteriser and PNG '
+              'encoder run on the device')
+ROLL_PITCH = (21, 108)
+
+
 DECODERS = ('host', 'device')
 _DECODE_HELP = ("reader of the input files: 'host' = the pure-Python reader (the default), 'device' = the HIP decoder "
                 "(--songs: --slots files per decode call, as the queue pulls them; CRC-8, CRC-16 and MD5 verified as the "
@@ -251,6 +264,11 @@ def _shared_options(ap, sr_help, **stems_dir):
     ap.add_argument('--spectrogram-dir', default=None, metavar='DIR', help=_SPECTROGRAM_HELP)
     ap.add_argument('--spectrogram-size', default='1200x500', metavar='WxH',
                     help='pixels of every --spectrogram-dir image, each side 1 .. 16384 (default 1200x500)')
+    ap.add_argument('--roll-dir', default=None, metavar='DIR', help=_ROLL_HELP)
+    ap.add_argument('--roll-width', type=int, default=1200, metavar='W',
+                    help='pixel columns of every --roll-dir image, 1 .. 16384 (default 1200)')
+    ap.add_argument('--roll-row-px', type=int, default=5, metavar='N',
+                    help='pixel rows per pitch of every --roll-dir image, 1 .. 186 (default 5: 440 rows)')
 
 
 def _check_writer(a):
@@ -368,6 +386,47 @@ def write_song_spectrograms(st, slot, directory, name, size=(1200, 500)):
         print('spectrogram -> %s' % path)
 
 
+def _roll_size(a):
+    """(width, row_px) of --roll-width / --roll-row-px and the directory of --roll-dir, checked before any work; None
+    without --roll-dir."""
+    if a.roll_dir is None:
+        return None
+    if os.path.exists(a.roll_dir) and not os.path.isdir(a.roll_dir):
+        raise SystemExit('--roll-dir: %s is not a directory' % a.roll_dir)
+    try:
+        return host_roll.geometry(0, a.roll_width, a.roll_row_px, ROLL_PITCH)[:2]
+    except ValueError as e:
+        raise SystemExit('--roll-width / --roll-row-px: ' + str(e))
+
+
+def write_rolls(names, mid_paths, durations, directory, size, gold_paths=None):
+    """The piano rolls of written .mid files (amt_saga.roll): <directory>/<name>.roll.png for every song, and
+    <name>.roll.gold.png for every song whose entry of gold_paths is not None, read by score.read_gold.  Pitches 21..108,
+    from 0 to the song's duration in seconds (at least one microsecond a column), a tick every second, the loop's
+    instrument groups; size = (width, row_px).  ONE rasteriser call for all of them."""
+    notes = [ev.read_midi(p, full=True) for p in mid_paths]
+    gold_paths = [None] * len(names) if gold_paths is None else list(gold_paths)
+    pairs = [i for i, g in enumerate(gold_paths) if g is not None]
+    spans = [(0.0, max(float(d), size[0] * 1e-6)) for d in durations]
+    paths = [os.path.join(directory, nm + '.roll.png') for nm in names] + \
+        [os.path.join(directory, names[i] + '.roll.gold.png') for i in pairs]
+    host_roll.save_piano_rolls(notes + [notes[i] for i in pairs], paths,
+                               [None] * len(names) + [host_score.read_gold(gold_paths[i]) for i in pairs],
+                               width=size[0], row_px=size[1], pitch=ROLL_PITCH, span=spans + [spans[i] for i in pairs],
+                               tick=1.0, group=host_score.loop_groups())
+    for path in paths:
+        print('roll -> %s' % path)
+
+
+def _note_durations(wfs, rate, out):
+    """`wfs` passed through, the seconds of every item appended to `out` as it is pulled: an item is a waveform at `rate`
+    or a (waveform, rate) pair."""
+    for item in wfs:
+        wf, sr = item if isinstance(item, tuple) else (item, rate)
+        out.append(int(wf.shape[0]) / float(sr))
+        yield item
+
+
 def write_scores(names, mid_paths, gold_paths, collection_path=None):
     """Score the written .mid files against their gold files in one device call (score.score_files with the loop's
     instrument groups): <mid path minus its extension>.score.json per song, and collection_path (scores.json) for the
@@ -418,11 +477,12 @@ def main_songs(argv):
     a = ap.parse_args(argv)
     _check_writer(a)
     size = _spectrogram_size(a)
+    roll_size = _roll_size(a)
     if a.gold_dir is not None and not os.path.isdir(a.gold_dir):
         raise SystemExit('--gold-dir: %s is not a directory' % a.gold_dir)
     os.makedirs(a.out_dir, exist_ok=True)
     keep, keep_stems = a.residual_dir is not None, a.stems_dir is not None
-    for d in (a.residual_dir, a.stems_dir, a.spectrogram_dir):
+    for d in (a.residual_dir, a.stems_dir, a.spectrogram_dir, a.roll_dir):
         if d is not None:
             os.makedirs(d, exist_ok=True)
     stems = [os.path.splitext(os.path.basename(f))[0] for f in a.songs]
@@ -442,6 +502,9 @@ def main_songs(argv):
             first = next(wfs)
             rate, wfs = first[1], itertools.chain([first], wfs)
         wfs = _same_rate(a.songs, wfs, rate, a.decode)
+    durations = []
+    if roll_size is not None:
+        wfs = _note_durations(wfs, rate, durations)
     draw = size is not None
 
     def on_finish(i, slot, st):
@@ -458,16 +521,20 @@ def main_songs(argv):
                          residual_path=os.path.join(a.residual_dir, stems[i] + '.residual.' + a.format) if keep else None,
                          stems=item[-1] if keep_stems else None, stems_dir=a.stems_dir, name=stems[i], flac=a.flac,
                          format=a.format, predictor=a.flac_predictor)
+    golds = [None] * len(stems)
     if a.gold_dir is not None:
         scored = []
-        for stem in stems:
+        for i, stem in enumerate(stems):
             gold = os.path.join(a.gold_dir, stem + '.mid')
             if os.path.isfile(gold):
                 scored.append((stem, os.path.join(a.out_dir, stem + '.mid'), gold))
+                golds[i] = gold
             else:
                 print('%s: no gold file in %s, left out of the scores' % (stem, a.gold_dir), file=sys.stderr)
         if scored:
             write_scores(*zip(*scored), collection_path=os.path.join(a.out_dir, 'scores.json'))
+    if roll_size is not None:
+        write_rolls(stems, [os.path.join(a.out_dir, s + '.mid') for s in stems], durations, a.roll_dir, roll_size, golds)
 
 
 def main(argv=None):
@@ -498,7 +565,9 @@ def main(argv=None):
     if a.spectrogram_dir is not None and a.traversal != 'song':
         raise SystemExit('--spectrogram-dir needs --traversal song (independent windows have no song-level spectra)')
     size = _spectrogram_size(a)
+    roll_size = _roll_size(a)
     wf, sr = next(_read_inputs([a.infile], a.decode))
+    duration = int(wf.shape[0]) / float(sr)
     if a.sr is None:                             # the model at the file's rate
         wf, model_sr, file_sr = _mono(wf, sr, a.decode), sr, None
     elif a.sr <= 0:
@@ -532,6 +601,9 @@ def main(argv=None):
                      predictor=a.flac_predictor)
     if a.gold is not None:
         write_scores([name], [a.outfile], [a.gold])
+    if roll_size is not None:
+        os.makedirs(a.roll_dir, exist_ok=True)
+        write_rolls([name], [a.outfile], [duration], a.roll_dir, roll_size, [a.gold])
 
 
 if __name__ == '__main__':

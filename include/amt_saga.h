@@ -353,6 +353,54 @@ int amt_score_check_notes(const int32_t *pitch, const int32_t *program, long lon
 int amt_score_pairs(const amt_score_args *args, void *stream);
 
 /* ------------------------------------------------------------------------ *
+ * Piano-roll images of note lists (stands where the reference's users plot a piano roll of a transcription against the
+ * gold MIDI of the MIDI/audio pairs it trains on, main.py:7, with matplotlib).  The rule lives in csrc/amt_roll_core.h.
+ * DESIGN.md 29.
+ *
+ * Times and lists are those of the scoring section: int64 microseconds, lists sorted by (pitch, on, off, program).  An
+ * image is int64 [10]: W, row_px, pitch_lo, pitch_hi, t0, t1, tick, pair, first output byte, reserved (0) -- W in
+ * 1..16384, 0 <= pitch_lo <= pitch_hi <= 127, row_px >= 1 with H = (pitch_hi - pitch_lo + 1) row_px <= 16384,
+ * W <= t1 - t0 <= 2^40, |t0| <= 2^61, tick in 0..2^40, pair 0 or 1.  Column x is [c_x, c_{x+1}), c_x = t0 +
+ * floor(x (t1 - t0) / W); pitch p owns rows (pitch_hi - p) row_px .. + row_px - 1.  A note covers [on, max(off, on + 1)).
+ * Per side and pixel: j = the pitch's last note with on < c_{x+1}; onset = on_j >= c_x; covered = max_{i <= j} end_i >
+ * c_x; the drawn note is j if it still sounds, else the first to attain that maximum.  Pixel: 0 / 1 (white / black key
+ * row) + 2 on a column that holds a multiple of tick where nothing is covered; 16 + 2 (group[program of the drawn note]
+ * mod 16) + onset for one list; 64 + 4 (est_covered | 2 gold_covered) + est_onset + 2 gold_onset for a pair.
+ * ------------------------------------------------------------------------ */
+typedef struct amt_roll_args {
+    const int32_t *est_pitch, *est_program;   /* device [n_est_total]: the estimates of all images back to back */
+    const int64_t *est_on, *est_off;
+    const int32_t *gold_pitch, *gold_program; /* device [n_gold_total]; read for the images with pair = 1 */
+    const int64_t *gold_on, *gold_off;
+    const int64_t *est_offsets_host;          /* HOST [n_images + 1]: image i draws estimates [est_offsets[i], est_offsets[i + 1]) */
+    const int64_t *gold_offsets_host;         /* HOST [n_images + 1] */
+    const int64_t *est_offsets, *gold_offsets;/* device [n_images + 1]: the same numbers, what the kernel reads */
+    const int64_t *image_meta_host;           /* HOST [n_images][10] */
+    const int64_t *image_meta;                /* device [n_images][10]: the same numbers */
+    const int32_t *group;                     /* device [128]: program -> group, drawn mod 16 */
+    void          *scratch;                   /* device, 16-byte aligned: the running maxima */
+    int64_t        scratch_bytes;             /* >= amt_roll_scratch_bytes(est_offsets[n_images], gold_offsets[n_images]) */
+    uint8_t       *out;                       /* device [out_bytes]: image i is H rows of W bytes from its first output byte */
+    int64_t        out_bytes;
+    int64_t        n_images;
+} amt_roll_args;
+/* Scratch bytes of amt_roll_draw for that many notes per side over the whole call (what a piano-roll plot of the
+ * reference's pairs, main.py:7, needs beside the lists); negative (AMT_E_INVALID) for a negative count or one above
+ * 2^40. */
+long long amt_roll_scratch_bytes(long long n_est_total, long long n_gold_total);
+/* The piano rolls of any number of transcriptions, alone or against gold (the plot a user of the reference's MIDI/audio
+ * pairs, main.py:7, makes on the host), in ONE launch enqueued on `stream`; nothing is waited for.  The work item is one
+ * (image, pitch): a workgroup scans the pitch's notes into running maxima of their ends, finds every column's note by
+ * binary search, and stores the pitch's row_px equal rows as one run with 16-byte stores.  No atomics: a byte does not
+ * depend on the schedule.  The kernel reads the device tables and holds every range inside the arrays whatever they say;
+ * an image whose device geometry would leave `out` is left unwritten; lists that are not sorted give other pixels, never a
+ * fault.  Images must not overlap in `out`.  All checks come before any HIP call.  AMT_E_INVALID with nothing written: a
+ * NULL pointer, a scratch that is not 16-byte aligned, n_images < 0 or above 2^24, host offsets that begin below 0 or
+ * decrease, an image with more than 2^31 - 1 notes on a side, a geometry outside the limits above, an image outside
+ * out[0 .. out_bytes).  AMT_E_SHAPE: scratch_bytes too small. */
+int amt_roll_draw(const amt_roll_args *args, void *stream);
+
+/* ------------------------------------------------------------------------ *
  * Spectral subtraction (replaces audio_complete.subtract, util_audio.py:221-259)
  * ------------------------------------------------------------------------ */
 typedef struct amt_subtract_args {
