@@ -1602,3 +1602,194 @@ def spectrogram_png(mags, refs, size=(1200, 500), axis='log', sr=44100, n_fft=20
 def save_spectrograms(mags, paths, refs, **kw):
     """spectrogram_png(mags, refs, ...) written to `paths`, one file per spectrogram, one write per file."""
     _write_files(spectrogram_png(mags, refs, **kw), paths)
+
+
+# ======================================================================================
+# Harmonic/percussive separation on the device, ahead of a transcription whose heads know pitched notes only
+# (drum tracks are rendered into every training song, util_audio.py:843; the gold is pitched, util_train_test.py:83)
+# ======================================================================================
+class HpssArgs(C.Structure):
+    """amt_hpss_args of amt_hpss_ragged (include/amt_saga.h)."""
+    _fields_ = [('mag', C.c_void_p), ('out_h', C.c_void_p), ('out_p', C.c_void_p), ('out_r', C.c_void_p),
+                ('med_t', C.c_void_p), ('med_f', C.c_void_p), ('frame_base', C.c_void_p), ('t_frames', C.c_void_p),
+                ('n', C.c_int64), ('pool_frames', C.c_int64), ('max_frames', C.c_int32), ('ldf', C.c_int32),
+                ('F', C.c_int32), ('kt', C.c_int32), ('kf', C.c_int32), ('power', C.c_float), ('margin_h', C.c_float),
+                ('margin_p', C.c_float)]
+
+
+def hpss_args(**fields):
+    """HpssArgs filled by _lib.args: a tensor gives its device pointer, None a NULL."""
+    return _lib.args(HpssArgs, **fields)
+
+
+HPSS_MAX_KERNEL = 63
+HPSS_POWERS = (1.0, 2.0, float('inf'))
+HPSS_MAX_MARGIN = 100.0
+
+
+def hpss_params(kernel=(31, 31), power=2.0, margin=(1.0, 1.0)):
+    """(kt, kf, power, margin_h, margin_p) of hpss / hpss_spectra, checked: kernel a pair of odd integers in 1..63,
+    power 1, 2 or inf, margin a pair of numbers in [1, 100].  ValueError otherwise; no device is touched."""
+    try:
+        kt, kf = kernel
+        ok = all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) and 1 <= k <= HPSS_MAX_KERNEL and k % 2 == 1
+                 for k in (kt, kf))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('hpss: kernel must be a pair of odd integers in 1..%d (frames, bins) . Got: %r'
+                         % (HPSS_MAX_KERNEL, kernel))
+    try:
+        power = float(power)
+    except (TypeError, ValueError):
+        power = float('nan')
+    if power not in HPSS_POWERS:
+        raise ValueError('hpss: power must be 1, 2 or inf . Got: %r' % (power,))
+    try:
+        mh, mp = (float(m) for m in margin)
+    except (TypeError, ValueError):
+        mh = mp = float('nan')
+    if not (1.0 <= mh <= HPSS_MAX_MARGIN and 1.0 <= mp <= HPSS_MAX_MARGIN):
+        raise ValueError('hpss: margin must be a pair of numbers in [1, %g] (harmonic, percussive) . Got: %r'
+                         % (HPSS_MAX_MARGIN, margin))
+    return int(kt), int(kf), power, mh, mp
+
+
+def _hpss_launch(pool, pool_frames, ldf, dev, fbase, frames, F, params, rest=False, medians=False):
+    """ONE amt_hpss_ragged launch on the current stream over the signals frames [fbase[i], + frames[i]) of the pool
+    [pool_frames, ldf] at `pool` (a tensor, or a device address the caller keeps alive): (harmonic, percussive, rest or
+    None, Ht or None, Pf or None), pools of the same shape; frames of no signal are left as allocated."""
+    kt, kf, power, mh, mp = params
+    lib = _lib.load()
+    outs = [torch.empty((pool_frames, ldf), dtype=torch.float32, device=dev) if on else None
+            for on in (True, True, rest, medians, medians)]
+    d_fb = to_dev(np.asarray(fbase, np.int64), torch.int64, dev)
+    d_tf = to_dev(np.asarray(frames, np.int32), torch.int32, dev)
+    a = hpss_args(mag=pool, out_h=outs[0], out_p=outs[1], out_r=outs[2], med_t=outs[3], med_f=outs[4],
+                       frame_base=d_fb, t_frames=d_tf, n=len(frames), pool_frames=pool_frames,
+                       max_frames=max(frames) if len(frames) else 0, ldf=ldf, F=F, kt=kt, kf=kf,
+                       power=power, margin_h=mh, margin_p=mp)
+    _lib.check(lib.amt_hpss_ragged(C.byref(a), stream_ptr()))
+    return outs
+
+
+def hpss_spectra(mags, n_fft, kernel=(31, 31), power=2.0, margin=(1.0, 1.0), medians=False):
+    """Median-filter harmonic/percussive separation (Fitzgerald 2010) of every magnitude spectrogram of `mags` -- float32
+    device tensors [T, >= F] frame-major, F = n_fft // 2 + 1, taken the way spectrogram_levels takes them (views of a
+    song pool included).  Returns one (harmonic, percussive) per spectrogram -- (harmonic, percussive, Ht, Pf) with
+    medians=True, the two median-filtered spectrograms -- each [T, row pitch] with the columns from F on zero.
+    kernel = (frames, bins), odd, 1..63; power 1, 2 or inf; margin = (harmonic, percussive) in [1, 100].  The rule:
+    DESIGN 30 -- scipy's 'reflect' ends on each spectrogram's own frames and bins, exact medians, librosa's softmask
+    in float32; with power = inf a tie is harmonic, where librosa.decompose.hpss gives a tie to neither side.
+    ONE amt_hpss_ragged launch for the whole list, on the current stream.  Spectrograms that are views of one allocation
+    (equal row pitch, a multiple of 4 floats, whole rows apart, not overlapping, spanning at most twice their own frames)
+    are read where they lie and the results are views of pools of that extent; any other list is first copied into one
+    packed pool."""
+    params = hpss_params(kernel, power, margin)
+    mags = [mags] if isinstance(mags, torch.Tensor) and mags.dim() == 2 else list(mags)
+    F = int(n_fft) // 2 + 1
+    for m in mags:
+        if not (isinstance(m, torch.Tensor) and m.is_cuda and m.dtype == torch.float32 and m.dim() == 2
+                and m.shape[1] >= F and (m.shape[1] == 1 or m.stride(1) == 1)):
+            raise ValueError('Invalid Input shape. Expected: float32 device tensors [T, >= %d] . Got: %s'
+                             % (F, tuple(m.shape) if hasattr(m, 'shape') else type(m).__name__))
+    if not mags:
+        return []
+    if len({m.device for m in mags}) != 1:
+        raise ValueError('Invalid Input shape. Expected: spectrograms of one device . Got: several')
+    frames = [int(m.shape[0]) for m in mags]
+    live = [m for m, t in zip(mags, frames) if t]
+    pitches = {int(m.stride(0)) for m in live if m.shape[0] > 1}
+    ldf = pitches.pop() if len(pitches) == 1 else ldf_of(n_fft)
+    # one pool = one allocation: tensors of different storages may lie whole rows apart by coincidence, any distance apart
+    in_place = bool(live) and not pitches and ldf >= F and ldf % 4 == 0 and \
+        len({m.untyped_storage().data_ptr() for m in live}) == 1
+    if in_place:
+        anchor = min(m.data_ptr() for m in live)
+        offs = [(m.data_ptr() - anchor) // 4 if t else 0 for m, t in zip(mags, frames)]
+        in_place = all(o % ldf == 0 for o in offs)
+        spans = sorted((o // ldf, o // ldf + t) for o, t in zip(offs, frames) if t)
+        in_place = in_place and all(a[1] <= b[0] for a, b in zip(spans, spans[1:]))
+        # the outputs are pools of the extent: a few regions far apart in a large pool are cheaper to copy
+        in_place = in_place and spans[-1][1] <= 2 * sum(frames)
+    if in_place:
+        fbase = [o // ldf for o in offs]
+        extent = max(b + t for b, t in zip(fbase, frames))
+        pool = anchor              # rows of `ldf` floats from the lowest spectrogram on; `mags` keeps them alive
+    else:
+        ldf = (F + 3) // 4 * 4
+        fbase = [int(b) for b in np.concatenate([[0], np.cumsum(frames)])[:-1]]
+        extent = max(1, sum(frames))
+        pool = torch.zeros((extent, ldf), dtype=torch.float32, device=mags[0].device)
+        for m, b, t in zip(mags, fbase, frames):
+            pool[b:b + t, :F].copy_(m[:, :F])
+    outs = _hpss_launch(pool, extent, ldf, mags[0].device, fbase, frames, F, params, medians=medians)
+    keep = [o for o in outs if o is not None]
+    return [tuple(o[b:b + t] for o in keep) for b, t in zip(fbase, frames)]
+
+
+def _hpss_plan(n_fft, hop):
+    """The plans amt_istft_ragged accepts; ValueError otherwise, before any device work."""
+    if int(n_fft) not in (1024, 2048, 4096) or int(hop) * 4 != int(n_fft):
+        raise ValueError('hpss: n_fft must be 1024, 2048 or 4096 and hop n_fft / 4 . Got: n_fft=%r, hop=%r' % (n_fft, hop))
+    return int(n_fft), int(hop)
+
+
+def hpss(waves, n_fft=2048, hop=512, kernel=(31, 31), power=2.0, margin=(1.0, 1.0), residual=False):
+    """Harmonic/percussive separation of waveforms: `waves`, a list of 1-d float32 device signals (or one), each of
+    more than n_fft / 2 samples.  ONE amt_stft_mag_ragged launch for all of them, ONE amt_hpss_ragged launch on the
+    magnitudes (hpss_spectra's rule and parameters), then ONE amt_istft_ragged launch per component with each signal's
+    own phases.  Returns one (harmonic, percussive) per signal -- (harmonic, percussive, rest) with residual=True, the
+    rest being max(S - Sh - Sp, 0), more than rounding only where a margin exceeds 1 -- each a 1-d float32 device
+    tensor of hop * (len // hop) samples, like the residual of a song walk.  n_fft in 1024 / 2048 / 4096 with
+    hop == n_fft / 4 (the plans of amt_istft_ragged); anything else, and a signal of <= n_fft / 2 samples, is a
+    ValueError before any device work.  Everything is enqueued on the current stream; nothing is waited for."""
+    params = hpss_params(kernel, power, margin)
+    n_fft, hop = _hpss_plan(n_fft, hop)
+    sigs = _device_signals(waves)
+    if len(sigs) > MAX_SIGNALS:
+        raise ValueError('Invalid Input shape. Expected: at most %d signals a call . Got: %d' % (MAX_SIGNALS, len(sigs)))
+    lens = [int(s.numel()) for s in sigs]
+    for L in lens:
+        if L <= n_fft // 2:
+            raise ValueError('Invalid Input shape. Expected: signals of more than n_fft / 2 = %d samples '
+                             '(reflect padding) . Got: %d' % (n_fft // 2, L))
+    lib, dev, n = _lib.load(), sigs[0].device, len(sigs)
+    plan, sp = _plan(n_fft, hop, True), stream_ptr()
+    F, ldf = n_fft // 2 + 1, ldf_of(n_fft)
+    frames = [1 + L // hop for L in lens]
+    fbase = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
+    pool_frames = int(fbase[-1])
+    samples = torch.empty((pool_frames * hop,), dtype=torch.float32, device=dev)
+    for s, b, L in zip(sigs, fbase, lens):
+        samples[int(b) * hop:int(b) * hop + L].copy_(s)
+    mag = torch.empty((pool_frames, ldf), dtype=torch.float32, device=dev)
+    ph = torch.empty((pool_frames, ldf, 2), dtype=torch.float32, device=dev)
+    d_fb, d_sb = to_dev(fbase[:-1].copy(), torch.int64, dev), to_dev(fbase[:-1] * hop, torch.int64, dev)
+    d_len, d_tf = to_dev(np.asarray(lens, np.int32), torch.int32, dev), to_dev(np.asarray(frames, np.int32), torch.int32, dev)
+    _lib.check(lib.amt_stft_mag_ragged(plan, ptr(samples), ptr(d_sb), ptr(d_len), n, max(lens), samples.numel(), sum(lens),
+                                       ptr(mag), ptr(ph), None, ptr(d_fb), pool_frames, ldf, sp))
+    parts = [o for o in _hpss_launch(mag, pool_frames, ldf, dev, fbase[:-1].tolist(), frames, F, params, rest=residual)[:3] if o is not None]
+    out_lens = [hop * (t - 1) for t in frames]
+    obase = np.concatenate([[0], np.cumsum(out_lens)]).astype(np.int64)
+    d_ob = to_dev(obase[:-1].copy(), torch.int64, dev)
+    out = torch.empty((len(parts), int(obase[-1])), dtype=torch.float32, device=dev)
+    for g, part in enumerate(parts):
+        _lib.check(lib.amt_istft_ragged(plan, ptr(part), ptr(ph), ptr(d_fb), ptr(d_tf), n, max(frames), pool_frames, ldf,
+                                        ptr(out[g]), ptr(d_ob), int(obase[-1]), sp))
+    return [tuple(out[g, int(a):int(a) + m] for g in range(len(parts))) for a, m in zip(obase[:-1], out_lens)]
+
+
+def save_hpss(waves, paths, sr, format='flac', **kw):
+    """hpss(waves, **kw) written out: paths[i] = (harmonic path, percussive path) of signal i, 24-bit FLAC through
+    save_flac or PCM-24 WAV through save_wav (format='wav'), all files in one encode call."""
+    if format not in ('flac', 'wav'):
+        raise ValueError('Requested attribute does not exist')
+    paths = [tuple(p) for p in paths]
+    n = 1 if isinstance(waves, torch.Tensor) and waves.dim() == 1 else len(waves)
+    if len(paths) != n or any(len(p) != 2 for p in paths):
+        raise ValueError('Invalid Input shape. Expected: one (harmonic, percussive) pair of paths per signal (%d) . Got: %d'
+                         % (n, len(paths)))
+    parts = hpss(waves, **kw)
+    flat, names = [w for pair in parts for w in pair[:2]], [p for pair in paths for p in pair]
+    (save_wav(flat, names, sr, fmt='pcm24') if format == 'wav' else save_flac(flat, names, sr))

@@ -46,6 +46,14 @@ provide for the inference direction:
     (--gold / --gold-dir), <stem>.roll.gold.png: estimate only, gold only, both.  Drawn and encoded on the device
     (amt_saga.roll); with --songs all rolls of the collection come from ONE rasteriser call after the last song.
 
+    --hpss [--hpss-kernel TxF, default 31x31] [--hpss-power {1,2,inf}, default 2] [--hpss-margin H,P, default 1,1] (both
+    modes): a median-filter harmonic/percussive split of the song on the device (audio.hpss) after resampling,
+    at the model's rate; the harmonic part is what is transcribed -- the heads were trained on pitched notes only, with
+    drum tracks in the audio (util_audio.py:843, util_train_test.py:83).  --percussive OUT.flac (one file) /
+    --percussive-dir DIR (with --songs, <stem>.percussive.flac) writes the percussive part through the writer --format,
+    --flac and --flac-predictor choose; with --spectrogram-dir also <stem>.percussive.png against the song's own maximum.
+    With --traversal song, residual + stems + percussive is the song.  Without --hpss nothing changes.
+
     --instrument-model NAME (both modes): the instrument head is the reference's model NAME (training.py:466-477; one of
     loop.INSTRUMENT_MODELS), fed the recipe arrays that model was trained on; the default is the plain CQT model.
 
@@ -90,6 +98,27 @@ def _model_option(instrument_model):
     return {} if instrument_model == 'instrument' else {'instrument_model': instrument_model}
 
 
+def _hpss_option(hpss, percussive=False):
+    """The `hpss` argument of transcribe / iter_transcribe_songs as audio.hpss's keywords: None (off) for None / False,
+    {} for True, a dict of kernel / power / margin checked by audio.hpss_params.  ValueError before any device work."""
+    if hpss is None or hpss is False:
+        if percussive:
+            raise ValueError('percussive=True needs hpss')
+        return None
+    opts = {} if hpss is True else hpss
+    if not isinstance(opts, dict) or set(opts) - {'kernel', 'power', 'margin'}:
+        raise ValueError("hpss: True, or a dict of 'kernel', 'power', 'margin' . Got: %r" % (hpss,))
+    audio.hpss_params(**opts)
+    return dict(opts)
+
+
+def _split(wf, p, opts):
+    """(harmonic, percussive) of one mono waveform at p.sr through audio.hpss with the model's p.N / p.H."""
+    w = wf if isinstance(wf, torch.Tensor) and wf.is_cuda else \
+        torch.from_numpy(np.ascontiguousarray(wf, dtype=np.float32).reshape(-1)).cuda()
+    return audio.hpss([w.to(torch.float32).reshape(-1)], n_fft=p.N, hop=p.H, **opts)[0][:2]
+
+
 def _make_loop(p, iters, heads, groups, weights_dir, guess, instrument_model='instrument'):
     loop = TranscriptionLoop(p, heads=heads, iters=iters, groups=groups, guess=guess, instrument_model=instrument_model)
     if weights_dir:
@@ -103,7 +132,8 @@ def _make_loop(p, iters, heads, groups, weights_dir, guess, instrument_model='in
 
 def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument', 'velocity'),
                groups=(0, 1, 2), weights_dir=None, guess='bank', loop=None, batch=1024, traversal='windows',
-               silence=1e-3, sr=None, residual=False, stems=False, instrument_model='instrument', on_finish=None):
+               silence=1e-3, sr=None, residual=False, stems=False, instrument_model='instrument', on_finish=None,
+               hpss=None, percussive=False):
     """wf: float32 mono waveform at params.sr -- or, with `sr` given, a waveform [n] or [n, channels] at `sr`, resampled
     to params.sr (and downmixed) on the device first (audio.resample): everything below, the length the note times are
     computed from included, then sees the resampled signal.  Returns (notes, events) where notes is the
@@ -122,9 +152,14 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
     instrument_model: which of the reference's ten instrument models the instrument head is (loop.INSTRUMENT_MODELS);
     no effect on a `loop` handed in.
     on_finish(0, 0, state) (traversal='song' only): called after the walk with the song's SongState, its pool still in
-    place -- iter_song_queue's hook; state.region_spectra([0]) is what write_song_spectrograms draws."""
+    place -- iter_song_queue's hook; state.region_spectra([0]) is what write_song_spectrograms draws.
+    hpss=True, or a dict of audio.hpss's kernel / power / margin: the waveform, once resampled, is split by audio.hpss
+    at params.N / params.H and the HARMONIC part (hop * (len // hop) samples) is what either traversal sees.
+    percussive=True (needs hpss: ValueError) appends the percussive waveform, a 1-d float32 device tensor, to what is
+    returned.  hpss=None: nothing changes."""
     if traversal not in ('windows', 'song'):
         raise ValueError('Requested attribute does not exist')
+    split = _hpss_option(hpss, percussive)
     if residual and traversal != 'song':
         raise ValueError("transcribe: residual=True needs traversal='song'")
     if stems and traversal != 'song':
@@ -134,6 +169,10 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
         loop = _make_loop(p, iters, heads, groups, weights_dir, guess, **_model_option(instrument_model))
     if sr is not None:
         wf = audio.resample(wf, sr, p.sr)                              # 1-d float32, on the device; sr == p.sr: a downmix
+    perc = ()
+    if split is not None:
+        wf, drums = _split(wf, p, split)
+        perc = (drums,) if percussive else ()
     on_dev = isinstance(wf, torch.Tensor) and wf.is_cuda
     if traversal == 'song':
         wf32 = wf if on_dev else np.ascontiguousarray(wf, dtype=np.float32)      # (run_songs takes either)
@@ -142,7 +181,7 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
         if on_finish is not None:
             on_finish(0, 0, st)
         notes = ev.song_events_to_notes(evs, 1 + len(wf32) // p.H, len(wf32), sr=p.sr)
-        return (notes, evs) + ((st.residual[0],) if residual else ()) + ((st.stem_audio[0],) if stems else ())
+        return (notes, evs) + ((st.residual[0],) if residual else ()) + ((st.stem_audio[0],) if stems else ()) + perc
     L = p.H * (p.timing_frames - 1)
     wf_dev = wf if on_dev else torch.from_numpy(np.ascontiguousarray(wf, dtype=np.float32)).cuda()
     wins, starts = cut_windows(wf.cpu().numpy() if on_dev else np.asarray(wf, dtype=np.float32), L, L // 2)
@@ -158,18 +197,26 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
     evs = np.concatenate(all_ev, axis=1)
     notes = ev.events_to_notes(evs, p.timing_frames, L, sr=p.sr,
                                window_start_s=[s / p.sr for s in starts])
-    return ev.merge_overlap_duplicates(notes), evs
+    return (ev.merge_overlap_duplicates(notes), evs) + perc
 
 
 def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', 'instrument', 'velocity'),
                           groups=(0, 1, 2), weights_dir=None, guess='bank', loop=None, slots=8, silence=1e-3, poll=16,
-                          pool_frames=None, residual=False, stems=False, instrument_model='instrument', on_finish=None):
+                          pool_frames=None, residual=False, stems=False, instrument_model='instrument', on_finish=None,
+                          hpss=None, percussive=False):
     """The song queue behind transcribe_songs (TranscriptionLoop.iter_song_queue): yields (index, notes, events) as
     each song finishes, in finishing order -- (index, notes, events[, residual waveform][, stems [G, samples]]) with
     residual=True / stems=True.  wfs: a sequence or an iterator of mono float32 waveforms at params.sr; an
     item may also be a (waveform [n] or [n, channels], sr) pair, which is resampled to params.sr on the device as it is
     pulled (audio.resample).  on_finish(index, slot, state): iter_song_queue's hook, called when a song is found
-    finished, before its slot and its pool region are given away."""
+    finished, before its slot and its pool region are given away.
+    hpss (True or a dict, see transcribe): every song is split by audio.hpss as it is pulled, after resampling, and its
+    harmonic part is what the queue walks.  percussive (needs hpss: ValueError): the song's percussive waveform is
+    appended to what is yielded; a dict in place of True is also filled with {index: percussive waveform} while the
+    song is in flight, which is where an on_finish hook finds it."""
+    want = percussive is True or isinstance(percussive, dict)
+    split = _hpss_option(hpss, want)
+    drums = percussive if isinstance(percussive, dict) else {}
     p = params or Hyperparams(N=2048)
     if loop is None:
         loop = _make_loop(p, iters, heads, groups, weights_dir, guess, **_model_option(instrument_model))
@@ -181,6 +228,10 @@ def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', '
                 w = audio.resample(wf[0], wf[1], p.sr)
             else:
                 w = np.ascontiguousarray(wf, dtype=np.float32).reshape(-1)
+            if split is not None:
+                w, drum = _split(w, p, split)
+                if want:                                           # (kept on the device only for a caller that asked)
+                    drums[i] = drum
             lens[i] = len(w)
             yield w
     for item in loop.iter_song_queue(feed(), slots, max_notes=iters, silence=silence, poll=poll,
@@ -192,7 +243,8 @@ def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', '
         notes = ev.song_events_to_notes(one, 1 + n // p.H, n, sr=p.sr)
         for note in notes:
             note['song'] = i
-        yield (i, notes, evs) + tuple(item[2:])
+        drum = drums.pop(i, None)
+        yield (i, notes, evs) + tuple(item[2:]) + ((drum,) if want else ())
 
 
 def transcribe_songs(wfs, params=None, slots=8, **kw):
@@ -264,11 +316,52 @@ def _shared_options(ap, sr_help, **stems_dir):
     ap.add_argument('--spectrogram-dir', default=None, metavar='DIR', help=_SPECTROGRAM_HELP)
     ap.add_argument('--spectrogram-size', default='1200x500', metavar='WxH',
                     help='pixels of every --spectrogram-dir image, each side 1 .. 16384 (default 1200x500)')
+    ap.add_argument('--hpss', action='store_true', help=_HPSS_HELP)
+    ap.add_argument('--hpss-kernel', default='31x31', metavar='TxF',
+                    help='median lengths of --hpss in frames x bins, each odd and in 1 .. 63 (default 31x31)')
+    ap.add_argument('--hpss-power', default='2', choices=('1', '2', 'inf'),
+                    help='exponent of the soft masks of --hpss; inf: hard masks, a tie is harmonic (default 2)')
+    ap.add_argument('--hpss-margin', default='1,1', metavar='H,P',
+                    help='margins of --hpss for the harmonic and the percussive mask, each in 1 .. 100 (default 1,1); '
+                         'above 1 a third part belongs to neither and is dropped')
     ap.add_argument('--roll-dir', default=None, metavar='DIR', help=_ROLL_HELP)
     ap.add_argument('--roll-width', type=int, default=1200, metavar='W',
                     help='pixel columns of every --roll-dir image, 1 .. 16384 (default 1200)')
     ap.add_argument('--roll-row-px', type=int, default=5, metavar='N',
                     help='pixel rows per pitch of every --roll-dir image, 1 .. 186 (default 5: 440 rows)')
+
+
+_HPSS_HELP = ('split every song into a harmonic and a percussive part on the device before it is transcribed (median '
+              'filtering, after resampling, at the model\'s rate) and transcribe the harmonic part: the heads know pitched '
+              'notes only, and a drum hit is energy none of them can explain.  With --traversal song, residual + stems + '
+              'percussive is the song.  Without --hpss nothing changes')
+
+
+def _hpss_cli(a, percussive):
+    """audio.hpss's keywords from --hpss-kernel / --hpss-power / --hpss-margin, or None without --hpss; `percussive` (the
+    value of --percussive / --percussive-dir) without --hpss and malformed strings are refused, before any file is read."""
+    if not a.hpss:
+        if percussive is not None:
+            raise SystemExit('--percussive / --percussive-dir needs --hpss (there is no percussive part without the split)')
+        return None
+    try:
+        kernel = tuple(int(k) for k in a.hpss_kernel.lower().split('x'))
+        if len(kernel) != 2:
+            raise ValueError
+    except ValueError:
+        raise SystemExit('--hpss-kernel: expected TxF, two odd integers in 1 .. 63 . Got: %s' % a.hpss_kernel)
+    try:
+        margin = tuple(float(m) for m in a.hpss_margin.split(','))
+        if len(margin) != 2:
+            raise ValueError
+    except ValueError:
+        raise SystemExit('--hpss-margin: expected H,P, two numbers in 1 .. 100 . Got: %s' % a.hpss_margin)
+    for option, given in (('--hpss-kernel', dict(kernel=kernel)), ('--hpss-margin', dict(margin=margin))):
+        try:
+            audio.hpss_params(**given)
+        except ValueError as e:
+            raise SystemExit('%s: %s' % (option, e))
+    return dict(kernel=kernel, power=float(a.hpss_power), margin=margin)
 
 
 def _check_writer(a):
@@ -314,7 +407,7 @@ def _mono(wf, sr, decode):
 
 
 def write_song_audio(rate, residual=None, residual_path=None, stems=None, stems_dir=None, name=None, flac='host',
-                     format='flac', predictor='fixed'):
+                     format='flac', predictor='fixed', percussive=None, percussive_path=None):
     """What a song walk kept, as 24-bit FLAC at `rate`: `residual` (1-d device tensor) to residual_path, and / or the rows
     of `stems` [G, samples] to <stems_dir>/<name>.group<g>.flac, g the reference group id of the row (CLI_GROUPS).
     flac='host': the VERBATIM writer of amt_saga.flac, file by file (the default: the bytes every earlier call wrote);
@@ -323,7 +416,9 @@ def write_song_audio(rate, residual=None, residual_path=None, stems=None, stems_
     format='wav': PCM-24 WAV instead, <name>.group<g>.wav, through audio.save_wav -- one pack call and one copy for the
     residual and all stems of the song; `flac` then has no effect.
     predictor='lpc' (with flac='device'): save_flac's LPC subframes beside the fixed predictors; the host writer has no
-    predictors and refuses it."""
+    predictors and refuses it.
+    percussive (1-d device tensor, the percussive part of an --hpss split) goes to percussive_path the same way, in the
+    same call."""
     if flac not in FLAC_WRITERS or format not in FORMATS or predictor not in FLAC_PREDICTORS:
         raise ValueError('Requested attribute does not exist')
     if predictor == 'lpc' and flac == 'host' and format == 'flac':
@@ -338,6 +433,10 @@ def write_song_audio(rate, residual=None, residual_path=None, stems=None, stems_
             waves.append(row)
             paths.append(os.path.join(stems_dir, '%s.group%d.%s' % (name, g, format)))
             notes.append('stem of group %d -> %s' % (g, paths[-1]))
+    if percussive is not None:
+        waves.append(percussive)
+        paths.append(percussive_path)
+        notes.append('percussive -> %s' % percussive_path)
     if not waves:
         return
     if format == 'wav':
@@ -361,14 +460,15 @@ def _spectrogram_size(a):
         raise SystemExit('--spectrogram-size: ' + str(e))
 
 
-def write_song_spectrograms(st, slot, directory, name, size=(1200, 500)):
+def write_song_spectrograms(st, slot, directory, name, size=(1200, 500), percussive=None):
     """The pictures of a finished song (plot_specs, util_audio.py:938-960: the reference's before / after comparison):
     <directory>/<name>.song.png from an STFT of the song's samples in the pool, <name>.residual.png from the region of
     the pool the slides wrote back, <name>.group<g>.png from its stem regions (g the reference group id of the row,
     CLI_GROUPS) -- SongState.region_spectra(slot), so the state keeps residual and stems and the song is finished
     (ValueError otherwise).  Every image: dB over 80 dB below the SONG's maximum (the slot's ref_mag, read on the
     device), log frequency axis, `size` = (W, H) pixels.  ONE audio.spectrogram_levels launch and ONE audio.png_encode
-    call for all of them, on the walk's stream and ahead of the slot's release."""
+    call for all of them, on the walk's stream and ahead of the slot's release.  percussive (the percussive waveform of
+    an --hpss split): also <name>.percussive.png, from its STFT, against the same maximum, in the same two calls."""
     residual, stems = st.region_spectra([slot])[0]
     p, f0 = st.lp.p, st.region[slot]
     song = audio.AudioBatch(st.samples[f0 * p.H:f0 * p.H + st.lens[slot]][None, :], p.N, p.H, sample_rate=p.sr).stft(False)
@@ -380,6 +480,9 @@ def write_song_spectrograms(st, slot, directory, name, size=(1200, 500)):
         for row, g in zip(stems.unbind(0), CLI_GROUPS):
             mags.append(row)
             kinds.append('group%d' % g)
+    if percussive is not None:
+        mags.append(audio.AudioBatch(percussive[None, :], p.N, p.H, sample_rate=p.sr).stft(False).mag[0])
+        kinds.append('percussive')
     paths = [os.path.join(directory, '%s.%s.png' % (name, k)) for k in kinds]
     audio.save_spectrograms(mags, paths, [st.refs['ref_mag'][slot]] * len(mags), size=size, sr=p.sr, n_fft=p.N)
     for path in paths:
@@ -467,6 +570,9 @@ def main_songs(argv):
     ap.add_argument('--residual-dir', default=None,
                     help='write <stem>.residual.flac per song as it finishes: what the walk left after every subtraction, '
                          '24-bit FLAC at the rate the model runs at (with --sr, the resampled rate)')
+    ap.add_argument('--percussive-dir', default=None, metavar='DIR',
+                    help='with --hpss: write <stem>.percussive.flac per song as it finishes, the percussive part of the '
+                         'split, through the writer --format, --flac and --flac-predictor choose')
     _shared_options(ap, 'rate the model runs at; every file is resampled to it from its own rate (mixed rates allowed)',
                     help='write <stem>.group<g>.flac per song and instrument group as it finishes: what the subtractions '
                          'took out of the song, 24-bit FLAC at the rate the model runs at')
@@ -476,13 +582,14 @@ def main_songs(argv):
                          'without a gold file is named on stderr and left out')
     a = ap.parse_args(argv)
     _check_writer(a)
+    split = _hpss_cli(a, a.percussive_dir)
     size = _spectrogram_size(a)
     roll_size = _roll_size(a)
     if a.gold_dir is not None and not os.path.isdir(a.gold_dir):
         raise SystemExit('--gold-dir: %s is not a directory' % a.gold_dir)
     os.makedirs(a.out_dir, exist_ok=True)
     keep, keep_stems = a.residual_dir is not None, a.stems_dir is not None
-    for d in (a.residual_dir, a.stems_dir, a.spectrogram_dir, a.roll_dir):
+    for d in (a.residual_dir, a.stems_dir, a.spectrogram_dir, a.roll_dir, a.percussive_dir):
         if d is not None:
             os.makedirs(d, exist_ok=True)
     stems = [os.path.splitext(os.path.basename(f))[0] for f in a.songs]
@@ -507,20 +614,30 @@ def main_songs(argv):
         wfs = _note_durations(wfs, rate, durations)
     draw = size is not None
 
+    drums = {}                                   # {song: percussive waveform} of the songs in flight, with --hpss
+
     def on_finish(i, slot, st):
-        write_song_spectrograms(st, slot, a.spectrogram_dir, stems[i], size)
+        write_song_spectrograms(st, slot, a.spectrogram_dir, stems[i], size, percussive=drums.get(i))
+    split_options = {} if split is None else dict(hpss=split, percussive=drums)
     queue = iter_transcribe_songs(wfs, Hyperparams(N=2048, sr=rate), iters=a.iters, weights_dir=a.weights, guess=a.guess,
                                   slots=a.slots, residual=keep or draw, stems=keep_stems or draw, groups=CLI_GROUPS,
-                                  instrument_model=a.instrument_model, on_finish=on_finish if draw else None)
+                                  instrument_model=a.instrument_model, on_finish=on_finish if draw else None,
+                                  **split_options)
     for item in queue:
         i, notes = item[0], item[1]
+        drum = item[-1] if split is not None else None
+        if split is not None:
+            item = item[:-1]
         out = os.path.join(a.out_dir, stems[i] + '.mid')
         ev.write_midi(notes, out)
         print('%d notes -> %s' % (len(notes), out))
         write_song_audio(rate, residual=item[3] if keep else None,
                          residual_path=os.path.join(a.residual_dir, stems[i] + '.residual.' + a.format) if keep else None,
                          stems=item[-1] if keep_stems else None, stems_dir=a.stems_dir, name=stems[i], flac=a.flac,
-                         format=a.format, predictor=a.flac_predictor)
+                         format=a.format, predictor=a.flac_predictor,
+                         percussive=drum if a.percussive_dir is not None else None,
+                         percussive_path=os.path.join(a.percussive_dir, stems[i] + '.percussive.' + a.format)
+                         if a.percussive_dir is not None else None)
     golds = [None] * len(stems)
     if a.gold_dir is not None:
         scored = []
@@ -554,8 +671,12 @@ def main(argv=None):
                          'subtractions took out of the song, 24-bit FLAC at the rate the model runs at')
     ap.add_argument('--gold', default=None, metavar='GOLD.mid',
                     help='score the written file against this gold MIDI file: <outfile stem>.score.json beside it')
+    ap.add_argument('--percussive', default=None, metavar='OUT.flac',
+                    help='with --hpss: write the percussive part of the split, through the writer --format, --flac and '
+                         '--flac-predictor choose')
     a = ap.parse_args(argv)
     _check_writer(a)
+    split = _hpss_cli(a, a.percussive)
     if a.gold is not None and not os.path.isfile(a.gold):
         raise SystemExit('--gold: %s: no such file' % a.gold)
     if a.residual is not None and a.traversal != 'song':
@@ -581,7 +702,14 @@ def main(argv=None):
         if not int(st.finished[slot]):
             raise SystemExit('--spectrogram-dir: the walk stopped before the end of the song')
         os.makedirs(a.spectrogram_dir, exist_ok=True)
-        write_song_spectrograms(st, slot, a.spectrogram_dir, name, size)
+        write_song_spectrograms(st, slot, a.spectrogram_dir, name, size, percussive=drums.get(0))
+    drums = {}
+    if split is not None:
+        # the split here, at the model's rate, so that the walk's hook can draw the percussive part; transcribe() then
+        # sees the harmonic waveform at its own rate and splits nothing
+        p = Hyperparams(N=2048, sr=model_sr)
+        wf, drums[0] = _split(wf if file_sr is None else audio.resample(wf, file_sr, model_sr), p, split)
+        file_sr = None
     got = transcribe(wf, Hyperparams(N=2048, sr=model_sr), iters=a.iters, weights_dir=a.weights, guess=a.guess,
                      traversal=a.traversal, sr=file_sr, residual=a.residual is not None or draw,
                      stems=a.stems_dir is not None or draw, groups=CLI_GROUPS, instrument_model=a.instrument_model,
@@ -598,7 +726,8 @@ def main(argv=None):
     write_song_audio(model_sr, residual=got[2] if a.residual is not None else None, residual_path=a.residual,
                      stems=got[-1] if a.stems_dir is not None else None, stems_dir=a.stems_dir,
                      name=name, flac=a.flac, format=a.format,
-                     predictor=a.flac_predictor)
+                     predictor=a.flac_predictor, percussive=drums.get(0) if a.percussive is not None else None,
+                     percussive_path=a.percussive)
     if a.gold is not None:
         write_scores([name], [a.outfile], [a.gold])
     if roll_size is not None:

@@ -401,6 +401,49 @@ long long amt_roll_scratch_bytes(long long n_est_total, long long n_gold_total);
 int amt_roll_draw(const amt_roll_args *args, void *stream);
 
 /* ------------------------------------------------------------------------ *
+ * Harmonic/percussive separation of magnitude spectrograms by median filtering (Fitzgerald 2010), in front of the
+ * transcription: the reference renders drum tracks into every training song (util_audio.py:843) and hands the heads
+ * pitched notes only (relevant_notes(..., include_drums=False), util_train_test.py:83; validate_note rejects is_drum,
+ * util_train_test.py:159), so a drum hit is energy no head can explain.  The rule lives in csrc/amt_hpss_core.h.
+ * DESIGN.md 30.
+ *
+ * S [T][ldf] float32 frame-major with F <= ldf live bins, finite values in [0, 2^100].  idx(j, n) = j mod 2n
+ * (non-negative), mapped to 2n - 1 - j where that is >= n.  Ht[t][f] = the median of S[idx(t + d, T)][f] over the kt
+ * frames around t, Pf[t][f] the median of S[t][idx(f + d, F)] over the kf bins around f: exact, an input value.
+ * soft(X, R): Z = max(X, R); Z < FLT_MIN -> 0.5 when both margins are 1, else 0; otherwise a = X / Z, b = R / Z, squared
+ * when power == 2, a / (a + b), every operation single-rounded float32.  mask_h = soft(Ht, Pf margin_h), mask_p =
+ * soft(Pf, Ht margin_p); power = inf: mask_h = (Ht >= Pf margin_h), mask_p = (Pf > Ht margin_p).  Sh = S mask_h,
+ * Sp = S mask_p, and on request Sr = max((S - Sh) - Sp, 0).
+ * ------------------------------------------------------------------------ */
+typedef struct amt_hpss_args {
+    const float   *mag;                       /* device [pool_frames][ldf]: the pool the signals lie in */
+    float         *out_h, *out_p;             /* device, pools of the same shape: harmonic and percussive magnitudes */
+    float         *out_r;                     /* device, a pool of the same shape, or NULL: max((S - Sh) - Sp, 0) */
+    float         *med_t, *med_f;             /* device, pools of the same shape, or NULL: Ht and Pf */
+    const int64_t *frame_base;                /* device [n]: signal i is frames [frame_base[i], + t_frames[i]) */
+    const int32_t *t_frames;                  /* device [n] */
+    int64_t        n;
+    int64_t        pool_frames;
+    int32_t        max_frames;                /* HOST value: the longest t_frames; it sizes the grid, a longer signal is left unwritten */
+    int32_t        ldf, F;                    /* row pitch in floats (a multiple of 4) and live bins */
+    int32_t        kt, kf;                    /* odd, 1..63 */
+    float          power;                     /* 1, 2 or +inf */
+    float          margin_h, margin_p;        /* 1..100 */
+} amt_hpss_args;
+/* The split of any number of spectrograms in ONE launch enqueued on `stream`, ahead of a transcription whose heads know
+ * pitched notes only (util_audio.py:843, util_train_test.py:83, util_train_test.py:159); nothing is waited for.  The
+ * tables are amt_istft_ragged's.  Outputs go to the signal's own frames of out_h / out_p (and out_r / med_t / med_f), pad columns
+ * F..ldf-1 as zero; frames that belong to no signal are not written.  Reflection happens at the signal's own ends: a
+ * signal's result is bit-identical to the same signal alone, whatever else the launch holds.  No atomics.  The kernel
+ * reads the device tables and holds every range inside the pools whatever they say: a signal whose frames would leave
+ * the pool, or with t_frames outside 1..max_frames, is left unwritten.  Signals must not overlap.  n = 0 and
+ * max_frames = 0 are AMT_OK with nothing launched.  All checks come before any HIP call.  AMT_E_INVALID with nothing
+ * written: a NULL pointer (out_r / med_t / med_f excepted), an output that is the input or another output, an even or
+ * out-of-range kernel, a power other than the three, a margin outside [1, 100], F < 1, F > ldf, ldf % 4 != 0, a negative
+ * count. */
+int amt_hpss_ragged(const amt_hpss_args *args, void *stream);
+
+/* ------------------------------------------------------------------------ *
  * Spectral subtraction (replaces audio_complete.subtract, util_audio.py:221-259)
  * ------------------------------------------------------------------------ */
 typedef struct amt_subtract_args {
