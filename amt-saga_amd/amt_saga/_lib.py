@@ -129,6 +129,9 @@ PROTOTYPES = {
     'amt_roll_scratch_bytes': (C.c_longlong, [C.c_longlong, C.c_longlong]),
     'amt_roll_draw': (C.c_int, [vp, vp]),                        # (amt_roll_args *: roll.RollArgs)
     'amt_hpss_ragged': (C.c_int, [vp, vp]),                      # (amt_hpss_args *: audio.HpssArgs)
+    'amt_beat_scratch_bytes': (C.c_longlong, [C.c_longlong, C.c_longlong, C.c_int, C.c_longlong]),
+    'amt_beat_envelope': (C.c_int, [vp, vp]),                    # (amt_beat_env_args *: beat.EnvArgs)
+    'amt_beat_track': (C.c_int, [vp, vp]),                       # (amt_beat_track_args *: beat.TrackArgs)
     'amt_istft': (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp,
                             C.c_size_t, vp]),
     'amt_istft_ragged': (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int, vp, vp, C.c_longlong, vp]),

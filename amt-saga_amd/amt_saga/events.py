@@ -14,7 +14,9 @@ half a window).  Host-side, plain Python: a few hundred integers per song.
   * notes that the 50 %-overlapped windows both report (same pitch and program,
     onsets within `merge_tol_s`) are merged, keeping the longer one;
   * the file is SMF format 1, 480 ticks per quarter at 120 bpm (1 tick = 1/960 s),
-    one track per program (channels 0-15 round-robin, skipping 9 = drums).
+    one track per program (channels 0-15 round-robin, skipping 9 = drums);
+  * given the beats of amt_saga.beat, write_midi writes a tempo map instead (tempo_anchors): every beat on a multiple
+    of 480 ticks, time 0 on tick 0, note times unchanged in seconds to within half a tick plus the tempo rounding.
 """
 import struct
 
@@ -100,19 +102,90 @@ def _vlq(v):
     return bytes(reversed(out))
 
 
-def write_midi(notes, path):
-    """Write the note list as a format-1 Standard MIDI File."""
+QUANTIZE_DIVISIONS = (1, 2, 3, 4, 6, 8, 12)          # grid points per quarter that divide 480 ticks
+MAX_TEMPO_US = 0xFFFFFF                              # a set-tempo event holds three bytes
+
+
+def tempo_anchors(beats):
+    """[(seconds, tick)] of a tempo map through the beat times `beats` (seconds, strictly increasing, none negative; at
+    least two): it starts at (0, 0) -- nothing is shifted against the audio -- and every beat it keeps falls on a multiple
+    of 480 ticks, one quarter per beat.  The lead-in, with i0 = beats[1] - beats[0]: a first beat before i0 / 2 is
+    dropped as a grid point ([0, beats[1]) is one quarter); otherwise [0, beats[0]) holds max(1, round(beats[0] / i0))
+    quarters."""
+    b = [float(t) for t in beats]
+    if len(b) < 2 or b[0] < 0 or any(not y > x for x, y in zip(b, b[1:])) or b[-1] == float('inf'):
+        raise ValueError('Invalid Input shape. Expected: at least two beat times, >= 0 and strictly increasing . Got: %d'
+                         % len(b))
+    i0 = b[1] - b[0]
+    if b[0] < i0 / 2:
+        b, lead = b[1:], 1
+    else:
+        lead = max(1, int(round(b[0] / i0)))
+    return [(0.0, 0)] + [(t, TICKS_PER_QUARTER * (lead + k)) for k, t in enumerate(b)]
+
+
+def _anchor_tempos(anchors):
+    """round(us per quarter) of every anchor's segment, the last anchor repeating the segment before it."""
+    tempos = []
+    for (s0, k0), (s1, k1) in zip(anchors, anchors[1:]):
+        us = int(round((s1 - s0) * 1e6 * TICKS_PER_QUARTER / (k1 - k0)))
+        if not 1 <= us <= MAX_TEMPO_US:
+            raise ValueError('Invalid Input shape. Expected: beats between 1 us and %.3f s a quarter apart . Got: %.6f s'
+                             % (MAX_TEMPO_US * 1e-6, (s1 - s0) * TICKS_PER_QUARTER / (k1 - k0)))
+        tempos.append(us)
+    return tempos + tempos[-1:]
+
+
+def _anchor_ticks(anchors):
+    """seconds -> tick (a float) by piecewise-linear interpolation through the anchors, the last segment extended."""
+    secs = [a[0] for a in anchors]
+
+    def tick(t):
+        k = min(max(int(np.searchsorted(secs, t, side='right')) - 1, 0), len(anchors) - 2)
+        (s0, k0), (s1, k1) = anchors[k], anchors[k + 1]
+        return k0 + (t - s0) * (k1 - k0) / (s1 - s0)
+    return tick
+
+
+def write_midi(notes, path, beats=None, quantize=None):
+    """Write the note list as a format-1 Standard MIDI File: 480 ticks per quarter at 120 bpm.
+    beats: beat times in seconds (beat.beat_track's).  With at least two, the first track carries the tempo map of
+    tempo_anchors(beats) -- one set-tempo event per anchor, round(us per quarter) of the segment it opens -- and note
+    ticks come from the interpolation through the anchors, so a beat is a bar-line candidate in a notation program while
+    every note keeps its time in seconds to within half a tick plus the tempo rounding.  quantize=DIV (1, 2, 3, 4, 6, 8,
+    12) then snaps onsets to 480 / DIV ticks and keeps each duration, at least one tick.  beats=None, an empty list or a
+    single beat writes the fixed-tempo file, byte for byte what it was without these arguments (quantize has no grid
+    to snap to there and is not applied)."""
+    if quantize is not None and not (isinstance(quantize, (int, np.integer)) and not isinstance(quantize, bool)
+                                     and quantize in QUANTIZE_DIVISIONS):
+        raise ValueError('write_midi: quantize must be one of %s . Got: %r' % (', '.join(map(str, QUANTIZE_DIVISIONS)), quantize))
+    mapped = beats is not None and len(beats) >= 2
+    if mapped:
+        anchors = tempo_anchors(beats)
+        tick_of = _anchor_ticks(anchors)
+        head, last = b'', 0
+        for (_, k), us in zip(anchors, _anchor_tempos(anchors)):
+            head += _vlq(k - last) + b'\xff\x51\x03' + struct.pack('>I', us)[1:]
+            last = k
+        head += b'\x00\xff\x2f\x00'
+    else:
+        tick_of = lambda t: t * TICKS_PER_SECOND                      # noqa: E731
+        head = b'\x00\xff\x51\x03' + struct.pack('>I', TEMPO_US_PER_QUARTER)[1:] + b'\x00\xff\x2f\x00'
+    grid = TICKS_PER_QUARTER // int(quantize) if mapped and quantize else 0
     programs = sorted({n['program'] for n in notes})
     chans = [c for c in range(16) if c != 9]
-    tracks = [b'\x00\xff\x51\x03' + struct.pack('>I', TEMPO_US_PER_QUARTER)[1:] + b'\x00\xff\x2f\x00']
+    tracks = [head]
     for i, prog in enumerate(programs):
         ch = chans[i % len(chans)]
         evs = []
         for n in notes:
             if n['program'] != prog:
                 continue
-            t_on = int(round(n['start'] * TICKS_PER_SECOND))
-            t_off = max(int(round(n['end'] * TICKS_PER_SECOND)), t_on + 1)
+            t_on = max(int(round(tick_of(n['start']))), 0) if mapped else int(round(tick_of(n['start'])))
+            t_off = max(int(round(tick_of(n['end']))), t_on + 1)
+            if grid:
+                snapped = (2 * t_on + grid) // (2 * grid) * grid       # the nearest grid point, a tie upwards
+                t_on, t_off = snapped, snapped + (t_off - t_on)
             evs.append((t_on, 1, bytes([0x90 | ch, n['pitch'] & 0x7F, min(max(n['velocity'], 1), 127)])))
             evs.append((t_off, 0, bytes([0x80 | ch, n['pitch'] & 0x7F, 0])))
         evs.sort(key=lambda e: (e[0], e[1]))

@@ -54,6 +54,12 @@ provide for the inference direction:
     --flac and --flac-predictor choose; with --spectrogram-dir also <stem>.percussive.png against the song's own maximum.
     With --traversal song, residual + stems + percussive is the song.  Without --hpss nothing changes.
 
+    --tempo-map [--quantize DIV] (both modes): the beats of every song, tracked on the device (amt_saga.beat)
+    on the signal as given -- after resampling, before any --hpss split -- go into the .mid as a tempo map, every beat on a
+    multiple of 480 ticks and every note where it was in seconds to within half a tick; --quantize snaps onsets to 1/DIV
+    of a beat and is refused without --tempo-map.  --beats-out FILE (one file) / --beats-dir DIR (with --songs,
+    <stem>.beats.txt) writes the beat times, one per line.  Without these the .mid is byte for byte what it was.
+
     --instrument-model NAME (both modes): the instrument head is the reference's model NAME (training.py:466-477; one of
     loop.INSTRUMENT_MODELS), fed the recipe arrays that model was trained on; the default is the plain CQT model.
 
@@ -69,7 +75,7 @@ import sys
 import numpy as np
 import torch
 
-from . import audio, events as ev, flac as host_flac, png as host_png, roll as host_roll, score as host_score, wav as host_wav
+from . import audio, beat as beat_mod, events as ev, flac as host_flac, png as host_png, roll as host_roll, score as host_score, wav as host_wav
 from .hyperparams import Hyperparams
 from .loop import INSTRUMENT_MODELS, TranscriptionLoop
 
@@ -112,6 +118,29 @@ def _hpss_option(hpss, percussive=False):
     return dict(opts)
 
 
+def _beats_option(beats, p):
+    """The `beats` argument of transcribe / iter_transcribe_songs as beat.beat_track's keywords: None (off) for None /
+    False, {} for True, a dict of beat.params's bpm / tightness / mean_s / centre / octaves, checked at the model's rate
+    and hop.  ValueError before any device work."""
+    if beats is None or beats is False:
+        return None
+    opts = {} if beats is True else beats
+    if not isinstance(opts, dict) or set(opts) - {'bpm', 'tightness', 'mean_s', 'centre', 'octaves'}:
+        raise ValueError("beats: True, or a dict of 'bpm', 'tightness', 'mean_s', 'centre', 'octaves' . Got: %r" % (beats,))
+    beat_mod.params(p.sr, p.H, **opts)
+    return dict(opts)
+
+
+def _track(wf, p, opts):
+    """beat.beat_track's dict(period, tempo, beats, frames) of one mono waveform at p.sr, at the model's p.N / p.H; a
+    signal too short for the STFT's padding has no beats."""
+    w = wf if isinstance(wf, torch.Tensor) and wf.is_cuda else \
+        torch.from_numpy(np.ascontiguousarray(wf, dtype=np.float32).reshape(-1)).cuda()
+    if w.numel() <= p.N // 2:
+        return dict(period=0, tempo=None, beats=[], frames=[])
+    return beat_mod.beat_track([w.to(torch.float32).reshape(-1)], p.sr, n_fft=p.N, hop=p.H, **opts)[0]
+
+
 def _split(wf, p, opts):
     """(harmonic, percussive) of one mono waveform at p.sr through audio.hpss with the model's p.N / p.H."""
     w = wf if isinstance(wf, torch.Tensor) and wf.is_cuda else \
@@ -133,7 +162,7 @@ def _make_loop(p, iters, heads, groups, weights_dir, guess, instrument_model='in
 def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument', 'velocity'),
                groups=(0, 1, 2), weights_dir=None, guess='bank', loop=None, batch=1024, traversal='windows',
                silence=1e-3, sr=None, residual=False, stems=False, instrument_model='instrument', on_finish=None,
-               hpss=None, percussive=False):
+               hpss=None, percussive=False, beats=False):
     """wf: float32 mono waveform at params.sr -- or, with `sr` given, a waveform [n] or [n, channels] at `sr`, resampled
     to params.sr (and downmixed) on the device first (audio.resample): everything below, the length the note times are
     computed from included, then sees the resampled signal.  Returns (notes, events) where notes is the
@@ -156,7 +185,11 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
     hpss=True, or a dict of audio.hpss's kernel / power / margin: the waveform, once resampled, is split by audio.hpss
     at params.N / params.H and the HARMONIC part (hop * (len // hop) samples) is what either traversal sees.
     percussive=True (needs hpss: ValueError) appends the percussive waveform, a 1-d float32 device tensor, to what is
-    returned.  hpss=None: nothing changes."""
+    returned.  hpss=None: nothing changes.
+    beats=True, or a dict of beat.params's keywords: the waveform as given -- once resampled, before any hpss split -- is
+    beat-tracked on the device (beat.beat_track at params.N / params.H) and the song's dict(period, tempo, beats,
+    frames) is appended last to what is returned; events.write_midi(notes, path, beats=that['beats']) writes the tempo
+    map.  Notes and events are those of the run without it."""
     if traversal not in ('windows', 'song'):
         raise ValueError('Requested attribute does not exist')
     split = _hpss_option(hpss, percussive)
@@ -165,14 +198,17 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
     if stems and traversal != 'song':
         raise ValueError("transcribe: stems=True needs traversal='song'")
     p = params or Hyperparams(N=2048)
+    tracked = _beats_option(beats, p)
     if loop is None:
         loop = _make_loop(p, iters, heads, groups, weights_dir, guess, **_model_option(instrument_model))
     if sr is not None:
         wf = audio.resample(wf, sr, p.sr)                              # 1-d float32, on the device; sr == p.sr: a downmix
     perc = ()
+    found = (_track(wf, p, tracked),) if tracked is not None else ()
     if split is not None:
         wf, drums = _split(wf, p, split)
         perc = (drums,) if percussive else ()
+    perc = perc + found
     on_dev = isinstance(wf, torch.Tensor) and wf.is_cuda
     if traversal == 'song':
         wf32 = wf if on_dev else np.ascontiguousarray(wf, dtype=np.float32)      # (run_songs takes either)
@@ -203,7 +239,7 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
 def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', 'instrument', 'velocity'),
                           groups=(0, 1, 2), weights_dir=None, guess='bank', loop=None, slots=8, silence=1e-3, poll=16,
                           pool_frames=None, residual=False, stems=False, instrument_model='instrument', on_finish=None,
-                          hpss=None, percussive=False):
+                          hpss=None, percussive=False, beats=False):
     """The song queue behind transcribe_songs (TranscriptionLoop.iter_song_queue): yields (index, notes, events) as
     each song finishes, in finishing order -- (index, notes, events[, residual waveform][, stems [G, samples]]) with
     residual=True / stems=True.  wfs: a sequence or an iterator of mono float32 waveforms at params.sr; an
@@ -213,11 +249,14 @@ def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', '
     hpss (True or a dict, see transcribe): every song is split by audio.hpss as it is pulled, after resampling, and its
     harmonic part is what the queue walks.  percussive (needs hpss: ValueError): the song's percussive waveform is
     appended to what is yielded; a dict in place of True is also filled with {index: percussive waveform} while the
-    song is in flight, which is where an on_finish hook finds it."""
+    song is in flight, which is where an on_finish hook finds it.
+    beats (True or a dict, see transcribe): every song is beat-tracked as it is pulled, after resampling and before any
+    split -- three device calls and one copy back per song -- and its beat dict is appended last to what is yielded."""
     want = percussive is True or isinstance(percussive, dict)
     split = _hpss_option(hpss, want)
     drums = percussive if isinstance(percussive, dict) else {}
     p = params or Hyperparams(N=2048)
+    tracked, found = _beats_option(beats, p), {}
     if loop is None:
         loop = _make_loop(p, iters, heads, groups, weights_dir, guess, **_model_option(instrument_model))
     lens = {}
@@ -228,6 +267,8 @@ def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', '
                 w = audio.resample(wf[0], wf[1], p.sr)
             else:
                 w = np.ascontiguousarray(wf, dtype=np.float32).reshape(-1)
+            if tracked is not None:
+                found[i] = _track(w, p, tracked)
             if split is not None:
                 w, drum = _split(w, p, split)
                 if want:                                           # (kept on the device only for a caller that asked)
@@ -244,14 +285,14 @@ def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', '
         for note in notes:
             note['song'] = i
         drum = drums.pop(i, None)
-        yield (i, notes, evs) + tuple(item[2:]) + ((drum,) if want else ())
+        yield (i, notes, evs) + tuple(item[2:]) + ((drum,) if want else ()) + ((found.pop(i),) if tracked is not None else ())
 
 
 def transcribe_songs(wfs, params=None, slots=8, **kw):
     """A collection of songs through the song queue: `slots` live windows, a finished slot refilled with the next
     song.  Returns [(notes, events [k, 9]), ...] in input order; a song's notes are those of
     transcribe(wf, traversal='song') for it alone (with `song` = its index).  residual=True / stems=True:
-    (notes, events[, residual][, stems])."""
+    (notes, events[, residual][, stems]); beats=True appends each song's beat dict."""
     out = {item[0]: tuple(item[1:]) for item in iter_transcribe_songs(wfs, params, slots=slots, **kw)}
     return [out[i] for i in range(len(out))]
 
@@ -324,11 +365,36 @@ def _shared_options(ap, sr_help, **stems_dir):
     ap.add_argument('--hpss-margin', default='1,1', metavar='H,P',
                     help='margins of --hpss for the harmonic and the percussive mask, each in 1 .. 100 (default 1,1); '
                          'above 1 a third part belongs to neither and is dropped')
+    ap.add_argument('--tempo-map', action='store_true', help=_TEMPO_MAP_HELP)
+    ap.add_argument('--quantize', type=int, default=None, metavar='DIV', choices=ev.QUANTIZE_DIVISIONS,
+                    help='with --tempo-map: snap every onset to 1/DIV of a beat (480 / DIV ticks), durations kept; one of '
+                         + ', '.join(map(str, ev.QUANTIZE_DIVISIONS)))
     ap.add_argument('--roll-dir', default=None, metavar='DIR', help=_ROLL_HELP)
     ap.add_argument('--roll-width', type=int, default=1200, metavar='W',
                     help='pixel columns of every --roll-dir image, 1 .. 16384 (default 1200)')
     ap.add_argument('--roll-row-px', type=int, default=5, metavar='N',
                     help='pixel rows per pitch of every --roll-dir image, 1 .. 186 (default 5: 440 rows)')
+
+
+_TEMPO_MAP_HELP = ('track the beats of every song on the device (amt_saga.beat: the signal as given, after resampling and '
+                   'before any --hpss split) and write them into the .mid as a tempo map: every beat on a multiple of 480 '
+                   'ticks, time 0 on tick 0, every note where it was in seconds to within half a tick.  A song with fewer '
+                   'than two beats keeps the fixed 120 bpm.  Without it the .mid is what it was')
+
+
+def _beats_cli(a, beats_out):
+    """True when the beats are wanted (--tempo-map, or `beats_out`, the value of --beats-out / --beats-dir); --quantize
+    without --tempo-map is refused, before any file is read."""
+    if a.quantize is not None and not a.tempo_map:
+        raise SystemExit('--quantize needs --tempo-map (there is no beat grid to snap to without it)')
+    return bool(a.tempo_map or beats_out is not None)
+
+
+def write_beats(path, found):
+    """One beat time per line, seconds with microseconds."""
+    with open(path, 'w') as f:
+        f.write(''.join('%.6f\n' % t for t in found['beats']))
+    print('%d beats -> %s' % (len(found['beats']), path))
 
 
 _HPSS_HELP = ('split every song into a harmonic and a percussive part on the device before it is transcribed (median '
@@ -580,16 +646,19 @@ def main_songs(argv):
                     help='when the last song has been written, score every song that has a <stem>.mid in DIR against it, '
                          'all in one device call: <stem>.score.json beside each .mid and scores.json in --out-dir; a song '
                          'without a gold file is named on stderr and left out')
+    ap.add_argument('--beats-dir', default=None, metavar='DIR',
+                    help='write <stem>.beats.txt per song as it finishes: its beat times in seconds, one per line')
     a = ap.parse_args(argv)
     _check_writer(a)
     split = _hpss_cli(a, a.percussive_dir)
+    want_beats = _beats_cli(a, a.beats_dir)
     size = _spectrogram_size(a)
     roll_size = _roll_size(a)
     if a.gold_dir is not None and not os.path.isdir(a.gold_dir):
         raise SystemExit('--gold-dir: %s is not a directory' % a.gold_dir)
     os.makedirs(a.out_dir, exist_ok=True)
     keep, keep_stems = a.residual_dir is not None, a.stems_dir is not None
-    for d in (a.residual_dir, a.stems_dir, a.spectrogram_dir, a.roll_dir, a.percussive_dir):
+    for d in (a.residual_dir, a.stems_dir, a.spectrogram_dir, a.roll_dir, a.percussive_dir, a.beats_dir):
         if d is not None:
             os.makedirs(d, exist_ok=True)
     stems = [os.path.splitext(os.path.basename(f))[0] for f in a.songs]
@@ -619,18 +688,28 @@ def main_songs(argv):
     def on_finish(i, slot, st):
         write_song_spectrograms(st, slot, a.spectrogram_dir, stems[i], size, percussive=drums.get(i))
     split_options = {} if split is None else dict(hpss=split, percussive=drums)
+    if want_beats:
+        split_options['beats'] = True
     queue = iter_transcribe_songs(wfs, Hyperparams(N=2048, sr=rate), iters=a.iters, weights_dir=a.weights, guess=a.guess,
                                   slots=a.slots, residual=keep or draw, stems=keep_stems or draw, groups=CLI_GROUPS,
                                   instrument_model=a.instrument_model, on_finish=on_finish if draw else None,
                                   **split_options)
     for item in queue:
         i, notes = item[0], item[1]
+        found = item[-1] if want_beats else None
+        if want_beats:
+            item = item[:-1]
         drum = item[-1] if split is not None else None
         if split is not None:
             item = item[:-1]
         out = os.path.join(a.out_dir, stems[i] + '.mid')
-        ev.write_midi(notes, out)
+        if a.tempo_map:
+            ev.write_midi(notes, out, beats=found['beats'], quantize=a.quantize)
+        else:
+            ev.write_midi(notes, out)
         print('%d notes -> %s' % (len(notes), out))
+        if a.beats_dir is not None:
+            write_beats(os.path.join(a.beats_dir, stems[i] + '.beats.txt'), found)
         write_song_audio(rate, residual=item[3] if keep else None,
                          residual_path=os.path.join(a.residual_dir, stems[i] + '.residual.' + a.format) if keep else None,
                          stems=item[-1] if keep_stems else None, stems_dir=a.stems_dir, name=stems[i], flac=a.flac,
@@ -674,9 +753,12 @@ def main(argv=None):
     ap.add_argument('--percussive', default=None, metavar='OUT.flac',
                     help='with --hpss: write the percussive part of the split, through the writer --format, --flac and '
                          '--flac-predictor choose')
+    ap.add_argument('--beats-out', default=None, metavar='FILE',
+                    help='write the beat times of the song in seconds, one per line')
     a = ap.parse_args(argv)
     _check_writer(a)
     split = _hpss_cli(a, a.percussive)
+    want_beats = _beats_cli(a, a.beats_out)
     if a.gold is not None and not os.path.isfile(a.gold):
         raise SystemExit('--gold: %s: no such file' % a.gold)
     if a.residual is not None and a.traversal != 'song':
@@ -703,7 +785,11 @@ def main(argv=None):
             raise SystemExit('--spectrogram-dir: the walk stopped before the end of the song')
         os.makedirs(a.spectrogram_dir, exist_ok=True)
         write_song_spectrograms(st, slot, a.spectrogram_dir, name, size, percussive=drums.get(0))
-    drums = {}
+    drums, found = {}, None
+    if want_beats and split is not None:         # the signal as given, at the model's rate, ahead of the split below
+        if file_sr is not None:
+            wf, file_sr = audio.resample(wf, file_sr, model_sr), None
+        found = _track(wf, Hyperparams(N=2048, sr=model_sr), {})
     if split is not None:
         # the split here, at the model's rate, so that the walk's hook can draw the percussive part; transcribe() then
         # sees the harmonic waveform at its own rate and splits nothing
@@ -713,10 +799,17 @@ def main(argv=None):
     got = transcribe(wf, Hyperparams(N=2048, sr=model_sr), iters=a.iters, weights_dir=a.weights, guess=a.guess,
                      traversal=a.traversal, sr=file_sr, residual=a.residual is not None or draw,
                      stems=a.stems_dir is not None or draw, groups=CLI_GROUPS, instrument_model=a.instrument_model,
-                     on_finish=on_finish if draw else None)
+                     on_finish=on_finish if draw else None, **(dict(beats=True) if want_beats and found is None else {}))
+    if want_beats and found is None:
+        got, found = got[:-1], got[-1]
     notes = got[0]
-    ev.write_midi(notes, a.outfile)
+    if a.tempo_map:
+        ev.write_midi(notes, a.outfile, beats=found['beats'], quantize=a.quantize)
+    else:
+        ev.write_midi(notes, a.outfile)
     print('%d notes -> %s' % (len(notes), a.outfile))
+    if a.beats_out is not None:
+        write_beats(a.beats_out, found)
     if a.residual is not None and got[2] is None:
         raise SystemExit('--residual: the walk stopped before the end of the song')
     if a.stems_dir is not None:

@@ -18,7 +18,7 @@ LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libamt_saga_hip.so')
 SOURCES = ['amt_stft.hip', 'amt_subtract.hip', 'amt_features.hip', 'amt_cqt.hip',
            'amt_rdcnn.hip', 'amt_loop.hip', 'amt_song.hip', 'amt_synth.hip', 'amt_train.hip', 'amt_probe.hip', 'amt_fftconv.hip', 'amt_fftpk.hip', 'amt_resample.hip',
-           'amt_flac.hip', 'amt_flacdec.hip', 'amt_pcm.hip', 'amt_png.hip', 'amt_score.hip', 'amt_roll.hip', 'amt_hpss.hip']
+           'amt_flac.hip', 'amt_flacdec.hip', 'amt_pcm.hip', 'amt_png.hip', 'amt_score.hip', 'amt_roll.hip', 'amt_hpss.hip', 'amt_beat.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-fast-math',
          '-ffp-contract=off', '-Wall', '-Wno-unused-function',
@@ -38,7 +38,7 @@ FILE_FLAGS = {'amt_stft.hip': ['-ffp-contract=fast'], 'amt_cqt.hip': ['-ffp-cont
               'amt_fftconv.hip': NO_PK, 'amt_fftpk.hip': NO_PK, 'amt_rdcnn.hip': NO_PK,
               'amt_resample.hip': NO_PK, 'amt_flac.hip': NO_PK, 'amt_flacdec.hip': NO_PK,
               'amt_pcm.hip': NO_PK, 'amt_png.hip': NO_PK, 'amt_score.hip': NO_PK,
-              'amt_roll.hip': NO_PK, 'amt_hpss.hip': NO_PK}
+              'amt_roll.hip': NO_PK, 'amt_hpss.hip': NO_PK, 'amt_beat.hip': NO_PK}
 
 
 def _newer(a, b):

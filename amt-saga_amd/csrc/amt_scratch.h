@@ -51,4 +51,27 @@ inline long long amt_flac_make_layout(void *scratch, long long n, long long fram
     return c.failed ? -1 : c.at;
 }
 
+// The beat tracker's scratch (amt_beat.hip), one layout for its two calls: amt_beat_envelope uses flux and prefix,
+// amt_beat_track the other three.  acorr_len = 2 lag_hi + 2 lags per song (beat_acorr_len of amt_beat_core.h).
+struct amt_beat_layout {
+    long long *prefix;                                     // [pool_frames]: inclusive prefix sums of a song's flux
+    long long *acorr;                                      // [n][acorr_len]
+    int *flux;                                             // [pool_frames] (used when the caller keeps no flux)
+    int *back;                                             // [pool_frames] (used when the caller keeps no back)
+    int *found;                                            // [beats_total]: the backtrace, before the trim
+};
+inline long long amt_beat_make_layout(void *scratch, long long n, long long pool_frames, long long acorr_len,
+                                      long long beats_total, amt_beat_layout *L) {
+    long long lags;
+    if (n < 0 || pool_frames < 0 || acorr_len < 0 || beats_total < 0 || __builtin_mul_overflow(n, acorr_len, &lags))
+        return -1;
+    amt_carver c(scratch);
+    L->prefix = c.take<long long>(pool_frames, 16);
+    L->acorr = c.take<long long>(lags, 16);
+    L->flux = c.take<int>(pool_frames, 16);
+    L->back = c.take<int>(pool_frames, 16);
+    L->found = c.take<int>(beats_total, 16);
+    return c.failed ? -1 : c.at;
+}
+
 #endif

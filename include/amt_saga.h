@@ -444,6 +444,73 @@ typedef struct amt_hpss_args {
 int amt_hpss_ragged(const amt_hpss_args *args, void *stream);
 
 /* ------------------------------------------------------------------------ *
+ * Beat tracking by dynamic programming (Ellis 2007), behind the transcription: the reference stops at fixed-tempo
+ * note_sequence files (add_note / save, util_audio.py:594-639, :790-792), so its MIDI has no bar a beat falls on.  The
+ * rule lives in csrc/amt_beat_core.h: c = (int)(sqrtf(min(mag / ref, 1)) 1024 + 0.5f) in float32, integers from there on
+ * -- flux, its excess over a local mean of half-width w, e in 1/256 of the excess's rms (uint16), the tempo from the
+ * autocorrelation of e under a host-built prior, C[t] = ls[t] + max(0, max_tau (C[t - tau] - pen[P - lag_lo][tau])),
+ * the backtrace and the trim.  Every tie rule is written out there.  DESIGN.md 31.
+ *
+ * Limits: F <= 2049, max_frames < 2^20, 1 <= lag_lo <= lag_hi <= 1024, w >= 0, n <= 2^24.
+ * ------------------------------------------------------------------------ */
+typedef struct amt_beat_env_args {
+    const float   *mag;                       /* device [pool_frames][ldf]: the pool the songs lie in */
+    const float   *ref;                       /* device [n]: each song's maximum magnitude; <= 0 or NaN: a song without beats */
+    const int64_t *frame_base;                /* device [n]: song i is frames [frame_base[i], + t_frames[i]) */
+    const int32_t *t_frames;                  /* device [n] */
+    uint16_t      *env;                       /* device [pool_frames]: e, one value per frame */
+    int32_t       *flux;                      /* device [pool_frames], or NULL: the flux before the local mean */
+    void          *scratch;                   /* device, 16-byte aligned */
+    int64_t        scratch_bytes;             /* >= amt_beat_scratch_bytes(n, pool_frames, 0, 0) */
+    int64_t        n;
+    int64_t        pool_frames;
+    int32_t        max_frames;                /* HOST value: the longest t_frames; a longer song is left unwritten */
+    int32_t        ldf, F;                    /* row pitch in floats and live bins */
+    int32_t        w;                         /* half-width of the local mean, frames */
+} amt_beat_env_args;
+typedef struct amt_beat_track_args {
+    const uint16_t *env;                      /* device [pool_frames] */
+    const int64_t *frame_base;                /* device [n] */
+    const int32_t *t_frames;                  /* device [n] */
+    const int32_t *prior;                     /* device [lag_hi - lag_lo + 1], values <= 32767 */
+    const int32_t *pen;                       /* device [lag_hi - lag_lo + 1][2 lag_hi + 1]: row P - lag_lo, entry tau */
+    const int64_t *beat_base;                 /* device [n]: song i owns beats[beat_base[i], + t_frames[i] / ceil(lag_lo / 2) + 1) */
+    int32_t       *period, *count;            /* device [n] */
+    int32_t       *beats;                     /* device [beats_total]: count[i] ascending frames from beat_base[i] on */
+    int64_t       *C;                         /* device [pool_frames], or NULL: the DP's scores */
+    int32_t       *back;                      /* device [pool_frames], or NULL: the DP's predecessors */
+    void          *scratch;                   /* device, 16-byte aligned */
+    int64_t        scratch_bytes;             /* >= amt_beat_scratch_bytes(n, pool_frames, lag_hi, beats_total) */
+    int64_t        n;
+    int64_t        pool_frames;
+    int64_t        beats_total;
+    int32_t        max_frames;                /* HOST value: the longest t_frames */
+    int32_t        lag_lo, lag_hi;
+} amt_beat_track_args;
+/* Scratch bytes of the two calls below, as amt_beat_make_layout (csrc/amt_scratch.h) lays it out (amt_beat_envelope
+ * needs the bytes of lag_hi = 0, beats_total = 0; the larger size serves both); negative (AMT_E_INVALID) for a negative
+ * count, lag_hi > 1024 or n > 2^24. */
+long long amt_beat_scratch_bytes(long long n, long long pool_frames, int lag_hi, long long beats_total);
+/* The onset envelopes of any number of spectrograms, the input of a beat track the reference's fixed-tempo files
+ * (util_audio.py:594-639) lack: two launches enqueued on `stream`, nothing is waited for.  The tables are
+ * amt_hpss_ragged's.  Each magnitude is read once (and one frame per run of 16 twice); pad columns F..ldf-1 are never
+ * read; frames of no song are not written.  Integer reductions only: a song's result is bit-identical to the same song
+ * alone.  The kernels read the device tables and hold every range inside the pool whatever they say: a song whose frames
+ * would leave the pool, or with t_frames outside 0..max_frames, is left unwritten.  n = 0 and max_frames = 0 are AMT_OK
+ * with nothing launched.  All checks come before any HIP call.  AMT_E_INVALID: a NULL pointer (flux excepted), a scratch
+ * that is not 16-byte aligned, a limit above exceeded, F < 1, F > ldf, a negative count.  AMT_E_SHAPE: scratch_bytes
+ * too small. */
+int amt_beat_envelope(const amt_beat_env_args *args, void *stream);
+/* Period, beat count and beat frames of every song from its envelope, for the tempo map the reference's note_sequence
+ * files (util_audio.py:594-639) do not have: two launches enqueued on `stream` (the autocorrelations; then tempo, DP,
+ * backtrace and trim, one workgroup per song), nothing is waited for and the period never leaves the device.  A song
+ * without beats (amt_beat_core.h) gets period 0 and count 0.  A song whose frames would leave the pool, with t_frames
+ * outside 0..max_frames or whose beats would leave `beats` gets period 0, count 0 and nothing else.  n = 0 is AMT_OK
+ * with nothing launched.  All checks come before any HIP call.  AMT_E_INVALID: a NULL pointer (C and back excepted), a
+ * scratch that is not 16-byte aligned, a limit above exceeded, a negative count.  AMT_E_SHAPE: scratch_bytes too small. */
+int amt_beat_track(const amt_beat_track_args *args, void *stream);
+
+/* ------------------------------------------------------------------------ *
  * Spectral subtraction (replaces audio_complete.subtract, util_audio.py:221-259)
  * ------------------------------------------------------------------------ */
 typedef struct amt_subtract_args {
