@@ -325,6 +325,51 @@ class res_net:
         fn.restype, fn.argtypes = C.c_int, [C.c_void_p]
         return int(fn(self._net))
 
+    # ConvImpl of amt_rdcnn.hip, in its order; the ints of amt_rdcnn_layer_plan
+    PLAN_IMPLS = ('first_mfma', 'first_valu', 'fft_row', 'fft_packed', 'f16x3', 'bf16x6', 'f32')
+    PLAN_KEYS = ('impl', 'kh', 'kw', 'cin', 'cout', 'H', 'W', 'cw', 'TH', 'TW', 'NWIN', 'masked', 'wm_ms', 'nslice', 'MT')
+
+    def layer_plans(self, mode=None):
+        """[[plan per conv layer] per tower]: what the forward runs for each layer in ``mode`` (default: the net's
+        current one) -- implementation, kernel size, channels, image, slice width, tile, masked / window-major form,
+        slices, M-tiles (amt_rdcnn_layer_plan).  Host only.  A diagnostic export of the library, bound here and not in
+        _lib.PROTOTYPES."""
+        self._ensure()
+        fn = self._lib.amt_rdcnn_layer_plan
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        mode = self.mode if mode is None else int(mode)
+        out = []
+        for t in range(len(self.cfg['input_shapes'])):
+            plans = []
+            for i in range(self.cfg['convolutional_layer_count']):
+                v = np.zeros(len(self.PLAN_KEYS), np.int32)
+                _lib.check(fn(self._net, t, i, mode, v.ctypes.data_as(C.c_void_p)))
+                p = dict(zip(self.PLAN_KEYS, map(int, v)), tower=t, layer=i + 1, mode=mode)
+                p['impl'] = self.PLAN_IMPLS[p['impl']]
+                plans.append(p)
+            out.append(plans)
+        return out
+
+    def layer_outputs(self, xs):
+        """predict_device with every conv layer tapped: (y, logits, [[block output per conv layer] per tower]), the block
+        outputs as device tensors [B, H, W, cout] taken before any max pool (amt_rdcnn_layer_tap).  Mode 3 cannot
+        tap a chained FFT-domain layer (the forward answers AMT_E_UNSUPPORTED).  A diagnostic export, bound here."""
+        self._ensure()
+        fn = self._lib.amt_rdcnn_layer_tap
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        B = xs[0].shape[0]
+        acts = [[empty((B, p['H'], p['W'], p['cout'])) for p in plans] for plans in self.layer_plans()]
+        try:
+            for t, row in enumerate(acts):
+                for i, a in enumerate(row):
+                    _lib.check(fn(self._net, t, i, ptr(a)))
+            y, lg = self.predict_device(xs, return_logits=True)
+        finally:
+            for t, row in enumerate(acts):
+                for i in range(len(row)):
+                    fn(self._net, t, i, None)
+        return y, lg, acts
+
     def set_mode(self, mode):
         """0 = f32 MFMA convolutions, 1 = split-bf16 (6 bf16 MFMAs per product block), 2 = split-fp16 (3 f16 MFMAs per
         product block), 3 = split-fp16 + the FFT-domain form of the 32 -> 32 (4 x 16) layers on images of at most 20 x 561

@@ -76,6 +76,8 @@ struct amt_rdcnn {
     mutable std::vector<ProfPending> prof_pending;
     mutable std::vector<hipEvent_t> prof_free;
     mutable std::vector<std::vector<ProfAcc>> prof_acc;   // [tower][layer]
+    // optional layer taps (amt_rdcnn_layer_tap): [tower][layer] device pointers, empty until the first one is set
+    mutable std::vector<std::vector<float *>> taps;
     amt_rdcnn_desc d;
     std::vector<Tower> towers;
     std::vector<void *> allocs;
@@ -496,6 +498,14 @@ static int build_conv_variants(amt_rdcnn *n, ConvOp &c, const float *kern) {
     return AMT_OK;
 }
 
+// layer tap (amt_rdcnn_layer_tap): n floats per window from src (window stride `stride`) into the dense dst
+__global__ __launch_bounds__(256) void tap_copy_kernel(const float *__restrict__ src, size_t stride, float *__restrict__ dst,
+                                                       size_t n) {
+    const float *s = src + (size_t)blockIdx.y * stride;
+    float *o = dst + (size_t)blockIdx.y * n;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) o[i] = s[i];
+}
+
 extern "C" {
 
 size_t amt_rdcnn_param_count(const amt_rdcnn_desc *desc) {
@@ -648,6 +658,60 @@ int amt_rdcnn_profile_read(amt_rdcnn *net, int32_t *desc, double *ms, double *wi
     *n_rows = r;
     if (reset)
         for (auto &v : net->prof_acc) for (auto &a : v) a = ProfAcc();
+    return AMT_OK;
+}
+
+// Diagnostic exports (not in include/amt_saga.h; tests/test_gpu_rdcnn_layers.py), bound in rdcnn.py like
+// amt_rdcnn_fc_pooled_layers.
+//
+// The layer tap.  dst: device memory for the block output of conv layer `layer` (0-based) of `tower` -- after BN +
+// sigmoid, after the shortcut add and its BN where a shortcut closes, before any max pool -- dense [B][H][W][cout]
+// for the B of the forwards that follow; NULL takes the tap away.  While a tap is set amt_rdcnn_forward copies the
+// layer's output there on its stream, right behind the layer's launches.  A mode-3 layer whose spatial output the
+// FFT-domain chain does not write (the next layer reads it transformed, or it leaves only its W-pooled pair) cannot be
+// tapped: the forward answers AMT_E_UNSUPPORTED before it launches that layer and computes what it always computes
+// otherwise.  Without taps the forward launches exactly what it launches without this export.
+int amt_rdcnn_layer_tap(amt_rdcnn *net, int tower, int layer, float *dst) {
+    if (!net || tower < 0 || tower >= (int)net->towers.size()) return AMT_E_INVALID;
+    if (layer < 0 || layer >= (int)net->towers[tower].convs.size()) return AMT_E_INVALID;
+    if (net->taps.empty()) {
+        if (!dst) return AMT_OK;
+        net->taps.resize(net->towers.size());
+        for (size_t t = 0; t < net->towers.size(); ++t) net->taps[t].assign(net->towers[t].convs.size(), nullptr);
+    }
+    net->taps[tower][layer] = dst;
+    return AMT_OK;
+}
+
+// The plan report: what amt_rdcnn_forward runs for conv layer `layer` (0-based) of `tower` in `mode`, as
+// AMT_RDCNN_PLAN_INTS ints: ConvImpl, kh, kw, cin, cout, H, W, slice width, TH, TW, NWIN, masked, wm_ms, nslice, MT.
+// Slice width, tile and slices are the running variant's (the window-major form: whole images of HXW_WIN windows; the
+// matrix-pipe first layer: its TH x TW tile; zero where the implementation has none).  MT is the f32 MFMA kernel's
+// M-tiles per wave, 0 for every other implementation.  Host only, reads the net and changes nothing.  (Mode 3 reports
+// an FFT-domain form only once amt_rdcnn_set_mode(net, 3) has built it.)
+#define AMT_RDCNN_PLAN_INTS 15
+int amt_rdcnn_layer_plan(const amt_rdcnn *net, int tower, int layer, int mode, int32_t *out) {
+    if (!net || !out || mode < 0 || mode > 3 || tower < 0 || tower >= (int)net->towers.size()) return AMT_E_INVALID;
+    if (layer < 0 || layer >= (int)net->towers[tower].convs.size()) return AMT_E_INVALID;
+    const ConvOp &c = net->towers[tower].convs[layer];
+    const ConvImpl impl = conv_impl(c, mode);
+    int cw = 0, TH = 0, TW = 0, NWIN = 0, masked = 0, wm_ms = 0, nslice = 0, MT = 0;
+    auto from_plan = [&](const ConvPlan &p) {
+        cw = p.cw; TH = p.TH; TW = p.TW; NWIN = p.NWIN; masked = p.masked ? 1 : 0; nslice = p.nslice;
+    };
+    switch (impl) {
+    case IMPL_FIRST_MFMA: cw = c.cout; nslice = 1; NWIN = 1; choose_tile1(c.H, c.W, &TH, &TW); break;
+    case IMPL_F16X3:
+        from_plan(c.f16);
+        wm_ms = c.f16.wm_ms;
+        if (wm_ms > 0) { TH = c.H; TW = c.W; NWIN = HXW_WIN; }
+        break;
+    case IMPL_BF16X6: from_plan(c.bf16); break;
+    case IMPL_F32: from_plan(c.f32); MT = c.MT; break;
+    default: break;
+    }
+    const int32_t v[AMT_RDCNN_PLAN_INTS] = {(int32_t)impl, c.kh, c.kw, c.cin, c.cout, c.H, c.W, cw, TH, TW, NWIN, masked, wm_ms, nslice, MT};
+    std::copy(v, v + AMT_RDCNN_PLAN_INTS, out);
     return AMT_OK;
 }
 
@@ -826,6 +890,10 @@ int amt_rdcnn_forward(const amt_rdcnn *net, const float *const *x, int B, float 
                 // the pooled pair shares the layer's output buffer: [Bc] wavg, then [Bc] wmax (a quarter of it together)
                 const bool wpooled = fc_wpooled_ok(net, tw, i, impl, H, W);
                 const size_t wp_stride = (size_t)H * (W / 8) * c.cout;
+                // an FFT-domain layer hands its output on transformed where the next layer is one of its kind
+                const bool next_fc = impl_is_fft(impl) && i + 1 < L && !c.pool_after && conv_impl(tw.convs[i + 1], mode) == impl;
+                float *const tap = net->taps.empty() ? nullptr : net->taps[t][i];
+                if (tap && impl_is_fft(impl) && (wpooled || (next_fc && !c.residual))) return AMT_E_UNSUPPORTED;      // no spatial output (run_fc)
                 ProfPending prof{nullptr, nullptr, t, i, Bc};
                 RD_TRY(prof_begin(net, prof, st));
                 switch (impl) {
@@ -843,7 +911,6 @@ int amt_rdcnn_forward(const amt_rdcnn *net, const float *const *x, int B, float 
                     ep.s1 = c.s1; ep.t1 = c.t1; ep.s2 = s2; ep.t2 = t2;
                     if (rank1) { ep.sc1 = p0; ep.sc1_stride = p0_stride; ep.sc1_w = rank1->w; ep.sc1_s = rank1->s; ep.sc1_t = rank1->t; }
                     else { ep.sc = sc; ep.sc_stride = sc_stride; }
-                    const bool next_fc = i + 1 < L && !c.pool_after && conv_impl(tw.convs[i + 1], mode) == impl;
                     if (wpooled) { ep.wavg = o; ep.wmax = o + (size_t)Bc * wp_stride; ep.wp_stride = wp_stride; }
                     RD_TRY(run_fc(c, cur, cur_stride, xf_valid, Bc, ep, fcb, o, o_stride, next_fc, amax_o, st));
                     xf_valid = next_fc;
@@ -865,6 +932,12 @@ int amt_rdcnn_forward(const amt_rdcnn *net, const float *const *x, int B, float 
                     // kernel is not built for; none of the reference's head topologies)
                     RD_TRY(launch_absmax(o, (size_t)H * W * c.cout, o_stride, Bc, amax_o, st));
                 RD_TRY(prof_end(net, prof, st));
+                if (tap) {
+                    const size_t n = (size_t)H * W * c.cout;      // o_stride is the flat row where this is the last layer
+                    tap_copy_kernel<<<dim3((unsigned)std::min<size_t>((n + 255) / 256, 64), Bc), 256, 0, st>>>(
+                        o, o_stride, tap + (size_t)b0 * n, n);
+                    AMT_LAUNCH_CHECK();
+                }
                 if (c.residual) { p0 = o; p0_stride = wpooled ? wp_stride : o_stride; p0_wpooled = wpooled; }
                 cur = o; cur_stride = o_stride;
                 if (wpooled) { cur = o + (size_t)Bc * wp_stride; cur_stride = wp_stride; }
