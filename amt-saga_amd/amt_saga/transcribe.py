@@ -131,21 +131,57 @@ def _beats_option(beats, p):
     return dict(opts)
 
 
-def _track(wf, p, opts):
-    """beat.beat_track's dict(period, tempo, beats, frames) of one mono waveform at p.sr, at the model's p.N / p.H; a
-    signal too short for the STFT's padding has no beats."""
-    w = wf if isinstance(wf, torch.Tensor) and wf.is_cuda else \
-        torch.from_numpy(np.ascontiguousarray(wf, dtype=np.float32).reshape(-1)).cuda()
-    if w.numel() <= p.N // 2:
-        return dict(period=0, tempo=None, beats=[], frames=[])
-    return beat_mod.beat_track([w.to(torch.float32).reshape(-1)], p.sr, n_fft=p.N, hop=p.H, **opts)[0]
+class Song:
+    """What one transcribed song carries from waveform to files -- THE list of outputs; every docstring below means these.
+    index: the song's place in the queue (0 for transcribe()).  samples: its length at the model's rate, as walked.
+    notes: list of dicts (pitch, program, velocity, start, end; from a song walk also `song`, the index).  events: the raw
+    int32 records.
+    residual: what the walk left, a 1-d float32 device tensor of hop * (frames - 1) samples.  stems: what it took out,
+    [len(groups), hop * (frames - 1)], row g of groups[g].  percussive: the percussive waveform of an hpss split, 1-d
+    float32 on the device.  beats: beat.beat_track's dict(period, tempo, beats, frames).
+    A field nobody asked for is None; so are residual and stems of a song whose walk stopped before its end."""
+    __slots__ = ('index', 'samples', 'notes', 'events', 'residual', 'stems', 'percussive', 'beats')
+
+    def __init__(self, index, samples, notes=None, events=None, residual=None, stems=None, percussive=None, beats=None):
+        self.index, self.samples, self.notes, self.events = index, samples, notes, events
+        self.residual, self.stems, self.percussive, self.beats = residual, stems, percussive, beats
 
 
-def _split(wf, p, opts):
-    """(harmonic, percussive) of one mono waveform at p.sr through audio.hpss with the model's p.N / p.H."""
-    w = wf if isinstance(wf, torch.Tensor) and wf.is_cuda else \
-        torch.from_numpy(np.ascontiguousarray(wf, dtype=np.float32).reshape(-1)).cuda()
-    return audio.hpss([w.to(torch.float32).reshape(-1)], n_fft=p.N, hop=p.H, **opts)[0][:2]
+def _result(song, residual, stems, percussive, beats, indexed=False):
+    """A Song as the tuple the public functions document: (notes, events[, residual][, stems][, percussive][, beats]),
+    an optional item present when its want is true; indexed=True puts the song's index in front (the queue's form).
+    The only place that builds or orders that tuple."""
+    fields = ((indexed, song.index), (True, song.notes), (True, song.events), (residual, song.residual),
+              (stems, song.stems), (percussive, song.percussive), (beats, song.beats))
+    return tuple(value for want, value in fields if want)
+
+
+def _on_device(wf):
+    return isinstance(wf, torch.Tensor) and wf.is_cuda
+
+
+def _device_mono(wf):
+    """One mono waveform, array or tensor, as the 1-d float32 device tensor beat.beat_track and audio.hpss take."""
+    w = wf if _on_device(wf) else torch.from_numpy(np.ascontiguousarray(wf, dtype=np.float32).reshape(-1)).cuda()
+    return w.to(torch.float32).reshape(-1)
+
+
+def _prepare(wf, sr, p, tracked, split):
+    """What happens to a song's waveform ahead of either traversal, in this order: resampled from `sr` to p.sr on the
+    device (sr given: audio.resample, a downmix at equal rates); beat-tracked on the signal as given (tracked: the
+    keywords of beat.beat_track at the model's p.N / p.H -- a signal too short for the STFT's padding has no beats);
+    split by audio.hpss at p.N / p.H, the harmonic part going on (split: its keywords).
+    -> (waveform at p.sr, percussive waveform or None, beat dict or None)."""
+    if sr is not None:
+        wf = audio.resample(wf, sr, p.sr)                              # 1-d float32, on the device
+    found = drums = None
+    if tracked is not None:
+        w = _device_mono(wf)
+        found = dict(period=0, tempo=None, beats=[], frames=[]) if w.numel() <= p.N // 2 else \
+            beat_mod.beat_track([w], p.sr, n_fft=p.N, hop=p.H, **tracked)[0]
+    if split is not None:
+        wf, drums = audio.hpss([_device_mono(wf)], n_fft=p.N, hop=p.H, **split)[0][:2]
+    return wf, drums, found
 
 
 def _make_loop(p, iters, heads, groups, weights_dir, guess, instrument_model='instrument'):
@@ -159,6 +195,84 @@ def _make_loop(p, iters, heads, groups, weights_dir, guess, instrument_model='in
     return loop.setup_device()
 
 
+def _song_records(pairs, p, loop, slots=None, iters=5, silence=1e-3, poll=16, pool_frames=None, residual=False,
+                  stems=False, on_finish=None, split=None, tracked=None, percussive=False, in_flight=None):
+    """The Songs of `pairs` -- (waveform, its rate or None for p.sr) each, pulled lazily and through _prepare -- by the
+    song walk, as they finish.  slots=None: the first song alone through run_songs (events [steps, 1, 9]); else all of
+    them through iter_song_queue's `slots` windows (events [k, 9], notes with `song`).  on_finish(song, slot, state):
+    the walk's hook with the Song of the song in flight in place of its index -- song.percussive is there for it.
+    percussive: keep the percussive parts; in_flight: a caller's dict that holds {index: percussive waveform} meanwhile."""
+    flight = {}
+
+    def feed():
+        for i, (wf, sr) in enumerate(pairs):
+            w, drums, found = _prepare(wf, sr, p, tracked, split)
+            if not _on_device(w):
+                w = np.ascontiguousarray(w, dtype=np.float32)
+            flight[i] = Song(i, len(w), percussive=drums if percussive else None, beats=found)   # (kept only if asked)
+            if in_flight is not None:
+                in_flight[i] = drums
+            yield w
+    hook = None if on_finish is None else lambda i, slot, st: on_finish(flight[i], slot, st)
+
+    def alone():
+        events, st = loop.run_songs([next(feed())], max_notes=iters, silence=silence, residual=residual, stems=stems)
+        evs = events.cpu().numpy()
+        if hook is not None:
+            hook(0, 0, st)
+        yield 0, evs, dict(residual=st.residual[0] if residual else None, stems=st.stem_audio[0] if stems else None)
+
+    def queued():
+        kinds = [k for k, want in (('residual', residual), ('stems', stems)) if want]     # iter_song_queue's own order
+        for i, evs, *kept in loop.iter_song_queue(feed(), slots, max_notes=iters, silence=silence, poll=poll,
+                                                  pool_frames=pool_frames, on_finish=hook, residual=residual,
+                                                  stems=stems):
+            yield i, evs, dict(zip(kinds, kept))
+    for i, evs, kept in (alone() if slots is None else queued()):
+        song = flight.pop(i)
+        if in_flight is not None:
+            in_flight.pop(i, None)
+        one = evs
+        if slots is not None:
+            one = evs.copy()
+            one[:, 0] = 0                                              # song_events_to_notes indexes scalars by song 0
+        song.notes = ev.song_events_to_notes(one, 1 + song.samples // p.H, song.samples, sr=p.sr)
+        if slots is not None:
+            for note in song.notes:
+                note['song'] = i
+        song.events, song.residual, song.stems = evs, kept.get('residual'), kept.get('stems')
+        yield song
+
+
+def _record(wf, sr, p, loop, traversal, batch=1024, split=None, tracked=None, percussive=False, **walk):
+    """The Song of one waveform by either traversal: 'song' is the one-song case of _song_records (`walk`: its iters,
+    silence, residual, stems, on_finish); 'windows' cuts independent 50 %-overlapped windows, merges duplicates, keeps
+    nothing and calls nothing back, so `walk` is not looked at."""
+    if traversal == 'song':
+        return next(_song_records([(wf, sr)], p, loop, split=split, tracked=tracked, percussive=percussive, **walk))
+    wf, drums, found = _prepare(wf, sr, p, tracked, split)
+    on_dev = _on_device(wf)
+    L = p.H * (p.timing_frames - 1)
+    wf_dev = wf if on_dev else torch.from_numpy(np.ascontiguousarray(wf, dtype=np.float32)).cuda()
+    wins, starts = cut_windows(wf.cpu().numpy() if on_dev else np.asarray(wf, dtype=np.float32), L, L // 2)
+    # song-level normalisers, as training.py:269-282 computes them: once per song, the maxima of the WHOLE song's
+    # STFT and CQTs (one pass of the block-sum kernel over the song as a single signal), shared by every window
+    song_refs = loop.song_levels(wf_dev)
+    # the loop proper: host batches streamed through run_stream (copy of batch i+1 under the compute of batch i)
+    chunks = [wins[b0:b0 + batch] for b0 in range(0, len(wins), batch)]
+
+    def refs_for(i):
+        return {k: v.expand(len(chunks[i])).contiguous() for k, v in song_refs.items()}
+    evs = np.concatenate([e.cpu().numpy() for e, _ in loop.run_stream(chunks, refs=refs_for)], axis=1)
+    notes = ev.events_to_notes(evs, p.timing_frames, L, sr=p.sr, window_start_s=[s / p.sr for s in starts])
+    return Song(0, len(wf), ev.merge_overlap_duplicates(notes), evs, percussive=drums if percussive else None, beats=found)
+
+
+def _by_index(on_finish):
+    """The public on_finish(index, slot, state) as _song_records' hook, which is handed the Song."""
+    return None if on_finish is None else lambda song, slot, st: on_finish(song.index, slot, st)
+
+
 def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument', 'velocity'),
                groups=(0, 1, 2), weights_dir=None, guess='bank', loop=None, batch=1024, traversal='windows',
                silence=1e-3, sr=None, residual=False, stems=False, instrument_model='instrument', on_finish=None,
@@ -167,7 +281,7 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
     to params.sr (and downmixed) on the device first (audio.resample): everything below, the length the note times are
     computed from included, then sees the resampled signal.  Returns (notes, events) where notes is the
     merged list of dicts (pitch, program, velocity, start, end) and events the raw int32
-    [iters, n_windows, 7] records.
+    [iters, n_windows, 7] records -- the fields of a Song, put in order by _result.
     traversal='windows' (default): independent 50 %-overlapped windows, `iters` notes each, duplicates merged.
     traversal='song': the reference's own walk (training.py:296-328, TranscriptionLoop.run_songs) -- one window that
     lives on the song's spectrogram and slides by half, at most `iters` notes per position (max_notes), windows below
@@ -201,39 +315,9 @@ def transcribe(wf, params=None, iters=5, heads=('timing', 'pitch', 'instrument',
     tracked = _beats_option(beats, p)
     if loop is None:
         loop = _make_loop(p, iters, heads, groups, weights_dir, guess, **_model_option(instrument_model))
-    if sr is not None:
-        wf = audio.resample(wf, sr, p.sr)                              # 1-d float32, on the device; sr == p.sr: a downmix
-    perc = ()
-    found = (_track(wf, p, tracked),) if tracked is not None else ()
-    if split is not None:
-        wf, drums = _split(wf, p, split)
-        perc = (drums,) if percussive else ()
-    perc = perc + found
-    on_dev = isinstance(wf, torch.Tensor) and wf.is_cuda
-    if traversal == 'song':
-        wf32 = wf if on_dev else np.ascontiguousarray(wf, dtype=np.float32)      # (run_songs takes either)
-        events, st = loop.run_songs([wf32], max_notes=iters, silence=silence, residual=residual, stems=stems)
-        evs = events.cpu().numpy()
-        if on_finish is not None:
-            on_finish(0, 0, st)
-        notes = ev.song_events_to_notes(evs, 1 + len(wf32) // p.H, len(wf32), sr=p.sr)
-        return (notes, evs) + ((st.residual[0],) if residual else ()) + ((st.stem_audio[0],) if stems else ()) + perc
-    L = p.H * (p.timing_frames - 1)
-    wf_dev = wf if on_dev else torch.from_numpy(np.ascontiguousarray(wf, dtype=np.float32)).cuda()
-    wins, starts = cut_windows(wf.cpu().numpy() if on_dev else np.asarray(wf, dtype=np.float32), L, L // 2)
-    # song-level normalisers, as training.py:269-282 computes them: once per song, the maxima of the WHOLE song's
-    # STFT and CQTs (one pass of the block-sum kernel over the song as a single signal), shared by every window
-    song_refs = loop.song_levels(wf_dev)
-    # the loop proper: host batches streamed through run_stream (copy of batch i+1 under the compute of batch i)
-    chunks = [wins[b0:b0 + batch] for b0 in range(0, len(wins), batch)]
-
-    def refs_for(i):
-        return {k: v.expand(len(chunks[i])).contiguous() for k, v in song_refs.items()}
-    all_ev = [e.cpu().numpy() for e, _ in loop.run_stream(chunks, refs=refs_for)]
-    evs = np.concatenate(all_ev, axis=1)
-    notes = ev.events_to_notes(evs, p.timing_frames, L, sr=p.sr,
-                               window_start_s=[s / p.sr for s in starts])
-    return (ev.merge_overlap_duplicates(notes), evs) + perc
+    song = _record(wf, sr, p, loop, traversal, batch, split, tracked, percussive, iters=iters, silence=silence,
+                   residual=residual, stems=stems, on_finish=_by_index(on_finish))
+    return _result(song, residual, stems, percussive, tracked is not None)
 
 
 def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', 'instrument', 'velocity'),
@@ -242,7 +326,8 @@ def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', '
                           hpss=None, percussive=False, beats=False):
     """The song queue behind transcribe_songs (TranscriptionLoop.iter_song_queue): yields (index, notes, events) as
     each song finishes, in finishing order -- (index, notes, events[, residual waveform][, stems [G, samples]]) with
-    residual=True / stems=True.  wfs: a sequence or an iterator of mono float32 waveforms at params.sr; an
+    residual=True / stems=True: the fields of a Song, put in order by _result.  wfs: a sequence or an iterator of mono
+    float32 waveforms at params.sr; an
     item may also be a (waveform [n] or [n, channels], sr) pair, which is resampled to params.sr on the device as it is
     pulled (audio.resample).  on_finish(index, slot, state): iter_song_queue's hook, called when a song is found
     finished, before its slot and its pool region are given away.
@@ -254,38 +339,20 @@ def iter_transcribe_songs(wfs, params=None, iters=5, heads=('timing', 'pitch', '
     split -- three device calls and one copy back per song -- and its beat dict is appended last to what is yielded."""
     want = percussive is True or isinstance(percussive, dict)
     split = _hpss_option(hpss, want)
-    drums = percussive if isinstance(percussive, dict) else {}
     p = params or Hyperparams(N=2048)
-    tracked, found = _beats_option(beats, p), {}
+    tracked = _beats_option(beats, p)
     if loop is None:
         loop = _make_loop(p, iters, heads, groups, weights_dir, guess, **_model_option(instrument_model))
-    lens = {}
+    for song in _song_records(_pairs(wfs), p, loop, slots, iters, silence, poll, pool_frames, residual, stems,
+                              _by_index(on_finish), split, tracked, want,
+                              percussive if isinstance(percussive, dict) else None):
+        yield _result(song, residual, stems, want, tracked is not None, indexed=True)
 
-    def feed():
-        for i, wf in enumerate(wfs):
-            if isinstance(wf, tuple):
-                w = audio.resample(wf[0], wf[1], p.sr)
-            else:
-                w = np.ascontiguousarray(wf, dtype=np.float32).reshape(-1)
-            if tracked is not None:
-                found[i] = _track(w, p, tracked)
-            if split is not None:
-                w, drum = _split(w, p, split)
-                if want:                                           # (kept on the device only for a caller that asked)
-                    drums[i] = drum
-            lens[i] = len(w)
-            yield w
-    for item in loop.iter_song_queue(feed(), slots, max_notes=iters, silence=silence, poll=poll,
-                                     pool_frames=pool_frames, on_finish=on_finish, residual=residual, stems=stems):
-        i, evs = item[0], item[1]
-        n = lens.pop(i)
-        one = evs.copy()
-        one[:, 0] = 0                                              # song_events_to_notes indexes scalars by song 0
-        notes = ev.song_events_to_notes(one, 1 + n // p.H, n, sr=p.sr)
-        for note in notes:
-            note['song'] = i
-        drum = drums.pop(i, None)
-        yield (i, notes, evs) + tuple(item[2:]) + ((drum,) if want else ()) + ((found.pop(i),) if tracked is not None else ())
+
+def _pairs(wfs):
+    """The queue's input as (waveform, rate) pairs: a bare item is a host waveform at the model's rate (None)."""
+    for wf in wfs:
+        yield wf if isinstance(wf, tuple) else (np.ascontiguousarray(wf, dtype=np.float32).reshape(-1), None)
 
 
 def transcribe_songs(wfs, params=None, slots=8, **kw):
@@ -293,7 +360,7 @@ def transcribe_songs(wfs, params=None, slots=8, **kw):
     song.  Returns [(notes, events [k, 9]), ...] in input order; a song's notes are those of
     transcribe(wf, traversal='song') for it alone (with `song` = its index).  residual=True / stems=True:
     (notes, events[, residual][, stems]); beats=True appends each song's beat dict."""
-    out = {item[0]: tuple(item[1:]) for item in iter_transcribe_songs(wfs, params, slots=slots, **kw)}
+    out = {i: tuple(rest) for i, *rest in iter_transcribe_songs(wfs, params, slots=slots, **kw)}
     return [out[i] for i in range(len(out))]
 
 
@@ -626,6 +693,60 @@ def _same_rate(paths, pairs, rate, decode):
         yield (wf, sr) if decode == 'device' else wf        # (the queue takes a device tensor as a pair; equal rates pass)
 
 
+def _preflight(a, percussive, beats_out, own, own_first):
+    """The checks both command-line modes make before a file is read, in the order each always made them: writer, split
+    and beat options, then the image sizes -- the mode's `own` checks ahead of the sizes (own_first: the one-file mode)
+    or after them.  -> (audio.hpss's keywords or None, beats wanted, spectrogram size or None, roll size or None)."""
+    _check_writer(a)
+    split, want_beats = _hpss_cli(a, percussive), _beats_cli(a, beats_out)
+    if own_first:
+        own()
+    size, roll_size = _spectrogram_size(a), _roll_size(a)
+    if not own_first:
+        own()
+    return split, want_beats, size, roll_size
+
+
+def _make_dirs(*dirs):
+    """Every output directory a command line was given, made before its first song is walked."""
+    for d in dirs:
+        if d is not None:
+            os.makedirs(d, exist_ok=True)
+
+
+def _cli_walk(a, rate, split, want_beats, keep_residual, draw, on_finish):
+    """The model of a command line at `rate` and what it asks of the walk: (hyperparameters, loop, the keywords of
+    _record / _song_records).  The pictures of --spectrogram-dir (draw) need the residual and the stems kept."""
+    p = Hyperparams(N=2048, sr=rate)
+    loop = _make_loop(p, a.iters, ('timing', 'pitch', 'instrument', 'velocity'), CLI_GROUPS, a.weights, a.guess,
+                      **_model_option(a.instrument_model))
+    return p, loop, dict(iters=a.iters, residual=keep_residual or draw, stems=a.stems_dir is not None or draw,
+                         on_finish=on_finish if draw else None, split=split, tracked=_beats_option(want_beats, p),
+                         percussive=split is not None)
+
+
+def _write_song(a, song, rate, name, out, residual_option):
+    """The files of one Song, in both modes: out['mid'] (with the tempo map under --tempo-map) and its line, then
+    out['beats'], then the residual to out['residual'], the stems into --stems-dir as <name>.group<g>.<format> and the
+    percussive part to out['percussive'] in ONE write_song_audio call; a path that is None is not written.  A walk that
+    stopped before the song's end has no residual and no stems: refused under the mode's name of the option."""
+    if a.tempo_map:
+        ev.write_midi(song.notes, out['mid'], beats=song.beats['beats'], quantize=a.quantize)
+    else:
+        ev.write_midi(song.notes, out['mid'])
+    print('%d notes -> %s' % (len(song.notes), out['mid']))
+    if out['beats'] is not None:
+        write_beats(out['beats'], song.beats)
+    for option, asked, kept in ((residual_option, out['residual'], song.residual), ('--stems-dir', a.stems_dir, song.stems)):
+        if asked is not None and kept is None:
+            raise SystemExit('%s: the walk stopped before the end of the song' % option)
+    write_song_audio(rate, residual=song.residual if out['residual'] is not None else None, residual_path=out['residual'],
+                     stems=song.stems if a.stems_dir is not None else None, stems_dir=a.stems_dir, name=name,
+                     flac=a.flac, format=a.format, predictor=a.flac_predictor,
+                     percussive=song.percussive if out['percussive'] is not None else None,
+                     percussive_path=out['percussive'])
+
+
 def main_songs(argv):
     """The many-files mode: --songs a.flac b.flac ... --out-dir DIR [--slots N]; one .mid per input, written as its song
     finishes."""
@@ -649,18 +770,12 @@ def main_songs(argv):
     ap.add_argument('--beats-dir', default=None, metavar='DIR',
                     help='write <stem>.beats.txt per song as it finishes: its beat times in seconds, one per line')
     a = ap.parse_args(argv)
-    _check_writer(a)
-    split = _hpss_cli(a, a.percussive_dir)
-    want_beats = _beats_cli(a, a.beats_dir)
-    size = _spectrogram_size(a)
-    roll_size = _roll_size(a)
-    if a.gold_dir is not None and not os.path.isdir(a.gold_dir):
-        raise SystemExit('--gold-dir: %s is not a directory' % a.gold_dir)
-    os.makedirs(a.out_dir, exist_ok=True)
-    keep, keep_stems = a.residual_dir is not None, a.stems_dir is not None
-    for d in (a.residual_dir, a.stems_dir, a.spectrogram_dir, a.roll_dir, a.percussive_dir, a.beats_dir):
-        if d is not None:
-            os.makedirs(d, exist_ok=True)
+
+    def own():
+        if a.gold_dir is not None and not os.path.isdir(a.gold_dir):
+            raise SystemExit('--gold-dir: %s is not a directory' % a.gold_dir)
+    split, want_beats, size, roll_size = _preflight(a, a.percussive_dir, a.beats_dir, own, False)
+    _make_dirs(a.out_dir, a.residual_dir, a.stems_dir, a.spectrogram_dir, a.roll_dir, a.percussive_dir, a.beats_dir)
     stems = [os.path.splitext(os.path.basename(f))[0] for f in a.songs]
     if len(set(stems)) != len(stems):
         raise SystemExit('--songs: two inputs would write the same .mid (equal file names)')
@@ -681,42 +796,19 @@ def main_songs(argv):
     durations = []
     if roll_size is not None:
         wfs = _note_durations(wfs, rate, durations)
-    draw = size is not None
 
-    drums = {}                                   # {song: percussive waveform} of the songs in flight, with --hpss
+    def on_finish(song, slot, st):
+        write_song_spectrograms(st, slot, a.spectrogram_dir, stems[song.index], size, percussive=song.percussive)
+    p, loop, walk = _cli_walk(a, rate, split, want_beats, a.residual_dir is not None, size is not None, on_finish)
 
-    def on_finish(i, slot, st):
-        write_song_spectrograms(st, slot, a.spectrogram_dir, stems[i], size, percussive=drums.get(i))
-    split_options = {} if split is None else dict(hpss=split, percussive=drums)
-    if want_beats:
-        split_options['beats'] = True
-    queue = iter_transcribe_songs(wfs, Hyperparams(N=2048, sr=rate), iters=a.iters, weights_dir=a.weights, guess=a.guess,
-                                  slots=a.slots, residual=keep or draw, stems=keep_stems or draw, groups=CLI_GROUPS,
-                                  instrument_model=a.instrument_model, on_finish=on_finish if draw else None,
-                                  **split_options)
-    for item in queue:
-        i, notes = item[0], item[1]
-        found = item[-1] if want_beats else None
-        if want_beats:
-            item = item[:-1]
-        drum = item[-1] if split is not None else None
-        if split is not None:
-            item = item[:-1]
-        out = os.path.join(a.out_dir, stems[i] + '.mid')
-        if a.tempo_map:
-            ev.write_midi(notes, out, beats=found['beats'], quantize=a.quantize)
-        else:
-            ev.write_midi(notes, out)
-        print('%d notes -> %s' % (len(notes), out))
-        if a.beats_dir is not None:
-            write_beats(os.path.join(a.beats_dir, stems[i] + '.beats.txt'), found)
-        write_song_audio(rate, residual=item[3] if keep else None,
-                         residual_path=os.path.join(a.residual_dir, stems[i] + '.residual.' + a.format) if keep else None,
-                         stems=item[-1] if keep_stems else None, stems_dir=a.stems_dir, name=stems[i], flac=a.flac,
-                         format=a.format, predictor=a.flac_predictor,
-                         percussive=drum if a.percussive_dir is not None else None,
-                         percussive_path=os.path.join(a.percussive_dir, stems[i] + '.percussive.' + a.format)
-                         if a.percussive_dir is not None else None)
+    def path(directory, stem, kind):                                   # <dir>/<stem>.<kind>, None without the directory
+        return None if directory is None else os.path.join(directory, '%s.%s' % (stem, kind))
+    for song in _song_records(_pairs(wfs), p, loop, a.slots, **walk):
+        stem = stems[song.index]
+        _write_song(a, song, rate, stem, dict(mid=path(a.out_dir, stem, 'mid'), beats=path(a.beats_dir, stem, 'beats.txt'),
+                                              residual=path(a.residual_dir, stem, 'residual.' + a.format),
+                                              percussive=path(a.percussive_dir, stem, 'percussive.' + a.format)),
+                    '--residual-dir')
     golds = [None] * len(stems)
     if a.gold_dir is not None:
         scored = []
@@ -731,6 +823,10 @@ def main_songs(argv):
             write_scores(*zip(*scored), collection_path=os.path.join(a.out_dir, 'scores.json'))
     if roll_size is not None:
         write_rolls(stems, [os.path.join(a.out_dir, s + '.mid') for s in stems], durations, a.roll_dir, roll_size, golds)
+
+
+# what the one-file mode writes only with --traversal song: (option, what the independent windows do not have)
+_SONG_ONLY = (('--residual', 'residual'), ('--stems-dir', 'stems'), ('--spectrogram-dir', 'spectra'))
 
 
 def main(argv=None):
@@ -756,19 +852,14 @@ def main(argv=None):
     ap.add_argument('--beats-out', default=None, metavar='FILE',
                     help='write the beat times of the song in seconds, one per line')
     a = ap.parse_args(argv)
-    _check_writer(a)
-    split = _hpss_cli(a, a.percussive)
-    want_beats = _beats_cli(a, a.beats_out)
-    if a.gold is not None and not os.path.isfile(a.gold):
-        raise SystemExit('--gold: %s: no such file' % a.gold)
-    if a.residual is not None and a.traversal != 'song':
-        raise SystemExit('--residual needs --traversal song (independent windows have no song-level residual)')
-    if a.stems_dir is not None and a.traversal != 'song':
-        raise SystemExit('--stems-dir needs --traversal song (independent windows have no song-level stems)')
-    if a.spectrogram_dir is not None and a.traversal != 'song':
-        raise SystemExit('--spectrogram-dir needs --traversal song (independent windows have no song-level spectra)')
-    size = _spectrogram_size(a)
-    roll_size = _roll_size(a)
+
+    def own():
+        if a.gold is not None and not os.path.isfile(a.gold):
+            raise SystemExit('--gold: %s: no such file' % a.gold)
+        for option, noun in _SONG_ONLY:
+            if getattr(a, option[2:].replace('-', '_')) is not None and a.traversal != 'song':
+                raise SystemExit('%s needs --traversal song (independent windows have no song-level %s)' % (option, noun))
+    split, want_beats, size, roll_size = _preflight(a, a.percussive, a.beats_out, own, True)
     wf, sr = next(_read_inputs([a.infile], a.decode))
     duration = int(wf.shape[0]) / float(sr)
     if a.sr is None:                             # the model at the file's rate
@@ -777,54 +868,20 @@ def main(argv=None):
         raise SystemExit('--sr: the rate must be positive')
     else:                                        # the file at the model's rate: resampled and downmixed on the device
         model_sr, file_sr = a.sr, sr
-    draw = size is not None
     name = os.path.splitext(os.path.basename(a.infile))[0]
+    _make_dirs(a.stems_dir, a.spectrogram_dir, a.roll_dir)
 
-    def on_finish(i, slot, st):
+    def on_finish(song, slot, st):
         if not int(st.finished[slot]):
             raise SystemExit('--spectrogram-dir: the walk stopped before the end of the song')
-        os.makedirs(a.spectrogram_dir, exist_ok=True)
-        write_song_spectrograms(st, slot, a.spectrogram_dir, name, size, percussive=drums.get(0))
-    drums, found = {}, None
-    if want_beats and split is not None:         # the signal as given, at the model's rate, ahead of the split below
-        if file_sr is not None:
-            wf, file_sr = audio.resample(wf, file_sr, model_sr), None
-        found = _track(wf, Hyperparams(N=2048, sr=model_sr), {})
-    if split is not None:
-        # the split here, at the model's rate, so that the walk's hook can draw the percussive part; transcribe() then
-        # sees the harmonic waveform at its own rate and splits nothing
-        p = Hyperparams(N=2048, sr=model_sr)
-        wf, drums[0] = _split(wf if file_sr is None else audio.resample(wf, file_sr, model_sr), p, split)
-        file_sr = None
-    got = transcribe(wf, Hyperparams(N=2048, sr=model_sr), iters=a.iters, weights_dir=a.weights, guess=a.guess,
-                     traversal=a.traversal, sr=file_sr, residual=a.residual is not None or draw,
-                     stems=a.stems_dir is not None or draw, groups=CLI_GROUPS, instrument_model=a.instrument_model,
-                     on_finish=on_finish if draw else None, **(dict(beats=True) if want_beats and found is None else {}))
-    if want_beats and found is None:
-        got, found = got[:-1], got[-1]
-    notes = got[0]
-    if a.tempo_map:
-        ev.write_midi(notes, a.outfile, beats=found['beats'], quantize=a.quantize)
-    else:
-        ev.write_midi(notes, a.outfile)
-    print('%d notes -> %s' % (len(notes), a.outfile))
-    if a.beats_out is not None:
-        write_beats(a.beats_out, found)
-    if a.residual is not None and got[2] is None:
-        raise SystemExit('--residual: the walk stopped before the end of the song')
-    if a.stems_dir is not None:
-        if got[-1] is None:
-            raise SystemExit('--stems-dir: the walk stopped before the end of the song')
-        os.makedirs(a.stems_dir, exist_ok=True)
-    write_song_audio(model_sr, residual=got[2] if a.residual is not None else None, residual_path=a.residual,
-                     stems=got[-1] if a.stems_dir is not None else None, stems_dir=a.stems_dir,
-                     name=name, flac=a.flac, format=a.format,
-                     predictor=a.flac_predictor, percussive=drums.get(0) if a.percussive is not None else None,
-                     percussive_path=a.percussive)
+        write_song_spectrograms(st, slot, a.spectrogram_dir, name, size, percussive=song.percussive)
+    p, loop, walk = _cli_walk(a, model_sr, split, want_beats, a.residual is not None, size is not None, on_finish)
+    song = _record(wf, file_sr, p, loop, a.traversal, **walk)
+    _write_song(a, song, model_sr, name, dict(mid=a.outfile, beats=a.beats_out, residual=a.residual,
+                                              percussive=a.percussive), '--residual')
     if a.gold is not None:
         write_scores([name], [a.outfile], [a.gold])
     if roll_size is not None:
-        os.makedirs(a.roll_dir, exist_ok=True)
         write_rolls([name], [a.outfile], [duration], a.roll_dir, roll_size, [a.gold])
 
 

@@ -382,6 +382,49 @@ def test_transcribe_songs_and_cli(env, tmp_path):
     assert os.path.getsize(str(tmp_path / 'one.mid')) > 20
 
 
+def test_every_optional_output_at_once_keeps_the_documented_order(env):
+    """transcribe(traversal='song') asked for residual, stems, percussive and beats together returns six items in the
+    documented order, each the item of the run that asks for it alone; transcribe_songs with the same flags returns the
+    same six for song 0 (notes up to `song`)."""
+    torch = env['torch']
+    from amt_saga import transcribe as tr
+    p = env['hp'].Hyperparams(N=2048, window_size_note_time=1)
+    lp = tr._make_loop(p, 1, ('timing', 'pitch', 'instrument', 'velocity'), (0, 1, 2), None, 'bank')
+    n = int(2.4 * p.H * (p.timing_frames - 1))
+    notes_in = [(j % 3, 60 + 2 * j, 100, 0.2 + 0.7 * j, 0.4) for j in range(int(n / p.sr / 0.7))]
+    wf = osynth.render_window(notes_in, n, p.sr).numpy().astype(np.float32)
+    rng = np.random.default_rng(6)
+    for s in range(3000, n - 64, 11000):                            # drum-like bursts: a percussive part that is not 0
+        wf[s:s + 64] += (0.5 * (2 * rng.random(64) - 1)).astype(np.float32)
+
+    def run(**kw):
+        return tr.transcribe(wf, p, iters=1, loop=lp, traversal='song', hpss=True, **kw)
+    everything = dict(residual=True, stems=True, percussive=True, beats=True)
+    got = run(**everything)
+    assert len(got) == 6
+    notes, evs, residual, stems, percussive, beats = got
+    assert residual.ndim == 1 and stems.ndim == 2 and stems.shape[0] == 3 and percussive.ndim == 1
+    assert float(percussive.abs().max()) > 0 and set(beats) == {'period', 'tempo', 'beats', 'frames'}
+    for k, flag in enumerate(('residual', 'stems', 'percussive', 'beats')):
+        alone = run(**{flag: True})
+        assert len(alone) == 3 and alone[0] == notes and np.array_equal(alone[1], evs), flag
+        if flag == 'beats':
+            assert alone[2] == got[2 + k]
+        else:
+            assert alone[2].shape == got[2 + k].shape and torch.equal(alone[2], got[2 + k]), flag
+    plain = run()
+    assert len(plain) == 2 and plain[0] == notes and np.array_equal(plain[1], evs)
+    queue = tr.transcribe_songs([wf, wf[:n // 2]], p, slots=2, iters=1, loop=lp, hpss=True, **everything)
+    assert [len(q) for q in queue] == [6, 6]
+    q_notes, q_evs, q_residual, q_stems, q_percussive, q_beats = queue[0]
+    assert [dict(nt, song=0) for nt in q_notes] == notes and all(nt['song'] == 0 for nt in q_notes)
+    live = evs[evs[:, 0, 2] != so.FINISHED, 0, :]
+    assert np.array_equal(q_evs[:, 1:], live[:, 1:]) and np.all(q_evs[:, 0] == 0)
+    assert torch.equal(q_residual, residual) and torch.equal(q_stems, stems) and torch.equal(q_percussive, percussive)
+    assert q_beats == beats
+    assert all(nt['song'] == 1 for nt in queue[1][0]) and queue[1][2].shape[0] < residual.shape[0]
+
+
 def test_song_queue_argument_checks(env):
     p = env['hp'].Hyperparams(N=2048, window_size_note_time=1)
     lp = env['loop'].TranscriptionLoop(p, heads=('timing', 'pitch')).setup_device()
