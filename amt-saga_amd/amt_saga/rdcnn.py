@@ -350,19 +350,64 @@ class res_net:
             out.append(plans)
         return out
 
-    def layer_outputs(self, xs):
-        """predict_device with every conv layer tapped: (y, logits, [[block output per conv layer] per tower]), the block
-        outputs as device tensors [B, H, W, cout] taken before any max pool (amt_rdcnn_layer_tap).  Mode 3 cannot
-        tap a chained FFT-domain layer (the forward answers AMT_E_UNSUPPORTED).  A diagnostic export, bound here."""
+    FC_FORMS = ('none', 'row', 'packed')
+    FC_SHORTCUTS = ('none', 'tensor', 'projected', 'rank1')
+    FC_PLAN_KEYS = ('form', 'have_xf', 'hands_on', 'writes_spatial', 'shortcut', 'wpooled', 'out_is_flat_row', 'per')
+
+    def fc_plans(self, mode=None, B=None):
+        """[[plan per conv layer] per tower]: the FFT-domain form the forward gives each layer in ``mode`` (default: the
+        net's current one) -- form ('none' / 'row' / 'packed'), have_xf (the input is read transformed), hands_on (writes
+        the next layer's transformed input), writes_spatial, shortcut ('none' / 'tensor' as is / 'projected' by the
+        projection kernel / 'rank1'), wpooled (leaves the W-pooled pair), out_is_flat_row, per (GEMM chunks per
+        workgroup in a forward of ``B`` windows; default: a full pass) -- from the function the forward itself asks
+        (amt_rdcnn_fc_plan).  Host only.  A diagnostic export of the library, bound here and not in _lib.PROTOTYPES."""
+        self._ensure()
+        fn = self._lib.amt_rdcnn_fc_plan
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        mode = self.mode if mode is None else int(mode)
+        out = []
+        for t in range(len(self.cfg['input_shapes'])):
+            plans = []
+            for i in range(self.cfg['convolutional_layer_count']):
+                v = np.zeros(len(self.FC_PLAN_KEYS), np.int32)
+                _lib.check(fn(self._net, t, i, mode, int(B or 0), v.ctypes.data_as(C.c_void_p)))
+                p = dict(zip(self.FC_PLAN_KEYS, map(int, v)), tower=t, layer=i + 1, mode=mode)
+                p['form'], p['shortcut'] = self.FC_FORMS[p['form']], self.FC_SHORTCUTS[p['shortcut']]
+                for k in ('have_xf', 'hands_on', 'writes_spatial', 'wpooled', 'out_is_flat_row'):
+                    p[k] = bool(p[k])
+                plans.append(p)
+            out.append(plans)
+        return out
+
+    def layer_outputs(self, xs, layers=None):
+        """predict_device with conv layers tapped: (y, logits, [[block output per conv layer] per tower]), the block
+        outputs as device tensors [B, H, W, cout] taken before any max pool (amt_rdcnn_layer_tap).  ``layers``: the
+        (tower, layer) pairs to tap, layers counted from 1 (default: all); an untapped layer's entry is None.  A mode-3
+        layer that leaves its W-pooled pair (fc_plans: wpooled) comes as [2, B, H, W // 8, cout], the 8-column means
+        and then the 8-column maxima; one that is only handed on transformed (hands_on and not writes_spatial) cannot
+        be tapped (the forward answers AMT_E_UNSUPPORTED).  A diagnostic export, bound here."""
         self._ensure()
         fn = self._lib.amt_rdcnn_layer_tap
         fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         B = xs[0].shape[0]
-        acts = [[empty((B, p['H'], p['W'], p['cout'])) for p in plans] for plans in self.layer_plans()]
+        want = None if layers is None else {(int(t), int(i)) for t, i in layers}
+        fcs = self.fc_plans()
+        acts = []
+        for t, plans in enumerate(self.layer_plans()):
+            row = []
+            for p, f in zip(plans, fcs[t]):
+                if want is not None and (t, p['layer']) not in want:
+                    row.append(None)
+                elif f['wpooled']:
+                    row.append(empty((2, B, p['H'], p['W'] // 8, p['cout'])))
+                else:
+                    row.append(empty((B, p['H'], p['W'], p['cout'])))
+            acts.append(row)
         try:
             for t, row in enumerate(acts):
                 for i, a in enumerate(row):
-                    _lib.check(fn(self._net, t, i, ptr(a)))
+                    if a is not None:
+                        _lib.check(fn(self._net, t, i, ptr(a)))
             y, lg = self.predict_device(xs, return_logits=True)
         finally:
             for t, row in enumerate(acts):

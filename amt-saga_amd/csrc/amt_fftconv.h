@@ -42,6 +42,7 @@ size_t amt_fftconv_freq_floats(int B, int H);                                // 
 int amt_fftconv_forward_fft(const amt_fftconv_layer *L, const float *in_sp, size_t in_stride, int B, int H, int W,
                             float *Xf, float *amaxf, hipStream_t st);
 int amt_fftconv_gemm(const amt_fftconv_layer *L, const float *Xf, const float *amaxf, int B, int H, float *Yf, hipStream_t st);
+int amt_fftconv_gemm_chunks_per_wg(int B);                                   // chunks of 8 windows per GEMM workgroup
 int amt_fftconv_inverse_epilogue(const amt_fftconv_layer *L, const float *Yf, const FcEpilogue &ep, int B, int H, int W,
                                  float *out_sp, size_t out_stride, float *Xf_next, float *amaxf_next, float *amax_out,
                                  hipStream_t st);

@@ -613,6 +613,14 @@ int amt_fftconv_forward_fft(const amt_fftconv_layer *L, const float *in_sp, size
     return fc_row_launch<false>(a, st);
 }
 
+// chunks of FC_CW windows that one GEMM workgroup walks for a batch of B (amt_rdcnn_fc_plan reports it)
+int amt_fftconv_gemm_chunks_per_wg(int B) {
+    const int nchunks = (B + FC_CW - 1) / FC_CW;
+    int per = 1;
+    while ((size_t)((nchunks + per - 1) / per) * FC_NP > 4096 && per < 16) per *= 2;      // ~2 resident rounds of workgroups
+    return per;
+}
+
 int amt_fftconv_gemm(const amt_fftconv_layer *L, const float *Xf, const float *amaxf, int B, int H, float *Yf, hipStream_t st) {
     if (!L || !Xf || !Yf || !amaxf) return AMT_E_INVALID;
     if (H > 20) return AMT_E_UNSUPPORTED;
@@ -620,8 +628,7 @@ int amt_fftconv_gemm(const amt_fftconv_layer *L, const float *Xf, const float *a
     const size_t lds = 2 * (rows_cap + 1) * FC_APITCH * sizeof(_Float16) + (size_t)4 * 16 * FC_OPITCH * 4 + 2 * FC_CW * 4 + rows_cap * 4 +
                        2 * rows_cap + 16;
     const int nchunks = (B + FC_CW - 1) / FC_CW;
-    int per = 1;
-    while ((size_t)((nchunks + per - 1) / per) * FC_NP > 4096 && per < 16) per *= 2;      // ~2 resident rounds of workgroups
+    const int per = amt_fftconv_gemm_chunks_per_wg(B);
     FcGemmArgs a{Xf, Yf, amaxf, L->gw, L->gsw, B, H, per, 0, 0};
     fc_strides(H, &a.sf, &a.sh);
     return amt_launch<fc_gemm_kernel>(lds, dim3(FC_NP, (nchunks + per - 1) / per), 256, lds, st, a);     // (the limit grows with H)
@@ -662,7 +669,7 @@ size_t amt_fftconv_workspace_bytes(int B, int H) { return (2 * amt_fftconv_freq_
 int amt_fftconv_run(const amt_fftconv_layer *L, const float *in, const float *shortcut, int B, int H, int W, float *out,
                     void *workspace, size_t workspace_bytes, int repeat_gemm, void *stream) {
     if (!L || !in || !out || !workspace || B <= 0 || H <= 0 || W <= 0) return AMT_E_INVALID;
-    if (W + 15 > FC_NF) return AMT_E_UNSUPPORTED;
+    if (W + 15 > FC_NF || H > 20) return AMT_E_UNSUPPORTED;      // refused here, before the forward transform is launched
     if (workspace_bytes < amt_fftconv_workspace_bytes(B, H)) return AMT_E_NOMEM;
     hipStream_t st = (hipStream_t)stream;
     float *Xf = (float *)workspace, *Yf = Xf + amt_fftconv_freq_floats(B, H), *amaxf = Yf + amt_fftconv_freq_floats(B, H);

@@ -667,10 +667,12 @@ int amt_rdcnn_profile_read(amt_rdcnn *net, int32_t *desc, double *ms, double *wi
 // The layer tap.  dst: device memory for the block output of conv layer `layer` (0-based) of `tower` -- after BN +
 // sigmoid, after the shortcut add and its BN where a shortcut closes, before any max pool -- dense [B][H][W][cout]
 // for the B of the forwards that follow; NULL takes the tap away.  While a tap is set amt_rdcnn_forward copies the
-// layer's output there on its stream, right behind the layer's launches.  A mode-3 layer whose spatial output the
-// FFT-domain chain does not write (the next layer reads it transformed, or it leaves only its W-pooled pair) cannot be
-// tapped: the forward answers AMT_E_UNSUPPORTED before it launches that layer and computes what it always computes
-// otherwise.  Without taps the forward launches exactly what it launches without this export.
+// layer's output there on its stream, right behind the layer's launches.  A mode-3 layer that leaves its W-pooled pair
+// in place of its output (amt_rdcnn_fc_plan: wpooled) is tapped as that pair: dst is dense [2][B][H][W / 8][cout], the
+// 8-column means (wavg) first, then the 8-column maxima (wmax).  A mode-3 layer with neither -- the next layer reads it
+// transformed and nothing else reads it (hands_on && !writes_spatial) -- cannot be tapped: the forward answers
+// AMT_E_UNSUPPORTED before it launches that layer and computes what it always computes otherwise.  Without taps the
+// forward launches exactly what it launches without this export.
 int amt_rdcnn_layer_tap(amt_rdcnn *net, int tower, int layer, float *dst) {
     if (!net || tower < 0 || tower >= (int)net->towers.size()) return AMT_E_INVALID;
     if (layer < 0 || layer >= (int)net->towers[tower].convs.size()) return AMT_E_INVALID;
@@ -809,15 +811,77 @@ static bool fc_wpooled_ok(const amt_rdcnn *net, const Tower &tw, int i, ConvImpl
     }
     return true;
 }
-static int run_fc(const ConvOp &c, const float *in, size_t in_stride, bool have_xf, int Bc, const FcEpilogue &ep,
-                  const FcBufs &f, float *o, size_t o_stride, bool next_fc, float *amax_o, hipStream_t st) {
+// THE form of one layer's step: what amt_rdcnn_forward launches for conv layer i of a tower in `mode`, decided here and
+// nowhere else (amt_rdcnn_fc_plan reports the same struct).  H x W: the layer's image.
+struct LayerForm {
+    ConvImpl impl;
+    bool last_op;              // the output goes into the tower's part of the dense input (stride: the flat row)
+    const ProjOp *rank1;       // shortcut: a 1 x 1 projection of the one-channel input, formed in the epilogue
+    const ProjOp *proj;        // shortcut: a tensor made by proj_kernel (neither: the block's input as is, where one closes)
+    // FFT-domain forms only (false elsewhere, need_sp true)
+    bool have_xf;              // the previous layer left this one's input transformed in Xf: no forward transform
+    bool next_fc;              // hands its output on transformed (Xf_next) to a next layer of its kind
+    bool wpooled;              // leaves the W-pooled pair in place of its output (fc_wpooled_ok)
+    bool need_sp;              // writes its spatial output
+};
+static bool fc_hands_on(const Tower &tw, int i, int mode) {
+    const ConvOp &c = tw.convs[i];
+    const ConvImpl impl = conv_impl(c, mode);
+    return impl_is_fft(impl) && i + 1 < (int)tw.convs.size() && !c.pool_after && conv_impl(tw.convs[i + 1], mode) == impl;
+}
+static LayerForm layer_form(const amt_rdcnn *net, const Tower &tw, int i, int mode, int H, int W) {
+    const ConvOp &c = tw.convs[i];
+    LayerForm f{};
+    f.impl = conv_impl(c, mode);
+    f.last_op = (i == (int)tw.convs.size() - 1) && !c.pool_after;
+    if (c.residual && c.sc_proj >= 0) {
+        const ProjOp &pr = tw.projs[c.sc_proj];
+        (shortcut_is_rank1(f.impl, c, pr) ? f.rank1 : f.proj) = &pr;
+    }
+    const bool fft = impl_is_fft(f.impl);
+    f.have_xf = fft && i > 0 && fc_hands_on(tw, i - 1, mode);
+    f.next_fc = fft && fc_hands_on(tw, i, mode);
+    f.wpooled = fc_wpooled_ok(net, tw, i, f.impl, H, W);
+    // the spatial output is written only where something reads it: a later shortcut, a pooling, a layer of another kind
+    f.need_sp = !fft || (!f.wpooled && (!f.next_fc || c.residual));
+    return f;
+}
+
+// Diagnostic export (not in include/amt_saga.h; tests/test_gpu_rdcnn_fft_layers.py), bound in rdcnn.py next to
+// amt_rdcnn_layer_plan: the FFT-domain form of conv layer `layer` (0-based) of `tower` in `mode`, from layer_form -- the
+// function the forward itself asks -- as 8 ints: form (0 none, 1 row, 2 packed), have_xf, hands_on (writes Xf_next),
+// writes_spatial, shortcut kind (0 none, 1 tensor as is, 2 tensor through proj_kernel, 3 rank-1), wpooled,
+// out_is_flat_row, GEMM chunks per workgroup for a forward of B windows (amt_fftconv_gemm; 1 for the packed form, whose
+// persistent grid has no such figure; B <= 0: a full pass of RD_CHUNK windows).  Host only, reads the net.  A layer that
+// is no FFT-domain form reports form 0 and its shortcut kind, spatial output and flat row all the same.  (Like
+// amt_rdcnn_layer_plan, mode 3 reports an FFT-domain form only once amt_rdcnn_set_mode(net, 3) has built it.)
+int amt_rdcnn_fc_plan(const amt_rdcnn *net, int tower, int layer, int mode, int B, int32_t *out) {
+    if (!net || !out || mode < 0 || mode > 3 || tower < 0 || tower >= (int)net->towers.size()) return AMT_E_INVALID;
+    if (layer < 0 || layer >= (int)net->towers[tower].convs.size()) return AMT_E_INVALID;
+    const Tower &tw = net->towers[tower];
+    const ConvOp &c = tw.convs[layer];
+    const LayerForm f = layer_form(net, tw, layer, mode, c.H, c.W);
+    const int form = f.impl == IMPL_FFT_ROW ? 1 : f.impl == IMPL_FFT_PACKED ? 2 : 0;
+    const int Bc = B <= 0 ? RD_CHUNK : std::min(B, RD_CHUNK);
+    out[0] = form;
+    out[1] = f.have_xf;
+    out[2] = f.next_fc;
+    out[3] = f.need_sp;
+    out[4] = !c.residual ? 0 : f.rank1 ? 3 : f.proj ? 2 : 1;
+    out[5] = f.wpooled;
+    out[6] = f.last_op;
+    out[7] = form == 1 ? amt_fftconv_gemm_chunks_per_wg(Bc) : form == 2 ? 1 : 0;
+    return AMT_OK;
+}
+
+static int run_fc(const ConvOp &c, const float *in, size_t in_stride, const LayerForm &f, int Bc, const FcEpilogue &ep,
+                  const FcBufs &b, float *o, size_t o_stride, float *amax_o, hipStream_t st) {
     int rc = AMT_OK;
-    if (!have_xf) rc = fc_forward_fft(c.fc, in, in_stride, Bc, f.Xf, f.amaxf, st);
-    if (rc == AMT_OK) rc = fc_gemm(c.fc, f.Xf, f.amaxf, Bc, f.Yf, st);
+    if (!f.have_xf) rc = fc_forward_fft(c.fc, in, in_stride, Bc, b.Xf, b.amaxf, st);
+    if (rc == AMT_OK) rc = fc_gemm(c.fc, b.Xf, b.amaxf, Bc, b.Yf, st);
     if (rc != AMT_OK) return rc;
-    const bool need_sp = !ep.wmax && (!next_fc || c.residual);
-    return fc_inverse_epilogue(c.fc, f.Yf, ep, Bc, need_sp ? o : nullptr, o_stride, next_fc ? f.Xf : nullptr, f.amaxf,
-                               next_fc ? nullptr : amax_o, st);
+    return fc_inverse_epilogue(c.fc, b.Yf, ep, Bc, f.need_sp ? o : nullptr, o_stride, f.next_fc ? b.Xf : nullptr, b.amaxf,
+                               f.next_fc ? nullptr : amax_o, st);
 }
 
 int amt_rdcnn_forward(const amt_rdcnn *net, const float *const *x, int B, float *y, float *logits,
@@ -853,7 +917,6 @@ int amt_rdcnn_forward(const amt_rdcnn *net, const float *const *x, int B, float 
             bool p0_wpooled = false;                     // p0 is the W-pooled average of a layer's output (fc_wpooled_ok)
             int H = tw.in_h, W = tw.in_w;
             const int L = (int)tw.convs.size();
-            bool xf_valid = false;                       // mode 3: the previous layer left its output transformed in Xf
             auto pick = [&](const float *a, const float *b_, const float *c_) -> float * {
                 for (int i = 0; i < 4; ++i)
                     if (buf[i] != a && buf[i] != b_ && buf[i] != c_) return buf[i];
@@ -861,39 +924,33 @@ int amt_rdcnn_forward(const amt_rdcnn *net, const float *const *x, int B, float 
             };
             for (int i = 0; i < L; ++i) {
                 const ConvOp &c = tw.convs[i];
-                const ConvImpl impl = conv_impl(c, mode);
-                const bool last_op = (i == L - 1) && !c.pool_after;
+                const LayerForm form = layer_form(net, tw, i, mode, H, W);
+                const ConvImpl impl = form.impl;
+                const bool last_op = form.last_op, wpooled = form.wpooled;
                 float *o = last_op ? flatbuf + flat_off : pick(cur, p0, nullptr);
                 const size_t o_stride = last_op ? (size_t)flat : (size_t)H * W * c.cout;
                 // shortcut: the block's input as is, its projection (a kernel of its own), or -- a 1 x 1 projection of
                 // the one-channel network input -- formed in the consumer's epilogue (rank1)
                 const float *sc = nullptr; size_t sc_stride = 0;
-                const ProjOp *rank1 = nullptr;
-                if (c.residual && c.sc_proj >= 0) {
-                    const ProjOp &pr = tw.projs[c.sc_proj];
-                    if (shortcut_is_rank1(impl, c, pr)) {
-                        rank1 = &pr;
-                    } else {
-                        float *sb = pick(cur, p0, o);
-                        ProjParams pp{p0, p0_stride, sb, (size_t)pr.HO * pr.WO * pr.cout, pr.w, pr.s, pr.t,
-                                      Bc, pr.H, pr.W, pr.cin, pr.cout, pr.ph, pr.pw, pr.HO, pr.WO};
-                        if (p0_wpooled) { pp.W = pr.W / 8; pp.PW = 1; }      // 1 / (sc_ph * 1) x the epilogue's 0.125 = 1 / (sc_ph * 8)
-                        proj_kernel<<<dim3((pr.WO + PJ_TW - 1) / PJ_TW, pr.HO, Bc), 256,
-                                      (size_t)PJ_TW * pr.cin * sizeof(float), st>>>(pp);
-                        sc = sb; sc_stride = (size_t)pr.HO * pr.WO * pr.cout;
-                    }
-                } else if (c.residual) {
+                const ProjOp *rank1 = form.rank1;
+                if (form.proj) {
+                    const ProjOp &pr = *form.proj;
+                    float *sb = pick(cur, p0, o);
+                    ProjParams pp{p0, p0_stride, sb, (size_t)pr.HO * pr.WO * pr.cout, pr.w, pr.s, pr.t,
+                                  Bc, pr.H, pr.W, pr.cin, pr.cout, pr.ph, pr.pw, pr.HO, pr.WO};
+                    if (p0_wpooled) { pp.W = pr.W / 8; pp.PW = 1; }      // 1 / (sc_ph * 1) x the epilogue's 0.125 = 1 / (sc_ph * 8)
+                    proj_kernel<<<dim3((pr.WO + PJ_TW - 1) / PJ_TW, pr.HO, Bc), 256,
+                                  (size_t)PJ_TW * pr.cin * sizeof(float), st>>>(pp);
+                    sc = sb; sc_stride = (size_t)pr.HO * pr.WO * pr.cout;
+                } else if (c.residual && !rank1) {
                     sc = p0; sc_stride = p0_stride;
                 }
                 const float *s2 = c.residual ? c.s2 : nullptr, *t2 = c.residual ? c.t2 : nullptr;
                 float *amax_o = mode >= 2 ? amax_row(i + 1) : nullptr;
                 // the pooled pair shares the layer's output buffer: [Bc] wavg, then [Bc] wmax (a quarter of it together)
-                const bool wpooled = fc_wpooled_ok(net, tw, i, impl, H, W);
                 const size_t wp_stride = (size_t)H * (W / 8) * c.cout;
-                // an FFT-domain layer hands its output on transformed where the next layer is one of its kind
-                const bool next_fc = impl_is_fft(impl) && i + 1 < L && !c.pool_after && conv_impl(tw.convs[i + 1], mode) == impl;
                 float *const tap = net->taps.empty() ? nullptr : net->taps[t][i];
-                if (tap && impl_is_fft(impl) && (wpooled || (next_fc && !c.residual))) return AMT_E_UNSUPPORTED;      // no spatial output (run_fc)
+                if (tap && !form.need_sp && !wpooled) return AMT_E_UNSUPPORTED;      // handed on transformed only: nothing to copy
                 ProfPending prof{nullptr, nullptr, t, i, Bc};
                 RD_TRY(prof_begin(net, prof, st));
                 switch (impl) {
@@ -912,8 +969,7 @@ int amt_rdcnn_forward(const amt_rdcnn *net, const float *const *x, int B, float 
                     if (rank1) { ep.sc1 = p0; ep.sc1_stride = p0_stride; ep.sc1_w = rank1->w; ep.sc1_s = rank1->s; ep.sc1_t = rank1->t; }
                     else { ep.sc = sc; ep.sc_stride = sc_stride; }
                     if (wpooled) { ep.wavg = o; ep.wmax = o + (size_t)Bc * wp_stride; ep.wp_stride = wp_stride; }
-                    RD_TRY(run_fc(c, cur, cur_stride, xf_valid, Bc, ep, fcb, o, o_stride, next_fc, amax_o, st));
-                    xf_valid = next_fc;
+                    RD_TRY(run_fc(c, cur, cur_stride, form, Bc, ep, fcb, o, o_stride, amax_o, st));
                     break;
                 }
                 default: {
@@ -932,7 +988,14 @@ int amt_rdcnn_forward(const amt_rdcnn *net, const float *const *x, int B, float 
                     // kernel is not built for; none of the reference's head topologies)
                     RD_TRY(launch_absmax(o, (size_t)H * W * c.cout, o_stride, Bc, amax_o, st));
                 RD_TRY(prof_end(net, prof, st));
-                if (tap) {
+                if (tap && wpooled) {
+                    // the pair as the epilogue left it: dense [2][B][H][W / 8][cout], wavg then wmax, B the forward's
+                    const size_t n = wp_stride;
+                    for (int half = 0; half < 2; ++half)
+                        tap_copy_kernel<<<dim3((unsigned)std::min<size_t>((n + 255) / 256, 64), Bc), 256, 0, st>>>(
+                            o + (size_t)half * Bc * wp_stride, wp_stride, tap + ((size_t)half * B + b0) * n, n);
+                    AMT_LAUNCH_CHECK();
+                } else if (tap) {
                     const size_t n = (size_t)H * W * c.cout;      // o_stride is the flat row where this is the last layer
                     tap_copy_kernel<<<dim3((unsigned)std::min<size_t>((n + 255) / 256, 64), Bc), 256, 0, st>>>(
                         o, o_stride, tap + (size_t)b0 * n, n);

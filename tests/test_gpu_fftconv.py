@@ -176,3 +176,114 @@ def test_fft_layer_beside_split_fp16_network_on_a_second_stream(form):
             assert torch.equal(y, want_net), (form, trial)
     finally:
         destroy(h)
+
+
+# ---- the row form alone, over the geometry it accepts (amt_fftconv_run: spatial in, spatial out) ---------------------
+# One axis at a time around B = 2, H = 5, W = 40, without a shortcut; both shortcut settings at the ends of every axis.
+#   H: 1, 3 (fewer rows than the 4 row taps), 4, 20 (the limit; 21 is refused)
+#   W: 1, 15, 16, 17 (around the 16 column taps), 24, 25 (w = 24 n1 + n2: one n1 block and one column more), 47, 561
+#   B: 1, 8, 9, 17 (GEMM chunks of 8 windows: one full, one ragged of 1, two full and one ragged)
+#   B = 120 at 3 x 17: 15 chunks, and 15 x 289 workgroups > 4096, so amt_fftconv_gemm walks two chunks per workgroup
+#   (per = 2; B <= 112 gives per = 1), with the last workgroup's second chunk past the end
+GEOMETRY = ([(2, H, 40, False) for H in (1, 3, 4, 20)] + [(2, 1, 40, True), (2, 20, 40, True)] +
+            [(2, 5, W, False) for W in (1, 15, 16, 17, 24, 25, 47, 561)] + [(2, 5, 1, True), (2, 5, 561, True)] +
+            [(B, 5, 40, False) for B in (1, 8, 9, 17)] + [(1, 5, 40, True), (17, 5, 40, True)] +
+            [(120, 3, 17, True), (120, 3, 17, False)])
+
+
+@pytest.fixture(scope='module')
+def row_layer():
+    """One 32 -> 32 layer with both BatchNormalizations for every geometry case (the shortcut argument decides)."""
+    import torch
+    assert torch.cuda.is_available()
+    from amt_saga import _lib
+    lib = _lib.load()
+    rng = np.random.default_rng(2024)
+    k = (rng.standard_normal((4, 16, 32, 32)) * 0.05).astype(np.float32)
+    bn = [rng.uniform(0.5, 2.0, 32).astype(np.float32), rng.uniform(-1, 1, 32).astype(np.float32),
+          rng.uniform(0.5, 2.0, 32).astype(np.float32), rng.uniform(-1, 1, 32).astype(np.float32)]
+    h = C.c_void_p()
+    fp = lambda x: x.ctypes.data_as(C.c_void_p)
+    _lib.check(lib.amt_fftconv_create(C.byref(h), fp(k), *[fp(v) for v in bn]))
+    yield lib, h, k, bn
+    lib.amt_fftconv_destroy(h)
+
+
+def _run_row(row_layer, a, sc):
+    """amt_fftconv_run twice on fresh outputs: (status, first result, the second has the same bits)."""
+    import torch
+    lib, h = row_layer[:2]
+    B, H, W, _ = a.shape
+    ad = torch.from_numpy(a).cuda()
+    scd = torch.from_numpy(sc).cuda() if sc is not None else None
+    need = lib.amt_fftconv_workspace_bytes(B, H)
+    ws = torch.empty((need + 3) // 4, dtype=torch.float32, device='cuda')
+    outs = []
+    for fill in (7.0, -7.0):
+        out = torch.full_like(ad, fill)
+        rc = lib.amt_fftconv_run(h, ad.data_ptr(), scd.data_ptr() if sc is not None else None, B, H, W, out.data_ptr(),
+                                 ws.data_ptr(), need, 1, None)
+        torch.cuda.synchronize()
+        outs.append(out)
+    return rc, outs[0].cpu().numpy(), torch.equal(outs[0], outs[1])
+
+
+@pytest.mark.parametrize('B,H,W,residual', GEOMETRY)
+def test_fftconv_geometry_vs_numpy(row_layer, B, H, W, residual):
+    """Window 0 three times as loud and the last window all zero (amax = 0 on the scaling path: its output is
+    sigmoid(t1), with a shortcut + sc and the second BN): finite, under the bar of this file, the same bits twice."""
+    from amt_saga import _lib
+    k, (s1, t1, s2, t2) = row_layer[2], row_layer[3]
+    if B == 120:
+        # the arithmetic of amt_fftconv_gemm: per doubles while ceil(nchunks / per) * 289 > 4096
+        nchunks = -(-B // 8)
+        assert nchunks == 15 and nchunks * 289 > 4096 >= -(-nchunks // 2) * 289 and 14 * 289 <= 4096
+    rng = np.random.default_rng(100000 * B + 1000 * H + W)
+    a = rng.random((B, H, W, 32)).astype(np.float32)
+    a[0] *= np.float32(3.0)
+    zero = B - 1 if B > 1 else None
+    if zero is not None:
+        a[zero] = 0
+    sc = rng.random((B, H, W, 32)).astype(np.float32) if residual else None
+    ref64 = _layer(a, k, s1, t1, sc, s2, t2, np.float64)
+    ref32 = _layer(a, k, s1, t1, sc, s2, t2, np.float32)
+    rc, got, same_bits = _run_row(row_layer, a, sc)
+    _lib.check(rc)
+    assert np.isfinite(got).all()
+    assert same_bits
+    scale = np.abs(ref64).max()
+    err = np.abs(got - ref64)
+    e_gpu = err.max() / scale
+    e_cpu = np.abs(ref32 - ref64).max() / scale
+    worst = np.unravel_index(np.argmax(err), err.shape)
+    print('fftconv geometry %dx%dx%d residual=%s: e_gpu %.3g  e_cpu(f32 direct) %.3g  worst (b, h, w, c) %s' %
+          (B, H, W, residual, e_gpu, e_cpu, worst))
+    assert e_gpu < 1e-5, (e_gpu, worst)
+    assert e_gpu <= 2.5 * e_cpu + 2.4e-7, (e_gpu, e_cpu, worst)
+    if zero is not None:
+        z = 1.0 / (1.0 + np.exp(-t1.astype(np.float64)))
+        if residual:
+            z = (z + sc[zero].astype(np.float64)) * s2 + t2
+        assert np.abs(ref64[zero] - z).max() <= 1e-12 * scale
+        e_zero = np.abs(got[zero] - z).max() / scale
+        print('    the all-zero window: e_gpu %.3g' % e_zero)
+        assert e_zero <= 2.5 * e_cpu + 2.4e-7, (e_zero, e_cpu)
+
+
+def test_fftconv_refusals(row_layer):
+    """H = 21 and W = 562 answer AMT_E_UNSUPPORTED and a workspace one byte short AMT_E_NOMEM -- each from the argument
+    checks at the head of amt_fftconv_run, before its first launch (the checks stand in front of the forward transform
+    in the entry's code); the output is not touched."""
+    import torch
+    from amt_saga import _lib
+    lib, h = row_layer[:2]
+    for B, H, W, short, want in ((1, 21, 40, 0, _lib.AMT_E_UNSUPPORTED), (1, 5, 562, 0, _lib.AMT_E_UNSUPPORTED),
+                                 (2, 5, 40, 1, _lib.AMT_E_NOMEM)):
+        a = torch.zeros((B, H, W, 32), device='cuda')
+        out = torch.full_like(a, 7.0)
+        need = lib.amt_fftconv_workspace_bytes(B, H)
+        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device='cuda')
+        rc = lib.amt_fftconv_run(h, a.data_ptr(), None, B, H, W, out.data_ptr(), ws.data_ptr(), need - short, 1, None)
+        torch.cuda.synchronize()
+        assert rc == want, (B, H, W, short, rc)
+        assert bool((out == 7.0).all())
